@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """DiffusionVID-R101 x1 inference throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one pass of the whole hot path over one synthetic video: L = 304 frames of 1000x600
@@ -124,6 +124,32 @@ def run_video(model, ds, device):
     return results
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, results, suffix=""):
+    """--dump-outputs: the detections one step returned to its caller (run_video: frame -> BoxList), frames in order, as
+    out_dir/<name><suffix>.npy -- boxes [N, 4] float32 (xyxy pixels), scores [N] float32, labels [N] float64, frame [N] float64
+    (the frame each detection belongs to), detections_per_frame [F] float64 and image_size [F, 2] float64 (width, height).
+    A 304-frame video is a few MB; should a run exceed DUMP_LIMIT_BYTES, a fixed seeded sample of its frames is written."""
+    import numpy as np
+    frames = sorted(results)
+    per_frame = 8 * (2 + 7 * max([len(results[f]) for f in frames] + [1]))
+    if per_frame * len(frames) > DUMP_LIMIT_BYTES:
+        keep = np.random.RandomState(0).choice(len(frames), DUMP_LIMIT_BYTES // per_frame, replace=False)
+        frames = [frames[i] for i in sorted(keep)]
+    bls = [results[f] for f in frames]
+    arrays = {"boxes": torch.cat([b.bbox.reshape(-1, 4) for b in bls]).to(torch.float32),
+              "scores": torch.cat([b.get_field("scores") for b in bls]).to(torch.float32),
+              "labels": torch.cat([b.get_field("labels") for b in bls]).to(torch.float64),
+              "frame": torch.cat([torch.full((len(b),), float(f), dtype=torch.float64) for f, b in zip(frames, bls)]),
+              "detections_per_frame": torch.tensor([len(b) for b in bls], dtype=torch.float64),
+              "image_size": torch.tensor([list(b.size) for b in bls], dtype=torch.float64).reshape(-1, 2)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a.cpu().numpy())
+
+
 def cpu_baseline(cfg, sd, frames, height, width):
     """Oracle (CPU port) on one steady-state 8-frame batch after a warm-up batch; returns dict for the JSON line."""
     from oracle import backbone_r101, detector as odet
@@ -195,6 +221,7 @@ def _decode_u8(path):
 
 
 _FEED_SHM = None
+FEED_WAIT_S = 60          # longest wait for one decoded frame of the feed-rate pool before the measurement is given up
 
 
 def _feed_attach(name):
@@ -243,6 +270,9 @@ def real_data_feed_rate(device, n_files=48, passes=4, feed_workers=None):
         # decode workers: the reference's 16 (configs/vid_R_101_DiffusionVID.yaml:69) and, when the host has them, 32 / 64 / 128 --
         # the knee is where the pool stops scaling; --feed-workers N measures one setting only
         cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 2)
+        quota = comm.cpu_quota()
+        if quota:          # the CPUs the container may run on at a time: a larger pool only queues, and forks that many more processes
+            cpus = min(cpus, max(2, int(quota)))
         sweep = [w for w in (feed_workers or (16, 32, 64, 128)) if w <= max(1, cpus - 1)] or [max(1, cpus - 1)]
         rates = {}
         from multiprocessing import shared_memory
@@ -252,12 +282,15 @@ def real_data_feed_rate(device, n_files=48, passes=4, feed_workers=None):
             jobs = [(pth, i) for i, pth in enumerate(paths)]
             for workers in sweep:
                 with mp.get_context("fork").Pool(workers, initializer=_feed_attach, initargs=(shm.name,)) as pool:
-                    pool.map(_decode_into, jobs[:min(workers, len(jobs))])                      # start-up
+                    # every wait is bounded: a worker that dies or never starts would leave a plain map waiting forever
+                    pool.map_async(_decode_into, jobs[:min(workers, len(jobs))]).get(FEED_WAIT_S)          # start-up
                     t0 = time.perf_counter()
                     n = 0
                     reps = max(passes, (6 * workers) // n_files + 1)                  # every worker gets several files
                     for _ in range(reps):
-                        for _slot in pool.imap_unordered(_decode_into, jobs, chunksize=1):
+                        it = pool.imap_unordered(_decode_into, jobs, chunksize=1)
+                        for _job in jobs:
+                            it.next(FEED_WAIT_S)
                             n += 1
                     rates[workers] = n / (time.perf_counter() - t0)
         finally:
@@ -466,7 +499,12 @@ def main():
     ap.add_argument("--dry", action="store_true",
                     help="launcher / collective check without a GPU: every rank fabricates its shard's predictions, the gather to "
                          "rank 0 runs over gloo, and the JSON line reports the ranks seen (tests/test_dist_gloo.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the detections of the last timed step to DIR/<name>.npy (float32 / float64), "
+                         "so that two builds can be compared output for output on the same seeded inputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # One process per GPU (the reference: `python -m torch.distributed.launch --nproc_per_node N tools/test_net.py`,
     # README.md:100-106, mega_core/utils/dist_env.py:18-23).  Started bare with --gpus N > 1, this process becomes the
@@ -564,6 +602,7 @@ def main():
                 r = run_video(model, ds, device)
                 frames += len(r)
                 results.update({k + s * L + rank * steps * L: v.to("cpu") for k, v in r.items()})
+            timed.last_step = r          # what the caller of run_video received in the last timed step (--dump-outputs)
             tg = time.perf_counter()
             if gather and grouped:
                 engine.gather_predictions(results, device=device, always=True)
@@ -611,6 +650,8 @@ def main():
         barrier()
     dt, total_frames = timed(model, ds, args.steps, args.warmup, gather=True)
     host_view = dict(timed.last)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, timed.last_step, "" if world == 1 else "_rank%d" % rank)
 
     # ---- the same workload fed from the HOST: pinned fp32 frames, double-buffered H2D inside the timed region (what the
     # reference's loop times, mega_core/engine/inference.py:29-40) -------------------------------------------------

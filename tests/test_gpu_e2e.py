@@ -30,6 +30,14 @@ from oracle import detector as odet  # noqa: E402
 from oracle import memory as omem  # noqa: E402
 
 
+def _report_path():
+    """reports/parity_report.txt under the repository root, the report every parity line is appended to; the directory is
+    kept out of git, so it is created on first use"""
+    d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "reports")
+    os.makedirs(d, exist_ok=True)
+    return os.path.join(d, "parity_report.txt")
+
+
 def _weights(model, weights="init", **trained_like):
     """"init": random-init heads with box-delta layers x0.1 (class scores 0.010 +- 0.003); "trained_like": additionally class layers
     with a trained detector's score spread (synthetic.trained_like_scores); "untamed": the raw random-init state dict"""
@@ -74,7 +82,7 @@ def _feature_check(tag, model, oracle, bound_max=0.06, bound_rms=0.012):
         assert e_max <= bound_max and e_rms <= bound_rms and abs(gain - 1) <= 2e-3, f"{tag} {lines[-1]}"
     line = f"{tag} backbone features vs oracle ({tuple(o.shape[:1])[0]} frames, rms {rms:.2f}): " + "; ".join(lines)
     print(line)
-    with open("gpurun_out/parity_report.txt", "a") as f:
+    with open(_report_path(), "a") as f:
         f.write(line + "\n")
 
 
@@ -113,9 +121,7 @@ def _stage_check(tag, gpf, opf, gcl, ocl, gbx, obx, frac_ok=0.99, b_logit=0.08, 
     frac = ok.float().mean().item()
     msg += f"; boxes outside a bound {1 - frac:.4%} ({int((~ok).sum())} of {ok.numel()}; bounds |dlogit| {b_logit}, box max({b_px} px, {b_rel:.0%}))"
     print(msg)
-    import os
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/parity_report.txt", "a") as f:
+    with open(_report_path(), "a") as f:
         f.write(msg + "\n")
     assert frac >= frac_ok, msg
     return frac
@@ -246,7 +252,7 @@ def _threshold_aware_detections(tag, o_logits, o_boxes, g_logits, g_boxes, w, h,
             f"max {used_ds.max():.2e}; box difference / max(0.5 px, 1 %) median {np.median(used_db):.2f} p99 {np.quantile(used_db, 0.99):.2f} max {used_db.max():.2f}; "
             f"beyond |dscore| {tol_s:g} or the box bound: {n_out} = {n_out / max(1, int(box_used.sum())):.2%} (allowed {max_outlier_frac:.0%})")
     print(dist)
-    with open("gpurun_out/parity_report.txt", "a") as fh:
+    with open(_report_path(), "a") as fh:
         fh.write(dist + "\n")
     assert n_out <= max_outlier_frac * max(1, int(box_used.sum())), f"{tag}: {n_out} of {int(box_used.sum())} candidate box slots differ beyond the stated tolerances"
     ok_box = box_used & ~outlier
@@ -364,7 +370,7 @@ def _threshold_aware_detections(tag, o_logits, o_boxes, g_logits, g_boxes, w, h,
             f"{n_open} excluded as within a band of the top-{M} / IoU {iou_thr} thresholds ({n_open / max(1, n_open + n_decided):.1%}); "
             f"kept pairs: max |dscore| = {worst_s:.2e}, max box error / bound = {worst_b:.2f}")
     print(line)
-    with open("gpurun_out/parity_report.txt", "a") as fh:
+    with open(_report_path(), "a") as fh:
         fh.write(line + "\n")
     assert worst_s <= spec_tol_s and worst_b <= 1.0, line
     return n_decided, n_open
@@ -472,7 +478,7 @@ def test_video_e2e(sample_step, noise, dtype):
     assert min(rates) >= 0.9
     ap = _ap50_vs_oracle(ref_out, got_out, (W0, H0))
     print(f"[x{sample_step}] VID AP50 of the GPU detections with the oracle's detections as ground truth: {ap:.4f}")
-    with open("gpurun_out/parity_report.txt", "a") as f:
+    with open(_report_path(), "a") as f:
         f.write(f"[x{sample_step}] AP50(GPU | oracle detections as ground truth) = {ap:.4f}\n")
     assert ap >= 0.95
     for g in got_out:
@@ -532,7 +538,7 @@ def test_video_e2e_untamed_box_deltas(sample_step):
     line = (f"{tag} detections kept {[len(g) for g in got_out]} vs oracle {[len(r['scores']) for r in ref_out]}; match "
             f"{['%.2f' % r for r in rates]}; AP50(GPU | all oracle detections) = {ap:.4f}; AP50(GPU | the oracle's {n_obj} objects, score >= 0.5) = {ap_obj:.4f}")
     print(line)
-    with open("gpurun_out/parity_report.txt", "a") as f:
+    with open(_report_path(), "a") as f:
         f.write(line + "\n")
     model.debug_taps = {}
     _final_stage_vs_oracle(model, oracle, L, W0, H0, sample_step, tag, min_decided=UNTAMED[sample_step]["decided"], max_outlier_frac=UNTAMED[sample_step]["outliers"],
@@ -785,12 +791,12 @@ def test_video_e2e_full_configuration(arch, sample_step, weights, dtype):
     top = [float(torch.as_tensor(r["scores"]).max()) if len(r["scores"]) else 0.0 for r in ref_out]
     print(f"{tag} detections kept {[len(g) for g in got_out]} vs oracle {[len(r['scores']) for r in ref_out]} (oracle top scores "
           f"{['%.2f' % t for t in top]}); match {['%.2f' % r for r in rates]}; AP50(GPU | oracle) = {ap:.4f}")
-    with open("gpurun_out/parity_report.txt", "a") as f:
+    with open(_report_path(), "a") as f:
         f.write(f"{tag} AP50(GPU | oracle detections as ground truth) = {ap:.4f}; match rates {['%.2f' % r for r in rates]}\n")
     ap_obj, n_obj = _ap50_on_objects(ref_out, got_out, (W0, H0))
     line = f"{tag} AP50(GPU | the oracle's {n_obj} objects = detections with score >= 0.5) = {ap_obj:.4f}"
     print(line)
-    with open("gpurun_out/parity_report.txt", "a") as f:
+    with open(_report_path(), "a") as f:
         f.write(line + "\n")
     g = (TRAINED_LIKE_F32 if f32 else TRAINED_LIKE)[(arch, sample_step)] if weights == "trained_like" else {"decided": 0.1, "outliers": 0.01, "ap": 0.95, "match": 0.9}
     sb.pop("b_feat", None)
@@ -908,7 +914,7 @@ def test_video_e2e_fp16_policy_oracle_bench_regime(full):
                  f"AP50(GPU | fp32 oracle) = {ap_32:.4f}")
         ok = ok and e_g.median() <= 1.5 * e_p.median() and e_g.quantile(0.99) <= 1.5 * e_p.quantile(0.99) and ap_16 >= ap_pol - 0.05
     print(line)
-    with open("gpurun_out/parity_report.txt", "a") as f:
+    with open(_report_path(), "a") as f:
         f.write(line + "\n")
     assert ok, line
 
@@ -1056,7 +1062,7 @@ def test_streaming_mode_online_memory_update(free_running):
         mem_close.append((torch.cdist(om, gm).min(dim=1).values < 0.5).float().mean().item())
     print(f"[streaming{' free-running' if free_running else ''}] match rates min {min(rates):.2f} mean {sum(rates) / len(rates):.3f}; memory rows with a GPU twin: "
           f"first {mem_close[0]:.3f} last {mem_close[-1]:.3f} min {min(mem_close):.3f}")
-    with open("gpurun_out/parity_report.txt", "a") as f:
+    with open(_report_path(), "a") as f:
         f.write(f"[streaming INFER_BATCH=1, online memory{', free-running (own memory over 30 calls)' if free_running else ''}] detections matched min {min(rates):.2f} mean {sum(rates) / len(rates):.3f}; "
                 f"memory twins first {mem_close[0]:.3f} last {mem_close[-1]:.3f}\n")
     if free_running:
@@ -1449,7 +1455,7 @@ def test_x4_free_running_divergence_belongs_to_the_precision_policy(full):
             f"fp16-policy oracle {['%.2f' % v for v in r['m_pol']]}; GPU vs fp16-policy oracle {['%.2f' % v for v in r['m_gp']]}; AP50 over the fp32 oracle's objects: "
             f"GPU {r['ap_gpu']:.4f}, fp16-policy oracle {r['ap_pol']:.4f}; AP50 over all its detections: GPU {r['ap_all_gpu']:.4f}, fp16-policy oracle {r['ap_all_pol']:.4f}")
     print(line)
-    with open("gpurun_out/parity_report.txt", "a") as f:
+    with open(_report_path(), "a") as f:
         f.write(line + "\n")
     assert r["n_obj"] >= 4
     assert float(np.mean(r["m_gpu"])) >= float(np.mean(r["m_pol"])) - 0.1 and r["ap_gpu"] >= r["ap_pol"] - 0.1 and r["ap_all_gpu"] >= r["ap_all_pol"] - 0.1, line
@@ -1482,7 +1488,7 @@ def test_x4_free_running_statistics():
         line = (f"[x4 statistics, video {v}] {r['n_obj']} objects; AP50 over the fp32 oracle's objects: GPU {r['ap_gpu']:.4f}, fp16-policy oracle {r['ap_pol']:.4f}; "
                 f"mean match with the fp32 oracle: GPU {np.mean(r['m_gpu']):.3f}, policy {np.mean(r['m_pol']):.3f}; GPU vs policy {np.mean(r['m_gp']):.3f}")
         print(line)
-        with open("gpurun_out/parity_report.txt", "a") as f:
+        with open(_report_path(), "a") as f:
             f.write(line + "\n")
     ap_gpu, ap_pol = float(np.mean([r["ap_gpu"] for r in rows])), float(np.mean([r["ap_pol"] for r in rows]))
     m_gpu, m_pol = float(np.mean([np.mean(r["m_gpu"]) for r in rows])), float(np.mean([np.mean(r["m_pol"]) for r in rows]))
@@ -1490,7 +1496,7 @@ def test_x4_free_running_statistics():
     line = (f"[x4 statistics, {len(rows)} videos, {n_obj} objects] mean AP50 over the fp32 oracle's objects: GPU {ap_gpu:.4f} (sd {np.std([r['ap_gpu'] for r in rows]):.3f}), "
             f"fp16-policy oracle {ap_pol:.4f} (sd {np.std([r['ap_pol'] for r in rows]):.3f}); mean match: GPU {m_gpu:.3f}, policy {m_pol:.3f}")
     print(line)
-    with open("gpurun_out/parity_report.txt", "a") as f:
+    with open(_report_path(), "a") as f:
         f.write(line + "\n")
     assert n_obj >= 100
     assert ap_gpu >= ap_pol - 0.07 and m_gpu >= m_pol - 0.07, line
@@ -1512,7 +1518,7 @@ def test_x4_free_running_statistics_float32():
         line = (f"[x4 statistics, DTYPE float32, video {v}] {r['n_obj']} objects; AP50 over the fp32 oracle's objects: GPU {r['ap_gpu']:.4f}; over all its "
                 f"detections {r['ap_all_gpu']:.4f}; per-frame match {['%.2f' % m for m in r['m_gpu']]}")
         print(line)
-        with open("gpurun_out/parity_report.txt", "a") as f:
+        with open(_report_path(), "a") as f:
             f.write(line + "\n")
     ap_gpu = float(np.mean([r["ap_gpu"] for r in rows]))
     m_gpu = float(np.mean([np.mean(r["m_gpu"]) for r in rows]))
@@ -1520,7 +1526,7 @@ def test_x4_free_running_statistics_float32():
     line = (f"[x4 statistics, DTYPE float32, {len(rows)} videos, {n_obj} objects] mean AP50 over the fp32 oracle's objects: GPU {ap_gpu:.4f} "
             f"(min {min(r['ap_gpu'] for r in rows):.4f}); mean match {m_gpu:.3f}")
     print(line)
-    with open("gpurun_out/parity_report.txt", "a") as f:
+    with open(_report_path(), "a") as f:
         f.write(line + "\n")
     assert n_obj >= 100
     assert ap_gpu >= 0.99 and m_gpu >= 0.95, line

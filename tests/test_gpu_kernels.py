@@ -29,6 +29,14 @@ def dv():
 REPORT = []
 
 
+def _report_path():
+    """reports/parity_report.txt under the repository root, the report every parity line is appended to; the directory is
+    kept out of git, so it is created on first use"""
+    d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "reports")
+    os.makedirs(d, exist_ok=True)
+    return os.path.join(d, "parity_report.txt")
+
+
 def check(name, got, want, rtol, atol_rms):
     got = got.detach().float().cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got, dtype=np.float32)
     want = want.detach().float().cpu().numpy() if isinstance(want, torch.Tensor) else np.asarray(want, dtype=np.float32)
@@ -40,8 +48,7 @@ def check(name, got, want, rtol, atol_rms):
     line = f"{name}: max_abs={err.max():.3e} rms_ref={rms:.3e} worst/bound={worst:.3f} nan={int(np.isnan(got).sum())}"
     REPORT.append(line)
     print(line)
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/parity_report.txt", "a") as f:
+    with open(_report_path(), "a") as f:
         f.write(line + "\n")
     assert not np.isnan(got).any(), f"{name}: NaN in output"
     assert worst <= 1.0, line
