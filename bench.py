@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """DiffusionVID-R101 x1 inference throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 3 --warmup 1 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 3 --warmup 1 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one pass of the whole hot path over one synthetic video: L = 304 frames of 1000x600
@@ -17,7 +17,11 @@ Schedule: INPUT.LOOKAHEAD_BATCHES (--lookahead, default 38 = the whole 304-frame
 every stage is per-frame independent given the video's global memory, so the group shares its launches and its one
 host sync; --lookahead 1 is the reference's schedule and gives the same detections (tests/test_gpu_e2e.py::test_lookahead_batches_do_not_change_results).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else runs.  --full adds
+every other measurement below (each with runs of its own, several minutes); --no-host-fed, --no-side-configs, ... skip single
+ones of them.
+
+Extra objects on the JSON line (--full only; null or empty otherwise):
   roofline     the dominant kernels are the implicit-GEMM MFMA conv/linear kernels (igemm2_kernel<...>, and conv3x3_* for the
                3x3 / stride-1 layers; ~80 % of the GPU time, profiles/r02d_kernel_stats.txt).  An instrumented repeat of one
                step right after the timed region brackets every such launch with HIP events on its launch stream (sub-batch
@@ -471,6 +475,10 @@ def main():
     ap.add_argument("--sample-step", type=int, default=1, help="MODEL.DiffusionDet.SAMPLE_STEP (4 = the x4 configuration)")
     ap.add_argument("--skip-unobservable", action="store_true",
                     help="MODEL.DiffusionDet.SKIP_UNOBSERVABLE for the main measurement (x4 only; SURVEY.md Appendix B)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement also run the others reported inside the line: roofline (instrumented repeat), host-fed, "
+                         "reference protocol / x4 / Swin-B / float32 / streaming configurations, the VID-val-shaped set, the real-data feed rate and the "
+                         "CPU baseline (the --no-* options below skip single ones of them); a plain run does only what the headline figure needs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="set a library option (csrc/options.h; A/B runs -- tools/ab_bench.sh): the line's build.library_config echoes the table, "
@@ -656,7 +664,7 @@ def main():
     # ---- the same workload fed from the HOST: pinned fp32 frames, double-buffered H2D inside the timed region (what the
     # reference's loop times, mega_core/engine/inference.py:29-40) -------------------------------------------------
     host_fed = None
-    if not args.no_host_fed:
+    if args.full and not args.no_host_fed:
         from diffusionvid_amd.data.prefetch import HostFedVideo
         hds = SyntheticVIDDataset([L], cfg, height=H, width=W, device="cpu", video_base=rank, emit_ref_ahead=False)
         # cyclic: the pass after the last group is the same video again, as in a stream of videos -- its first group is
@@ -778,12 +786,13 @@ def main():
              "kernel_ms_per_step": round(ms.value, 2)}
         return r
 
-    roofline = measure_roofline(model, ds, args.arch, args.sample_step, total_frames / dt, L, args.lookahead)
+    roofline = measure_roofline(model, ds, args.arch, args.sample_step, total_frames / dt, L, args.lookahead) if args.full else None
 
     # ---- the reference's own call protocol (no look-ahead hand-over from the dataset) and the other single-GPU
     # configurations of BASELINE.json, each with its own model; reported inside the same line ---------------------
-    sd_cpu = {k: v.detach().cpu() for k, v in model.state_dict().items()} if (rank == 0 and headline) else None
-    frames8 = [ds.frame(0, i).tensors.cpu() for i in range(8, 24)] if (rank == 0 and headline) else None
+    with_cpu_baseline = args.full and world == 1 and headline and not args.no_cpu_baseline
+    sd_cpu = {k: v.detach().cpu() for k, v in model.state_dict().items()} if with_cpu_baseline else None
+    frames8 = [ds.frame(0, i).tensors.cpu() for i in range(8, 24)] if with_cpu_baseline else None
     infer_batch = cfg.INPUT.INFER_BATCH
     release(model)
     del model
@@ -820,7 +829,7 @@ def main():
                 for kv in args.option:
                     ops.set_option(kv.partition("=")[0], int(kv.partition("=")[2]))
 
-    if not args.no_side_configs:
+    if args.full and not args.no_side_configs:
         side("reference_protocol_lookahead_1", args.arch, args.sample_step, 1, 5, with_roofline=True)
         if headline and world == 1:
             side("r101_x4", "r101", 4, 38, 5, with_roofline=True)
@@ -847,8 +856,8 @@ def main():
                       "by farthest-point sampling and finishes the frame; ms_per_frame is the per-call latency")
 
     # BASELINE.json configs[4] inside the same line: the VID-val-shaped set sharded over the ranks by whole videos (strong scaling).
-    # N > 1: the whole 555-video set; one rank: its first 60 videos (so that the default run stays within minutes).
-    if headline and not args.no_side_configs and not args.no_vidval:
+    # N > 1: the whole 555-video set; one rank: its first 60 videos (so that a --full run stays within minutes).
+    if args.full and headline and not args.no_side_configs and not args.no_vidval:
         try:
             import copy
             a2 = copy.copy(args)
@@ -861,7 +870,7 @@ def main():
             others["vidval"] = {"error": repr(e)[:300]}
 
     feed = None
-    if rank == 0 and headline and not grouped and not args.no_feed_rate:          # (forks decode workers: single-process runs only)
+    if args.full and rank == 0 and headline and not grouped and not args.no_feed_rate:          # (forks decode workers: single-process runs only)
         try:
             feed = real_data_feed_rate(device, feed_workers=(args.feed_workers,) if args.feed_workers > 0 else None)
         except Exception as e:
@@ -873,6 +882,7 @@ def main():
             "value": round(total_frames / dt, 2), "unit": "frames/sec", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32" if args.dtype == "float32" else "f16", "data": "synthetic",
+            "full": args.full,          # false: the headline alone; roofline, host_fed, real_data_feed, other_configs, cpu_baseline need --full
             "config": {"workload": "%s DiffusionVID x%d %s, 300 boxes, %d DDIM step(s); one step = one synthetic "
                                    "%d-frame 1000x600 video per GPU (24 global + %d local frames, %d batches of %d)"
                                    % ("ResNet-101" if args.arch == "r101" else "Swin-Base", args.sample_step, "fp32" if args.dtype == "float32" else "fp16",
@@ -902,7 +912,7 @@ def main():
             "real_data_feed": feed,
             "other_configs": others,
         }
-        if world == 1 and headline and not args.no_cpu_baseline:
+        if with_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, sd_cpu, frames8, H, W)
             line["gpu_over_cpu"] = round(line["value"] / max(line["cpu_baseline"]["value"], 1e-9), 1)
         print(json.dumps(line), flush=True)

@@ -87,6 +87,36 @@ def test_bench_under_torchrun_one_rank_runs_the_rccl_gather():
     assert line["host_view"]["gather_ms_max_over_ranks"] > 0
 
 
+def test_plain_bench_run_measures_the_headline_only(tmp_path):
+    """bench.py without --full: set-up, warm-up, the timed steps, --dump-outputs and the line -- no roofline pass, host-fed run,
+    side configuration, VID-val-shaped set, feed rate or CPU baseline (those are --full's)."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--frames", "32", "--lookahead", "2", "--steps", "1", "--warmup", "1",
+           "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith('{"metric"')][-1])
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 1 and line["warmup"] == 1 and line["full"] is False
+    assert line["roofline"] is None and line["host_fed"] is None and line["real_data_feed"] is None and line["other_configs"] == {}
+    assert "cpu_baseline" not in line
+    import numpy as np
+    per_frame = np.load(tmp_path / "detections_per_frame.npy")
+    assert len(per_frame) == 32 and np.load(tmp_path / "boxes.npy").shape == (int(per_frame.sum()), 4)
+
+
+def test_full_bench_run_keeps_the_roofline():
+    """bench.py --full still runs what moved behind it: here the instrumented roofline repeat (the other parts skipped by their
+    --no-* options), reported inside the same line as the headline."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--frames", "32", "--lookahead", "2", "--steps", "1", "--warmup", "1",
+           "--full", "--no-side-configs", "--no-host-fed", "--no-feed-rate", "--no-cpu-baseline"]
+    out = subprocess.run(cmd, env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith('{"metric"')][-1])
+    assert line["value"] > 0 and line["full"] is True
+    roof = line["roofline"]
+    assert roof is not None and roof["bound"] == "mfma" and roof["launches_per_step"] > 0 and roof["kernel_ms_per_step"] > 0
+    assert roof["top_kernels"]["kernels"]
+
+
 def test_vidval_workload_twelve_videos_end_to_end():
     """bench.py --workload vidval --videos 12: ragged video lengths (87 .. 820 frames), per-video memory builds, engine-built
     look-ahead groups with ragged tails, one rank, predictions of every frame accounted for (the line's own assertion)."""

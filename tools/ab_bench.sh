@@ -3,7 +3,7 @@
 # prints value / ms_per_step / family frac and the five heaviest kernel groups per run
 var=$1; vals=$2; shift 2
 for v in $vals; do
-  python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-host-fed --no-side-configs --option $var=$v "$@" 2>/dev/null > /tmp/ab_line.json
+  python bench.py --steps 8 --warmup 2 --full --no-cpu-baseline --no-host-fed --no-side-configs --option $var=$v "$@" 2>/dev/null > /tmp/ab_line.json
   python - "$var" "$v" <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab_line.json"))

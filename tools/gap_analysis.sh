@@ -3,8 +3,8 @@
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 export DVID_IGEMM_TUNE_CACHE=/tmp/dvid_tune_cache_gap.txt
-python $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline "$@" > /tmp/gap_pre.log 2>&1
-rocprofv3 --kernel-trace --output-format csv -d /tmp/gap_prof -o g -- python $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline "$@" > /tmp/gap.log 2>&1
+python $REPO/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline "$@" > /tmp/gap_pre.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/gap_prof -o g -- python $REPO/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline "$@" > /tmp/gap.log 2>&1
 python - <<'PY'
 import csv, glob, collections
 f = glob.glob("/tmp/gap_prof/**/*kernel_trace.csv", recursive=True)[0]

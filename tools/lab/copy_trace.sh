@@ -7,7 +7,7 @@ OUT=$REPO/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export DVID_IGEMM_TUNE_CACHE=/tmp/dvid_tune_cache.txt
-CMD="python $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed --no-side-configs --no-feed-rate $*"
+CMD="python $REPO/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-host-fed --no-side-configs --no-feed-rate $*"
 $CMD > /tmp/pre.log 2>&1
 rm -rf /tmp/ct; rocprofv3 --kernel-trace --output-format csv -d /tmp/ct -o ct -- $CMD > /tmp/ct.log 2>&1
 grep '^{"metric"' /tmp/ct.log | tail -1 > $OUT/copy_trace_bench.json

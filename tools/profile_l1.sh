@@ -10,7 +10,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export DVID_IGEMM_TUNE_CACHE=/tmp/dvid_tune_cache_l1.txt
 rm -f $DVID_IGEMM_TUNE_CACHE
-CMD="python $REPO/bench.py --lookahead 1 --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed --no-side-configs"
+CMD="python $REPO/bench.py --lookahead 1 --steps 2 --warmup 1 --full --no-cpu-baseline --no-host-fed --no-side-configs"
 $CMD > /tmp/l1_pre.log 2>&1
 grep '^{"metric"' /tmp/l1_pre.log | tail -1 > $OUT/${TAG}_l1_bench.json
 python $REPO/tools/profile_host.py 1 > $OUT/${TAG}_l1_host.txt 2>&1
@@ -22,7 +22,7 @@ f = glob.glob("/tmp/prof_l1/**/*kernel_stats.csv", recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 tot = sum(float(r["TotalDurationNs"]) for r in rows)
 with open(f"{out}/{tag}_l1_kernel_stats.txt", "w") as o:
-    o.write("# rocprofv3 --kernel-trace --stats -- python bench.py --lookahead 1 --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed --no-side-configs\n")
+    o.write("# rocprofv3 --kernel-trace --stats -- python bench.py --lookahead 1 --steps 2 --warmup 1 --full --no-cpu-baseline --no-host-fed --no-side-configs\n")
     o.write("# (6 videos of 304 frames: set-up, warm-up, 2 timed steps, chains=1 pass and instrumented pass; sub-batch chains on except in the last two)\n")
     o.write("total kernel time %.1f ms over 6 videos = %.1f ms per video\n" % (tot / 1e6, tot / 6e6))
     for r in rows[:45]:

@@ -5,7 +5,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $REPO/bench.py --lookahead 1 --steps 1 --warmup 1 --no-cpu-baseline --no-host-fed --no-side-configs --no-feed-rate"
+CMD="python $REPO/bench.py --lookahead 1 --steps 1 --warmup 1 --full --no-cpu-baseline --no-host-fed --no-side-configs --no-feed-rate"
 export DVID_IGEMM_TUNE_CACHE=/tmp/dvid_tune_cache_l1.txt
 rm -f $DVID_IGEMM_TUNE_CACHE
 $CMD > /tmp/prof_pre.log 2>&1
@@ -18,7 +18,7 @@ f = glob.glob("/tmp/prof_l1/**/*kernel_stats.csv", recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 tot = sum(float(r["TotalDurationNs"]) for r in rows)
 with open(f"{out}/{tag}_kernel_stats_lookahead1.txt", "w") as o:
-    o.write("# rocprofv3 --kernel-trace --stats -- python bench.py --lookahead 1 --steps 1 --warmup 1 (one 8-frame batch per call; the process runs ~5 videos of 304 frames)\n")
+    o.write("# rocprofv3 --kernel-trace --stats -- python bench.py --lookahead 1 --steps 1 --warmup 1 --full (one 8-frame batch per call; the process runs ~5 videos of 304 frames)\n")
     o.write("total kernel time %.1f ms over %d launches\n" % (tot / 1e6, sum(int(r["Calls"]) for r in rows)))
     for r in rows[:45]:
         o.write("%-100s calls %7s total %9.2f ms avg %9.1f us %5.1f%%\n" % (r["Name"][:100], r["Calls"], float(r["TotalDurationNs"]) / 1e6, float(r["AverageNs"]) / 1e3, float(r["Percentage"])))

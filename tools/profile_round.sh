@@ -17,7 +17,7 @@ OUT=$REPO/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export DVID_CHAINS=1            # sequential launches: per-kernel durations are not inflated by overlap
-CMD="python $REPO/bench.py --arch $ARCH --sample-step $SS --lookahead $LA --dtype $DT --steps 1 --warmup 1 --no-cpu-baseline --no-host-fed --no-side-configs --no-feed-rate"
+CMD="python $REPO/bench.py --arch $ARCH --sample-step $SS --lookahead $LA --dtype $DT --steps 1 --warmup 1 --full --no-cpu-baseline --no-host-fed --no-side-configs --no-feed-rate"
 # tile-tuner timing launches would pollute the statistics: fill the tuning cache in an unprofiled run first
 export DVID_IGEMM_TUNE_CACHE=/tmp/dvid_tune_cache.txt
 rm -f $DVID_IGEMM_TUNE_CACHE
@@ -37,7 +37,7 @@ rows = list(csv.DictReader(open(f)))
 tot = sum(float(r["TotalDurationNs"]) for r in rows)
 with open(f"{out}/{tag}_kernel_stats_{suf}.txt", "w") as o:
     o.write("# configuration " + suf + "\n")
-    o.write("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-host-fed --no-side-configs  (DVID_CHAINS=1; 5 videos of 304 frames:\n")
+    o.write("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-host-fed --no-side-configs  (DVID_CHAINS=1; 5 videos of 304 frames:\n")
     o.write("# set-up, warm-up, timed step, chains=1 pass and instrumented pass)\n")
     o.write("total kernel time %.1f ms\n" % (tot / 1e6))
     ig = [r for r in rows if "igemm2_kernel" in r["Name"] or "f32_igemm_kernel" in r["Name"] or "f32x3_igemm_kernel" in r["Name"] or "conv3x3_" in r["Name"] or "conv4x4_" in r["Name"] or "stem_pool" in r["Name"] or "wstat" in r["Name"] or "bneck" in r["Name"]]
@@ -78,7 +78,7 @@ if res["FETCH_SIZE"][1] and res["WRITE_SIZE"][1]:
                "mfma_busy_method": "sum(SQ_VALU_MFMA_BUSY_CYCLES) / 1024 SIMDs over sum(GRBM_GUI_ACTIVE) / 8 XCDs, implicit-GEMM launches only",
                "fetch_bytes_per_launch_corrected": fetch, "write_bytes_per_launch": write, "hbm_bytes_per_launch": fetch + write,
                "method": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --steps 1 "
-                         "--warmup 0 --no-cpu-baseline --no-host-fed --no-side-configs (the bench workload itself, 304-frame videos), DVID_CHAINS=1; KiB units; FETCH_SIZE doubled per MI355X_MICROARCH.md "
+                         "--warmup 0 --full --no-cpu-baseline --no-host-fed --no-side-configs (the bench workload itself, 304-frame videos), DVID_CHAINS=1; KiB units; FETCH_SIZE doubled "
                          "(gfx950 counts 128-B requests at 64 B); WRITE_SIZE uncorrected", "round": int(tag[1:3]) if tag[1:3].isdigit() else None},
               open(f"{out}/{tag}_pmc_igemm_traffic_{suf}.json", "w"), indent=1)
 else:

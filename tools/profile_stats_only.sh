@@ -7,7 +7,7 @@ OUT=$REPO/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export DVID_CHAINS=1
-CMD="python $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-host-fed --no-side-configs"
+CMD="python $REPO/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-host-fed --no-side-configs"
 export DVID_IGEMM_TUNE_CACHE=/tmp/dvid_tune_cache.txt
 rm -f $DVID_IGEMM_TUNE_CACHE
 $CMD > /tmp/prof_pre.log 2>&1
@@ -20,7 +20,7 @@ f = glob.glob("/tmp/prof_stats/**/*kernel_stats.csv", recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 tot = sum(float(r["TotalDurationNs"]) for r in rows)
 with open(f"{out}/{tag}_kernel_stats.txt", "w") as o:
-    o.write("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-host-fed --no-side-configs  (DVID_CHAINS=1; 5 videos of 304 frames:\n")
+    o.write("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-host-fed --no-side-configs  (DVID_CHAINS=1; 5 videos of 304 frames:\n")
     o.write("# set-up, warm-up, timed step, chains=1 pass and instrumented pass)\n")
     o.write("total kernel time %.1f ms\n" % (tot / 1e6))
     ig = [r for r in rows if "igemm2_kernel" in r["Name"] or "conv3x3_" in r["Name"] or "wstat" in r["Name"] or "bneck64" in r["Name"]]
