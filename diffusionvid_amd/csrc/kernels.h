@@ -85,7 +85,25 @@ int dvid_roialign_launch(const RoiLevels& lv, int channels, const float* boxes, 
 int dvid_mha_mfma_launch(const half_t* q, const half_t* k, const half_t* v, half_t* out, half_t* vt_scratch, int batch, int lq,
                          int lk, int nheads, int q_ld, int kv_ld, int out_ld, long q_bs, long kv_bs, long out_bs, hipStream_t s);
 
-constexpr int SWIN_RELBIAS_PITCH = 64;      // floats per query row of the relative-position bias table [heads][49][64] (keys 49..63 = 0)
+// localattn.hip: out = LayerNorm(x W^T + bias) over rows of d = 256 as one row kernel (the out-projection of the local box-level attention and
+// the LayerNorm behind it, box_head.py:362-363); the pre-LayerNorm rows stay in registers.
+struct OutProjLnParams {
+    const void* x;          // [rows, 256]: fp16 (mode 0) or fp32 (modes 1, 2)
+    int mode;               // 0: fp16 MFMA; 1: fp32 rows as split (hi, lo) fp16 operands, three fp16-MFMA passes; 2: fp32 MFMA
+    const half_t* wf_hi;    // [256][256] in MFMA fragment order (model.hip: make_frags): the fp16 weights (mode 0) / the hi plane (mode 1)
+    const half_t* wf_lo;    // mode 1: the lo plane, same order
+    const float* w32;       // mode 2: the scaled fp32 rows [256][256]
+    const float* wscale;    // modes 1, 2: [256], channel n's sum is multiplied by wscale[n]
+    const float* bias;      // [256]
+    const float* gamma;     // LayerNorm weight / bias [256]
+    const float* beta;
+    float* out;             // [rows, 256] fp32
+    int rows, d;
+    int* range_flag;        // mode 1: device int or null, ORed with 1 when a row value exceeds the fp16 range
+};
+int dvid_outproj_ln_launch(const OutProjLnParams& p, hipStream_t s);
+
+constexpr int SWIN_RELBIAS_PITCH = 64;     // floats per query row of the relative-position bias table [heads][49][64] (keys 49..63 = 0)
 int dvid_swin_window_attn_launch(const half_t* qkv, const half_t* qkv_bias16, const float* relbias, half_t* out, int batch, int H,
                                  int W, int C, int nheads, int shift, hipStream_t s);
 int dvid_patch_merge_ln_launch(const float* x, const float* g, const float* b, half_t* y16, int B, int H, int W, int C, hipStream_t s,

@@ -296,6 +296,12 @@ struct dvid_model {
     std::vector<HeadW> heads;       // head_series
     std::vector<HeadW> heads_cond;  // head_series_cond
     ConvW gq, gkv, gout;            // global attention projections
+    // local box-level attention (head.local_attention.{i}.*, box_head.py:186-194): only the LAST stage is ever observable (:360-363), so only
+    // its tensors are packed; local_stages = number of stages present (0: the model has none)
+    int local_stages = 0;
+    ConvW lq, lkv, lout;
+    LNW lln;
+    half_t *lout_f = nullptr, *lout_fhi = nullptr, *lout_flo = nullptr;          // out_proj in fragment order: fp16 rows / the (hi, lo) planes (DTYPE float32)
     std::vector<float> tm1_w, tm1_b, tm3_w, tm3_b;  // time_mlp host copies
     std::map<int64_t, std::vector<float>> time_cache;  // t -> time_mlp(t) [4*hidden]
 
@@ -311,6 +317,8 @@ struct dvid_model {
     size_t ss_slab_used = 0;          // rows taken from the last slab
 
     int mem_lk = 0;       // rows of the global memory whose K/V projections sit in kvproj (0: none)
+    DevBuf lkvproj, lmem16;          // K | V rows of the projected local memories, [groups * lk, 2 d]
+    int local_lk = 0, local_groups = 0;          // shape of what lkvproj holds (0: nothing projected)
 
     // sub-batch chains (see dvid_backbone_resnet_fpn)
     int nchain = 2;
@@ -537,6 +545,15 @@ int make_frags(dvid_model* m, const ConvW& w, half_t** out) {
                     dst[(((size_t)nt * ks_n + ks) * 64 + l) * 8 + e] = src[(size_t)row * w.kpad + ks * 16 + (l >> 5) * 8 + e];
             }
     return m->upload(dst.data(), dst.size() * sizeof(half_t), reinterpret_cast<void**>(out));
+}
+
+// the same from a [cout][kpad] fp16 plane that is not a ConvW's `w` (the (hi, lo) planes of the DTYPE float32 weights)
+int make_frags_plane(dvid_model* m, const half_t* plane, int cout, int kpad, half_t** out) {
+    ConvW t;
+    t.w = const_cast<half_t*>(plane);
+    t.cout = cout;
+    t.kpad = kpad;
+    return make_frags(m, t, out);
 }
 
 int make_head(dvid_model* m, const std::string& pfx, bool cond, HeadW* h) {
@@ -1204,7 +1221,7 @@ int dvid_model_destroy(dvid_model* m) {
     for (void* p : m->owned) (void)hipFree(p);
     DevBuf* bufs[] = {&m->img8, &m->bufX, &m->bufY, &m->bufT1, &m->bufT2, &m->bufSC, &m->c3, &m->c4, &m->c5, &m->lat[0], &m->sw_x, &m->sw_x2, &m->sw_ln16, &m->sw_qkv16, &m->sw_attn16, &m->sw_h16,
                       &m->lat[1], &m->lat[2], &m->roi, &m->params, &m->dyn, &m->qkv, &m->attn16, &m->f32a, &m->f32b, &m->f32c,
-                      &m->f32d, &m->h16a, &m->h16b, &m->hid16, &m->ss, &m->deltas, &m->kvproj, &m->mem16, &m->splitk, &m->vt};
+                      &m->f32d, &m->h16a, &m->h16b, &m->hid16, &m->ss, &m->deltas, &m->kvproj, &m->mem16, &m->splitk, &m->vt, &m->lkvproj, &m->lmem16};
     for (DevBuf* b : bufs) b->release();
     for (DevBuf& b : m->ss_slabs) b.release();
     delete m;
@@ -1321,6 +1338,31 @@ int dvid_model_finalize(dvid_model* m) {
         TRY(make_linear(m, "head.global_attention.0.0.in_proj", true, &m->gq, nullptr, 0, d));
         TRY(make_linear(m, "head.global_attention.0.0.in_proj", true, &m->gkv, nullptr, d, 2 * d));
         TRY(make_linear(m, "head.global_attention.0.0.out_proj", true, &m->gout));
+    }
+    // local box-level attention: present when its tensors are (as the global stage above); box_head.py:360-363 overwrites attn_ on every
+    // stage without touching the query, so the last stage alone is computed and earlier stages' tensors are accepted and ignored
+    {
+        int ns = 0;
+        while (m->get("head.local_attention." + std::to_string(ns) + ".0.in_proj_weight")) ++ns;
+        if (ns > 2)
+            FAIL(DVID_ERR_UNSUPPORTED, "%d local attention stages: the reference holds two local memories (box_head.py:338, :362), STAGE > 2 is an error there", ns);
+        if (ns > 0) {
+            const int d = c.hidden_dim;
+            if (d != 256 || c.nheads * 32 != d) FAIL(DVID_ERR_UNSUPPORTED, "local attention is built for hidden_dim 256 / head dim 32");
+            const std::string p = "head.local_attention." + std::to_string(ns - 1);
+            TRY(make_linear(m, p + ".0.in_proj", true, &m->lq, nullptr, 0, d));
+            TRY(make_linear(m, p + ".0.in_proj", true, &m->lkv, nullptr, d, 2 * d));
+            TRY(make_linear(m, p + ".0.out_proj", true, &m->lout));
+            TRY(make_ln(m, p + ".2", &m->lln));
+            if (m->lout.cout != d || m->lout.kpad != d || m->lln.d != d || !m->lout.bias) FAIL(DVID_ERR_ARG, "%s: unexpected out_proj / LayerNorm shape", p.c_str());
+            TRY(make_frags(m, m->lout, &m->lout_f));
+            if (m->precision == 1) {
+                if (m->lout.kpad32 != d) FAIL(DVID_ERR_ARG, "%s: unexpected out_proj packing", p.c_str());
+                TRY(make_frags_plane(m, m->lout.w16hi, d, d, &m->lout_fhi));
+                TRY(make_frags_plane(m, m->lout.w16lo, d, d, &m->lout_flo));
+            }
+        }
+        m->local_stages = ns;
     }
     {
         NEED(w1, "head.time_mlp.1.weight");
@@ -1891,6 +1933,81 @@ int dvid_global_xattn(dvid_model* m, const float* query, int rows, const float* 
     TRY(dvid_mha_mfma_launch(m->h16b.as<half_t>(), kv, kv + d, m->attn16.as<half_t>(), m->vt.as<half_t>(), 1, rows, lk, m->cfg.nheads,
                              d, 2 * d, d, 0, 0, 0, s));
     TRY(linear_run(m->gout, m->attn16.as<half_t>(), rows, out, 0, 1, s));
+    return DVID_OK;
+}
+
+// K/V projections of `groups` local memories of `lk` rows each (box_head.py:338, :362: key = value = proposal_feats_local[stage]) into
+// the model's own buffer: one linear over all groups * lk rows.
+int dvid_local_memory_project(dvid_model* m, int stage, const float* memory, int lk, int groups, void* stream) {
+    g_err[0] = 0;
+    if (!m || !m->finalized || m->local_stages == 0) FAIL(DVID_ERR_STATE, "model not finalized or has no local attention");
+    if (stage != m->local_stages - 1) FAIL(DVID_ERR_ARG, "local attention stage %d: only the last stage (%d) is computed", stage, m->local_stages - 1);
+    if (!memory || lk <= 0 || groups <= 0) FAIL(DVID_ERR_ARG, "empty local memory");
+    if ((long)lk * groups > (1L << 24)) FAIL(DVID_ERR_ARG, "local memory of %d x %d rows", groups, lk);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int d = m->cfg.hidden_dim, n = lk * groups;
+    m->local_lk = m->local_groups = 0;
+    TRY(m->lkvproj.ensure(((size_t)n + 64) * 2 * d * 4, &m->ws_gen));
+    if (m->precision == 1) {
+        TRY(linear_run32(m->lkv, memory, n, m->lkvproj.as<float>(), 0, s));
+    } else {
+        TRY(m->lmem16.ensure((size_t)n * d * 2, &m->ws_gen));
+        TRY(dvid_f32_to_f16_launch(memory, m->lmem16.as<half_t>(), (long)n * d, s));
+        TRY(linear_run(m->lkv, m->lmem16.as<half_t>(), n, m->lkvproj.p, 0, 0, s));
+    }
+    m->local_lk = lk;
+    m->local_groups = groups;
+    return DVID_OK;
+}
+
+// out = LayerNorm(out_proj(MHA(q_proj(query), K, V))), group g's rows / groups queries against group g's lk projected memory rows
+// (box_head.py:360-363).  Q projection and the attention product are the global stage's kernels with batch strides; the out-projection,
+// its bias and the LayerNorm are one launch (csrc/localattn.hip).
+int dvid_local_xattn(dvid_model* m, int stage, const float* query, int rows, int groups, int lk, float* out, void* stream) {
+    g_err[0] = 0;
+    if (!m || !m->finalized || m->local_stages == 0) FAIL(DVID_ERR_STATE, "model not finalized or has no local attention");
+    if (stage != m->local_stages - 1) FAIL(DVID_ERR_ARG, "local attention stage %d: only the last stage (%d) is computed", stage, m->local_stages - 1);
+    if (!query || !out || rows <= 0 || groups <= 0 || rows % groups) FAIL(DVID_ERR_ARG, "%d query rows in %d groups", rows, groups);
+    if (m->local_lk <= 0 || lk != m->local_lk || groups != m->local_groups)
+        FAIL(DVID_ERR_STATE, "no projected local memory of %d x %d rows (call dvid_local_memory_project)", groups, lk);
+    if (rows > m->ws_frames * m->ws_boxes) FAIL(DVID_ERR_STATE, "workspace too small");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int d = m->cfg.hidden_dim, lq = rows / groups;
+    OutProjLnParams p;
+    memset(&p, 0, sizeof(p));
+    p.bias = m->lout.bias;
+    p.gamma = m->lln.g;
+    p.beta = m->lln.b;
+    p.out = out;
+    p.rows = rows;
+    p.d = d;
+    if (m->precision == 1) {
+        float* qp = m->h16a.as<float>();
+        float* at = m->attn16.as<float>();
+        const float* kv32 = m->lkvproj.as<float>();
+        TRY(linear_run32(m->lq, query, rows, qp, 0, s));
+        TRY(dvid_f32_mha_launch(qp, kv32, kv32 + d, at, groups, lq, lk, m->cfg.nheads, d, 2 * d, d, (long)lq * d, (long)lk * 2 * d, (long)lq * d, s));
+        const bool split = g_opt.f32_split != 0 && m->lout_fhi && m->lout_flo;
+        p.x = at;
+        p.mode = split ? 1 : 2;
+        p.wf_hi = m->lout_fhi;
+        p.wf_lo = m->lout_flo;
+        p.w32 = m->lout.w32;
+        p.wscale = m->lout.wscale32;
+        p.range_flag = m->lout.range_flag;
+        TRY(dvid_outproj_ln_launch(p, s));
+        return DVID_OK;
+    }
+    TRY(dvid_f32_to_f16_launch(query, m->h16a.as<half_t>(), (long)rows * d, s));
+    TRY(linear_run(m->lq, m->h16a.as<half_t>(), rows, m->h16b.p, 0, 0, s));
+    const half_t* kv = m->lkvproj.as<half_t>();
+    TRY(m->vt.ensure((size_t)groups * m->cfg.nheads * 32 * (((size_t)lk + 31) / 32 * 32 + 32) * 2, &m->ws_gen));
+    TRY(dvid_mha_mfma_launch(m->h16b.as<half_t>(), kv, kv + d, m->attn16.as<half_t>(), m->vt.as<half_t>(), groups, lq, lk, m->cfg.nheads, d, 2 * d, d,
+                             (long)lq * d, (long)lk * 2 * d, (long)lq * d, s));
+    p.x = m->attn16.p;
+    p.mode = 0;
+    p.wf_hi = m->lout_f;
+    TRY(dvid_outproj_ln_launch(p, s));
     return DVID_OK;
 }
 

@@ -8,7 +8,9 @@ keys of vid_mega.py:236-248, `[]` on calls whose frame_id is not a multiple of I
 ValueError for targets at test time, AssertionError for degenerate predicted boxes.
 
 The video state machine (per-video reset, local frame queue, once-per-video global memory,
-DDIM loop, ensemble) is sequenced here; every numerical step is a HIP kernel launched through
+DDIM loop, ensemble) is sequenced here -- with MODEL.VID.ROI_BOX_HEAD.ATTENTION.ENABLE also the local
+box-level memory (the top-75 / top-25 object features of the frames in the local queue, diffusion_det.py:
+398-400, :507-512), see _local_memory; every numerical step is a HIP kernel launched through
 `ops` on the current stream.  Random draws go through `self.noise_fn(kind, frame_id, step, image,
 shape)` when set (parity/bench), else torch.randn on the device like the reference.
 """
@@ -145,6 +147,11 @@ class DiffusionDet(nn.Module):
         self.num_timesteps = timesteps
         self.sampling_timesteps = d.SAMPLE_STEP
         self.skip_unobservable = bool(getattr(d, "SKIP_UNOBSERVABLE", False)) and d.SAMPLE_STEP > 1
+        # the local box-level branch conditions the last head on the LOCAL frames' top-k features: their extraction pass is observable then
+        # (with the global stage also on, the global product overwrites the local one, box_head.py:366-371, and nothing changes)
+        self.local_active = bool(self.local_box_enable) and not self.global_enable
+        if self.local_active:
+            self.skip_unobservable = False
         assert self.sampling_timesteps <= timesteps
         self.ddim_sampling_eta = 1.0
         self.scale = d.SNR_SCALE
@@ -174,7 +181,8 @@ class DiffusionDet(nn.Module):
                                        dim_ff=d.DIM_FEEDFORWARD, dim_dynamic=d.DIM_DYNAMIC, num_classes=d.NUM_CLASSES,
                                        num_cls=d.NUM_CLS, num_reg=d.NUM_REG, num_heads=d.NUM_HEADS,
                                        num_heads_cond=d.NUM_HEADS_LOCAL, pooler=cfg.MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION,
-                                       prior_prob=d.PRIOR_PROB)
+                                       prior_prob=d.PRIOR_PROB,
+                                       local_stages=int(cfg.MODEL.VID.ROI_BOX_HEAD.ATTENTION.STAGE) if self.local_box_enable else 0)
         self.head = DynamicHead(cfg, None, engine_provider=self._get_engine)
         self.num_heads_local = self.head.num_heads_local
         self.top_k = self.head.top_k
@@ -303,6 +311,7 @@ class DiffusionDet(nn.Module):
         self.local_img_queue = []
         self._set_global_memory([None, None])
         self.head.proposal_feats_local = [None, None]
+        self.head.proposal_feats_local_groups = 1
         self.queue = deque(maxlen=n)      # entries: (split_outputs, frame index inside the split)
         self.video_index += 1
 
@@ -312,6 +321,24 @@ class DiffusionDet(nn.Module):
         self.head.proposal_feats_global = list(memory)
         if self._engine is not None:
             self._engine.invalidate_memory()
+
+    def _local_memory(self, entries=None):
+        """[cat of the queue's top-75 features, cat of its top-25 features] = head.proposal_feats_local of diffusion_det.py:507-512: the
+        reference keeps two more deques (proposals_feat, proposals_feat_dis) filled by the same fill_idx as the feature queue; here the
+        queue's entries already name (split, frame), and a split carries k1 / k2.  Consecutive frames of one split (the shipped protocol:
+        the rows the batch's own extraction pass just wrote) are a view; anything else (a new video's repeated frames, a queue spanning
+        two calls) is a concatenation."""
+        entries = list(self.queue) if entries is None else entries
+        src, idx = entries[0][0], [e[1] for e in entries]
+        d = self.hidden_dim
+        if all(e[0] is src for e in entries) and idx == list(range(idx[0], idx[0] + len(idx))):
+            a, b = idx[0], idx[0] + len(idx)
+            return [src[k][a:b].reshape(-1, d) for k in ("k1", "k2")]
+        return [torch.cat([sp[k][i] for sp, i in entries]) for k in ("k1", "k2")]
+
+    def _set_local_memory(self, memory, groups=1):
+        self.head.proposal_feats_local = list(memory)
+        self.head.proposal_feats_local_groups = groups
 
     # ---- one video over several ranks (engine/inference.py: compute_on_video_sharded) -------------------------
     def global_memory(self):
@@ -410,6 +437,8 @@ class DiffusionDet(nn.Module):
             fill_idx = list(range(n_local))
         for i in fill_idx:
             self.queue.append((splits[0], i))
+        if self.local_box_enable:
+            self._set_local_memory(self._local_memory())          # diffusion_det.py:511-512
 
         # 4. final stage.  Per frame it needs the frame's own extraction results and the video's global memory, nothing
         # of its neighbours, so the batches extracted ahead in this call are finished here as well -- in one pass per
@@ -434,6 +463,12 @@ class DiffusionDet(nn.Module):
                 else:
                     sp = run["split"]
                     feats_run, cached = sp["feats"], (sp["logits"], sp["boxes"], sp["obj"])
+                if self.local_box_enable:
+                    # every batch of the run brings its own local memory: under the look-ahead precondition (a batch = one full queue) it
+                    # is the top-k rows of the batch's own INFER_BATCH extraction slots, so the run's rows are the groups, back to back
+                    sp_run = src if run["src"] is not None else run["split"]
+                    a, b = (i0, i1) if run["src"] is not None else (0, sp_run["k1"].shape[0])
+                    self._set_local_memory([sp_run[k][a:b].reshape(-1, self.hidden_dim) for k in ("k1", "k2")], groups=len(run["items"]))
                 per_slot = self._final_stage(feats_run, cached, whwh, w, h, pairs, run["items"], ddim_draws)
                 for k, (fb, nb) in enumerate(run["items"]):
                     out = per_slot[k * self.infer_batch: k * self.infer_batch + nb]
@@ -441,6 +476,8 @@ class DiffusionDet(nn.Module):
                         mine = out
                     else:
                         self._results_ahead[fb] = out
+            if self.local_box_enable:
+                self._set_local_memory(self._local_memory())          # what the reference holds after this call: the current batch's
             return mine
 
         # current batch only (diffusion_det.py:515-523)
@@ -501,7 +538,10 @@ class DiffusionDet(nn.Module):
     def _call_graph_applies(self, infos, ref_l, ref_g, ahead, batch, frame_id):
         """A call that runs one full batch through the whole per-call pipeline and nothing else: the shipped protocol
         (KEY_FRAME_LOCATION 0, ALL_FRAME_INTERVAL == INFER_BATCH, memory final after the video's first call), not the video's
-        first call, no global frames, no look-ahead hand-over, every frame a resident fp32 tensor of one size, memory present."""
+        first call, no global frames, no look-ahead hand-over, every frame a resident fp32 tensor of one size, memory present.
+        It needs the global stage, so a model whose conditioning is the LOCAL box-level attention (GLOBAL.ENABLE False) is never replayed
+        from a graph: its calls are launched kernel by kernel whatever `use_call_graph` says.  Local + global replays: the local
+        product is unobservable there and not launched (DynamicHead)."""
         if not self.use_call_graph or self.lookahead != 1 or self.debug_taps is not None or self.demo:
             return False
         mega = self.cfg.MODEL.VID.MEGA
@@ -559,7 +599,8 @@ class DiffusionDet(nn.Module):
         # ... and it bakes in every switch the eager path reads per call
         gframes = [im.tensors for im in ref_g] if ref_g else []
         key = (tuple(frames[0].shape), len(frames), self.sampling_timesteps, int(mem[0].shape[0]), int(mem[1].shape[0]) if mem[1] is not None else 0,
-               id(eng), (float(w), float(h)), bool(self.skip_unobservable), bool(self.use_nms), eng.chains, eng.precision, len(gframes))
+               id(eng), (float(w), float(h)), bool(self.skip_unobservable), bool(self.use_nms), eng.chains, eng.precision, len(gframes),
+               bool(self.local_box_enable), int(self.head.local_stage))
         M = self.num_proposals
         g = self._graphs.get(key)
         if g is None:
@@ -603,6 +644,8 @@ class DiffusionDet(nn.Module):
         # graph's static buffers -- an eager call that follows never reads an older call's entries
         for i in range(batch):
             self.queue.append((g["local"], i))
+        if self.local_box_enable:
+            self._set_local_memory(self._local_memory())
         out = g["out"]
         if not self.results_on_host:
             # the BoxLists would be views of the graph's static output buffer, which the next replay overwrites: hand out copies

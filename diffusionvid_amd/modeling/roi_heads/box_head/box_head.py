@@ -9,8 +9,19 @@ Same constructor signature, attributes the detector mutates (`proposal_feats_glo
                      top-75 features [B*75,d], top-25 features [B*25,d])      (:286-317)
   box_extract == 0: (class_logits[None], pred_bboxes[None]) of the conditioned head (:319-432)
 
-Every RCNNHead / RCNNHead_cond pass, the global cross-attention and the top-k feature selection
-run as HIP kernels (ops.Model); this class only sequences them.  Training is out of scope.
+Every RCNNHead / RCNNHead_cond pass, the global and the local cross-attention and the top-k feature
+selection run as HIP kernels (ops.Model); this class only sequences them.  Training is out of scope.
+
+Local box-level attention (MODEL.VID.ROI_BOX_HEAD.ATTENTION.ENABLE, box_head.py:186-194, :360-363):
+`attn_ = LayerNorm_i(MHA_i(query, key = value = proposal_feats_local[i]))` for i < STAGE, with the query
+never updated and no residual -- only the LAST stage's result survives, so only it is launched
+(STAGE 1: the top-75 memory, STAGE 2: the top-25 memory with `local_attention.1`'s parameters; STAGE > 2
+indexes past the two memories in the reference and is refused here).  With GLOBAL.ENABLE also true the
+global stage overwrites `attn_` (:366-371, adaptive_norm is hard-wired True): the local product is
+unobservable and the local launch is skipped -- local + global computes what global alone computes.
+`proposal_feats_local_groups` (this repo's addition, default 1): the two local memories hold that many
+equal blocks, block g serving the g-th block of the call's frames (the detector's look-ahead schedule
+finishes several batches in one call, each with its own local memory).
 """
 import torch
 from torch import nn
@@ -31,9 +42,12 @@ class DynamicHead(nn.Module):
         self.local_enable = cfg.MODEL.VID.ROI_BOX_HEAD.ATTENTION.ENABLE
         self.global_enable = cfg.MODEL.VID.MEGA.GLOBAL.ENABLE
         self.global_stage = cfg.MODEL.VID.MEGA.GLOBAL.RES_STAGE
+        self.local_stage = 0
         if self.local_enable:
-            raise NotImplementedError("local box-level attention (MODEL.VID.ROI_BOX_HEAD.ATTENTION.ENABLE) is not on the "
-                                      "DiffusionVID inference path of the shipped configs and is not built")
+            self.local_stage = int(cfg.MODEL.VID.ROI_BOX_HEAD.ATTENTION.STAGE)
+            if not 1 <= self.local_stage <= 2:
+                raise NotImplementedError("MODEL.VID.ROI_BOX_HEAD.ATTENTION.STAGE must be 1 or 2, got %d: stage i attends proposal_feats_local[i] "
+                                          "and there are two local memories (top-75, top-25); the reference fails on a third" % self.local_stage)
         if self.global_enable and self.global_stage != 1:
             raise NotImplementedError("GLOBAL.RES_STAGE != 1 is not supported")
         self.infer_batch = cfg.INPUT.INFER_BATCH
@@ -42,6 +56,7 @@ class DynamicHead(nn.Module):
         self.use_topk = False
         self.proposal_feats_global = [None, None]
         self.proposal_feats_local = [None, None]
+        self.proposal_feats_local_groups = 1
         self.proposals_feat_cur = []
         self._engine_provider = engine_provider
 
@@ -95,13 +110,23 @@ class DynamicHead(nn.Module):
             k1, k2 = ops.select_topk_features(class_logits, proposal_features, self.top_k[0], self.top_k[1])
             return [class_logits, bboxes, proposal_features.unsqueeze(0)], k1, k2
 
-        if not self.global_enable:
+        if not self.global_enable and not self.local_enable:
             return class_logits[None], bboxes[None]
 
-        memory = self.proposal_feats_global[0]
-        if memory is None:
-            raise RuntimeError("proposal_feats_global is empty: the detector fills it from the global frames of a video")
-        attn_ = eng.global_xattn(proposal_features, memory)                               # box_head.py:366-394
+        if self.global_enable:
+            # (with local attention also on, its product would be overwritten here: it is not launched, see the module docstring)
+            memory = self.proposal_feats_global[0]
+            if memory is None:
+                raise RuntimeError("proposal_feats_global is empty: the detector fills it from the global frames of a video")
+            attn_ = eng.global_xattn(proposal_features, memory)                           # box_head.py:366-394
+        else:
+            stage = self.local_stage - 1                                                  # the only stage whose result survives
+            memory = self.proposal_feats_local[stage]
+            if memory is None:
+                raise RuntimeError("proposal_feats_local is empty: the detector fills it from the local frame queue")
+            if eng.local_stages != self.local_stage:
+                raise ops._lib.DvidError("ATTENTION.STAGE %d but the weights hold %d local attention stage(s)" % (self.local_stage, eng.local_stages))
+            attn_ = eng.local_xattn(proposal_features, memory, groups=self.proposal_feats_local_groups, stage=stage)   # box_head.py:360-363
         class_logits2, bboxes2 = class_logits, bboxes
         for i in range(self.num_heads_local):
             class_logits2, bboxes2, proposal_features = eng.rcnn_head(i, feats, height, width, bboxes2, proposal_features, t_host,

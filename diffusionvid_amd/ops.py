@@ -412,6 +412,11 @@ class Model:
         self._ws = None
         self.chains = -1                 # the library's default until set_chains
         self._kv_src = None
+        # local box-level attention: present when the state dict carries it (the library infers the same from the tensors it was given)
+        self.local_stages = 0
+        while f"head.local_attention.{self.local_stages}.0.in_proj_weight" in state_dict:
+            self.local_stages += 1
+        self._lkv = {}                   # stage -> (memory tensor, its version, groups) whose K / V projections the library holds
 
     def take_range_flag(self):
         """DTYPE float32 with split operands: True if a launch since the last call met an activation beyond the fp16 range (65504); synchronises
@@ -527,6 +532,39 @@ class Model:
         self.ensure_memory_projected(memory)
         out = torch.empty_like(query)
         call("dvid_global_xattn", self.handle, ptr(query), query.shape[0], None, memory.shape[0], ptr(out), stream_ptr())
+        return out
+
+    def invalidate_local_memory(self):
+        """The local memory changed behind the cache's back (a write through a raw pointer, e.g. a replayed launch sequence): the next
+        local_xattn projects K/V again."""
+        self._lkv = {}
+
+    def ensure_local_memory_projected(self, memory, groups=1, stage=None):
+        """K / V projections of `groups` local memories (memory [groups * lk, d], group g = rows [g lk, (g + 1) lk)) into the engine's
+        buffer unless they are current: same tensor object, same version, same grouping -- the cache idea of ensure_memory_projected,
+        keyed per stage.  The library keeps ONE projected local memory, so projecting a stage drops the others."""
+        stage = self.local_stages - 1 if stage is None else int(stage)
+        if memory.shape[0] % groups:
+            raise _lib.DvidError(f"local memory of {memory.shape[0]} rows does not split into {groups} groups")
+        hit = self._lkv.get(stage)
+        if hit is None or hit[0] is not memory or hit[1] != memory._version or hit[2] != groups:
+            mem = _cuda(memory, torch.float32)
+            self._lkv = {}
+            call("dvid_local_memory_project", self.handle, stage, ptr(mem), mem.shape[0] // groups, int(groups), stream_ptr())
+            self._lkv[stage] = (memory, memory._version, groups)          # holds the tensor: its storage cannot be recycled under the cache
+
+    def local_xattn(self, query, memory, groups=1, stage=None):
+        """cond = LayerNorm(MHA(query, memory, memory)) of the local box-level stage `stage` (default and only legal value: the last one,
+        the only observable one -- box_head.py:360-363).  query [rows, d] and memory [groups * lk, d] are `groups` consecutive blocks:
+        block g of the queries attends block g of the memory (every look-ahead batch has its own local memory).  K/V are projected
+        once per (memory object, version, groups), see ensure_local_memory_projected / invalidate_local_memory."""
+        stage = self.local_stages - 1 if stage is None else int(stage)
+        query = _cuda(query, torch.float32)
+        if query.shape[0] % groups:
+            raise _lib.DvidError(f"{query.shape[0]} query rows do not split into {groups} groups")
+        self.ensure_local_memory_projected(memory, groups, stage)
+        out = torch.empty_like(query)
+        call("dvid_local_xattn", self.handle, stage, ptr(query), query.shape[0], int(groups), memory.shape[0] // groups, ptr(out), stream_ptr())
         return out
 
     def close(self):

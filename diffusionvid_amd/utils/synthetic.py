@@ -28,7 +28,10 @@ def _ln(g, sd, name, d):
 
 
 def make_head_state_dict(seed=0, hidden=256, nheads=8, dim_ff=2048, dim_dynamic=64, num_classes=30, num_cls=1, num_reg=3,
-                         num_heads=3, num_heads_cond=1, pooler=7, prior_prob=0.01, prefix="head."):
+                         num_heads=3, num_heads_cond=1, pooler=7, prior_prob=0.01, prefix="head.", local_stages=0):
+    """local_stages > 0 adds `local_attention.{i}.0.*` (MultiheadAttention) and `local_attention.{i}.2.*` (LayerNorm) for i < local_stages
+    (box_head.py:186-194; entry 1 of each stage is a Dropout, which has no parameters).  They are drawn AFTER every other tensor, so the
+    rest of the dict is bit-identical whatever local_stages is."""
     g = torch.Generator().manual_seed(seed)
     sd = {}
     d = hidden
@@ -75,6 +78,9 @@ def make_head_state_dict(seed=0, hidden=256, nheads=8, dim_ff=2048, dim_dynamic=
     mha(prefix + "global_attention.0.0")
     linear(prefix + "time_mlp.1", 4 * d, d)
     linear(prefix + "time_mlp.3", 4 * d, 4 * d)
+    for i in range(local_stages):
+        mha(f"{prefix}local_attention.{i}.0")
+        _ln(g, sd, f"{prefix}local_attention.{i}.2", d)
     return sd
 
 

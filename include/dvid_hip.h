@@ -15,6 +15,7 @@
  *                              mega_core/modeling/roi_heads/box_head/box_head.py:495-548, :605-664, :687-711, :550-590
  *   dvid_roialign_v2_multilevel detectron2 ROIPooler(ROIAlignV2) built at box_head.py:250-271, called :507,:617
  *   dvid_global_xattn          nn.MultiheadAttention global stage, box_head.py:366-380
+ *   dvid_local_xattn           nn.MultiheadAttention + LayerNorm of the local box-level stage, box_head.py:186-194, :360-363
  *   dvid_select_topk_features  box_head.py:304-317
  *   dvid_noise_to_boxes        diffusion_det.py:657-660
  *   dvid_counter_normal        torch.randn(shape, device=self.device) at diffusion_det.py:449, :542, :587, :595
@@ -95,7 +96,7 @@ int dvid_model_finalize(dvid_model* m);
  * (multiples of 32) and boxes_per_frame boxes. */
 int dvid_workspace_reserve(dvid_model* m, int max_frames, int height, int width, int boxes_per_frame);
 /* Counts the MOVES of this model's workspace buffers (dvid_workspace_reserve growing the arena, dvid_global_memory_project /
- * dvid_global_xattn growing the memory's projection buffers; a buffer's first allocation does not count: nothing can hold its address yet).
+ * dvid_global_xattn / dvid_local_memory_project / dvid_local_xattn growing the memories' projection buffers; a buffer's first allocation does not count: nothing can hold its address yet).
  * A caller that captured launches into a hipGraph holds addresses inside the workspace; when the counter differs from its value at
  * capture time the graph must be dropped.  Per model: another model's growth leaves this one's graphs alone.
  * (The reference has no counterpart: its workspace is torch's caching allocator, mega_core/modeling/detector/diffusion_det.py:418-476.) */
@@ -143,6 +144,23 @@ int dvid_global_xattn(dvid_model* m, const float* query, int rows, const float* 
 /* Project the video's global memory [lk, hidden] to K/V once (box_head.py:366-380 re-projects the same rows on every
  * call); valid until the next call of this function. */
 int dvid_global_memory_project(dvid_model* m, const float* memory, int lk, void* stream);
+
+/* Local box-level attention (MODEL.VID.ROI_BOX_HEAD.ATTENTION.ENABLE; box_head.py:186-194, :338, :360-363).  The model has it when the
+ * tensors head.local_attention.{i}.0.in_proj_weight / .0.in_proj_bias / .0.out_proj.weight / .0.out_proj.bias / .2.weight / .2.bias were
+ * set before dvid_model_finalize, i = 0 .. stages - 1 (stages = the number of consecutive groups present; more than 2 fails the
+ * finalize with DVID_ERR_UNSUPPORTED: the reference holds two local memories and indexes past them).  The reference's loop overwrites
+ * attn_ on every stage and never updates the query, so ONLY THE LAST STAGE is observable and only it is computed: earlier stages' tensors
+ * are accepted and ignored, and `stage` must be stages - 1 (DVID_ERR_ARG otherwise).  A model without the tensors answers DVID_ERR_STATE.
+ *
+ * dvid_local_memory_project: K/V projection of `groups` local memories of `lk` rows each, memory fp32 [groups * lk, hidden] (group g = rows
+ * [g lk, (g + 1) lk): proposal_feats_local[stage] of that group's batch), into a buffer the MODEL owns; it moves only when it grows, and such a
+ * move is counted by dvid_workspace_generation.  Valid until the next call of this function.
+ * dvid_local_xattn: out[rows, hidden] = LayerNorm(out_proj(MHA(q_proj(query), K, V))), query fp32 [rows, hidden], rows / groups consecutive
+ * query rows per group, each group attending its own lk projected memory rows; groups and lk must be what the last
+ * dvid_local_memory_project projected (DVID_ERR_STATE otherwise).  The out-projection, its bias and the LayerNorm run as one kernel
+ * (csrc/localattn.hip).  DTYPE float32 follows option f32_split and reports the fp16 range like the other fp32 linears. */
+int dvid_local_memory_project(dvid_model* m, int stage, const float* memory, int lk, int groups, void* stream);
+int dvid_local_xattn(dvid_model* m, int stage, const float* query, int rows, int groups, int lk, float* out, void* stream);
 
 /* ---- stand-alone ops (also used by the parity tests) -------------------------------------- */
 int dvid_roialign_v2_multilevel(const void* p3, const void* p4, const void* p5, int n_frames, int height, int width,
