@@ -55,6 +55,7 @@ SIGNATURES = {
                                                 c_void_p, c_void_p, c_void_p]),
     "dvid_conv2d_nhwc_f32": (c_int, [c_void_p] * 8 + [c_int] * 12 + [c_void_p]),
     "dvid_mha_f32": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_int64] * 3 + [c_void_p]),
+    "dvid_swin_window_attn_f32": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
     "dvid_dynconv_f32": (c_int, [c_void_p] * 7 + [c_int, c_void_p]),
     "dvid_select_topk_features": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                           c_void_p]),
@@ -72,6 +73,9 @@ SIGNATURES = {
     "dvid_mha_f16": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_int64] * 3 + [c_void_p]),
     "dvid_dynconv": (c_int, [c_void_p] * 7 + [c_int, c_void_p]),
     "dvid_add_layernorm": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_void_p]),
+    "dvid_swin_pack_relbias": (c_int, [c_void_p, c_int, c_void_p]),
+    "dvid_swin_window_attn_f16": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
+    "dvid_patch_merge_ln": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "dvid_nhwc_from_nchw": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "dvid_nchw_from_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "dvid_f32_to_f16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

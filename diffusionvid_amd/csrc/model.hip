@@ -1190,6 +1190,20 @@ const std::vector<float>& time_embedding(dvid_model* m, int64_t t) {
     return m->time_cache.emplace(t, std::move(out)).first->second;
 }
 
+// Relative-position bias of a 7x7 window as the Swin attention kernels read it: table [169][nheads] (relative_position_bias_table)
+// -> out [nheads][49][SWIN_RELBIAS_PITCH], out[h][i][j] = table[index(i, j)][h] with the relative position index of
+// swintransformer.py:122-131, keys 49.. zero.  One 256-byte row per (head, query): a lane fetches the bias of its 16 keys as four
+// aligned 16-byte loads.
+void pack_swin_relbias(const float* table, int nheads, float* out) {
+    std::fill(out, out + (size_t)nheads * 49 * SWIN_RELBIAS_PITCH, 0.f);
+    for (int h = 0; h < nheads; ++h)
+        for (int i = 0; i < 49; ++i)
+            for (int j = 0; j < 49; ++j) {
+                const int relidx = ((i / 7 - j / 7) + 6) * 13 + ((i % 7 - j % 7) + 6);
+                out[((size_t)h * 49 + i) * SWIN_RELBIAS_PITCH + j] = table[(size_t)relidx * nheads + h];
+            }
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1273,10 +1287,6 @@ int dvid_model_finalize(dvid_model* m) {
             TRY(make_conv(m, *pw, {}, pb->v, 4, 0, 8, nullptr, &m->swin_patch));
             TRY(make_ln(m, bu + "patch_embed.norm", &m->swin_patch_norm));
         }
-        // relative position index of a 7x7 window (swintransformer.py:122-131)
-        int relidx[49][49];
-        for (int i = 0; i < 49; ++i)
-            for (int j = 0; j < 49; ++j) relidx[i][j] = ((i / 7 - j / 7) + 6) * 13 + ((i % 7 - j % 7) + 6);
         for (int st = 0; st < 4; ++st) {
             SwinStageW& S = m->swin[st];
             S.dim = c.swin_embed_dim << st;
@@ -1298,12 +1308,8 @@ int dvid_model_finalize(dvid_model* m) {
                 TRY(m->upload(qb16.data(), qb16.size() * sizeof(half_t), reinterpret_cast<void**>(&B.qkv_bias16)));
                 NEED(tb, p + ".attn.relative_position_bias_table");
                 if (tb->shape[0] != 169 || tb->shape[1] != S.heads) FAIL(DVID_ERR_ARG, "%s: bad bias table shape", p.c_str());
-                // one 256-byte row per (head, query): a lane fetches the bias of its 16 keys as four aligned 16-byte loads
-                std::vector<float> rb((size_t)S.heads * 49 * SWIN_RELBIAS_PITCH, 0.f);
-                for (int h = 0; h < S.heads; ++h)
-                    for (int i = 0; i < 49; ++i)
-                        for (int j = 0; j < 49; ++j)
-                            rb[((size_t)h * 49 + i) * SWIN_RELBIAS_PITCH + j] = tb->v[(size_t)relidx[i][j] * S.heads + h];
+                std::vector<float> rb((size_t)S.heads * 49 * SWIN_RELBIAS_PITCH);
+                pack_swin_relbias(tb->v.data(), S.heads, rb.data());
                 TRY(upload_f32(m, rb, &B.relbias));
             }
             S.has_down = st < 3;
@@ -2076,6 +2082,17 @@ int dvid_mha_f32(const float* q, const float* k, const float* v, float* out, int
     return DVID_OK;
 }
 
+int dvid_swin_window_attn_f32(const float* qkv, const float* qkv_bias, const float* relbias, float* out, int batch, int H, int W, int C,
+                              int nheads, int shift, void* stream) {
+    g_err[0] = 0;
+    if (!qkv || !qkv_bias || !relbias || !out) FAIL(DVID_ERR_ARG, "swin window attention: null pointer");
+    if (batch <= 0 || H <= 0 || W <= 0 || nheads <= 0 || shift < 0 || shift >= 7)
+        FAIL(DVID_ERR_ARG, "swin window attention: bad sizes (batch %d, %d x %d tokens, %d heads, shift %d)", batch, H, W, nheads, shift);
+    const int rc = dvid_f32_swin_window_attn_launch(qkv, qkv_bias, relbias, out, batch, H, W, C, nheads, shift, reinterpret_cast<hipStream_t>(stream));
+    if (rc != DVID_OK) FAIL(rc, "swin window attention (fp32): C %d with %d heads on %d x %d x %d tokens is not supported", C, nheads, batch, H, W);
+    return DVID_OK;
+}
+
 int dvid_dynconv_f32(const float* roi, const float* params, const float* g1, const float* b1, const float* g2, const float* b2, float* out,
                      int rows, void* stream) {
     g_err[0] = 0;
@@ -2211,6 +2228,34 @@ int dvid_add_layernorm(const float* x, const float* r, const float* g, const flo
                        void* stream) {
     g_err[0] = 0;
     TRY(dvid_add_layernorm_launch(x, r, g, b, y, nullptr, rows, d, relu, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_swin_pack_relbias(const float* table, int nheads, float* out) {
+    g_err[0] = 0;
+    if (!table || !out || nheads <= 0) FAIL(DVID_ERR_ARG, "swin relative-position bias: null pointer or %d heads", nheads);
+    pack_swin_relbias(table, nheads, out);
+    return DVID_OK;
+}
+
+int dvid_swin_window_attn_f16(const void* qkv, const void* qkv_bias16, const float* relbias, void* out, int batch, int H, int W, int C,
+                              int nheads, int shift, void* stream) {
+    g_err[0] = 0;
+    if (!qkv || !qkv_bias16 || !relbias || !out) FAIL(DVID_ERR_ARG, "swin window attention: null pointer");
+    if (batch <= 0 || H <= 0 || W <= 0 || nheads <= 0 || shift < 0 || shift >= 7)
+        FAIL(DVID_ERR_ARG, "swin window attention: bad sizes (batch %d, %d x %d tokens, %d heads, shift %d)", batch, H, W, nheads, shift);
+    const int rc = dvid_swin_window_attn_launch(reinterpret_cast<const half_t*>(qkv), reinterpret_cast<const half_t*>(qkv_bias16), relbias,
+                                                reinterpret_cast<half_t*>(out), batch, H, W, C, nheads, shift, reinterpret_cast<hipStream_t>(stream));
+    if (rc != DVID_OK) FAIL(rc, "swin window attention: C %d with %d heads on %d x %d x %d tokens is not supported", C, nheads, batch, H, W);
+    return DVID_OK;
+}
+
+int dvid_patch_merge_ln(const float* x, const float* g, const float* b, void* y16, float* y32, int B, int H, int W, int C, void* stream) {
+    g_err[0] = 0;
+    if (!x || !g || !b || (!y16 && !y32)) FAIL(DVID_ERR_ARG, "patch merge: null pointer (at least one of y16 / y32 is needed)");
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0) FAIL(DVID_ERR_ARG, "patch merge: bad sizes (%d x %d x %d tokens, C %d)", B, H, W, C);
+    const int rc = dvid_patch_merge_ln_launch(x, g, b, reinterpret_cast<half_t*>(y16), B, H, W, C, reinterpret_cast<hipStream_t>(stream), y32);
+    if (rc != DVID_OK) FAIL(rc, "patch merge: C %d is not supported (a multiple of 4, at most 512)", C);
     return DVID_OK;
 }
 

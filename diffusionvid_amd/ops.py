@@ -225,6 +225,58 @@ def add_layernorm(x, r, g, b, relu=False):
     return y
 
 
+def swin_pack_relbias(table):
+    """relative_position_bias_table fp32 [169, heads] (host) -> the table the Swin attention kernels read, fp32 [heads, 49, 64] (host;
+    keys 49..63 zero), packed by the library's own loader code."""
+    table = table.detach().cpu().contiguous()
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[0] != 169:
+        raise TypeError(f"expected a float32 [169, heads] table, got {table.dtype} {tuple(table.shape)}")
+    out = torch.empty((table.shape[1], 49, 64), dtype=torch.float32)
+    call("dvid_swin_pack_relbias", ptr(table), table.shape[1], ptr(out))
+    return out
+
+
+def _swin_window_attn(name, dtype, qkv, qkv_bias, relbias, B, H, W, nheads, shift, out):
+    qkv, qkv_bias, relbias = _cuda(qkv, dtype), _cuda(qkv_bias, dtype), _cuda(relbias, torch.float32)
+    C = qkv.shape[1] // 3
+    assert tuple(qkv.shape) == (B * H * W, 3 * C) and qkv_bias.numel() == 3 * C and tuple(relbias.shape) == (nheads, 49, 64)
+    if out is None:
+        out = torch.empty((B * H * W, C), dtype=dtype, device=qkv.device)
+    out = _cuda(out, dtype)
+    assert out.shape[0] >= B * H * W and out.shape[1] == C
+    call(name, ptr(qkv), ptr(qkv_bias), ptr(relbias), ptr(out), B, H, W, C, nheads, shift, stream_ptr())
+    return out
+
+
+def swin_window_attn_f16(qkv16, qkv_bias16, relbias, B, H, W, nheads, shift, out=None):
+    """Swin (shifted-)window attention on a [B, H, W] token map: qkv fp16 [B*H*W, 3C] (C = 32 * heads), qkv_bias16 fp16 [3C] (what a
+    padded window position holds), relbias fp32 [heads, 49, 64] (swin_pack_relbias) -> fp16 [B*H*W, C], written into `out`'s first
+    B*H*W rows when one is given."""
+    return _swin_window_attn("dvid_swin_window_attn_f16", torch.float16, qkv16, qkv_bias16, relbias, B, H, W, nheads, shift, out)
+
+
+def swin_window_attn_f32(qkv, qkv_bias, relbias, B, H, W, nheads, shift, out=None):
+    """the fp32 form of swin_window_attn_f16 (csrc/f32.hip)"""
+    return _swin_window_attn("dvid_swin_window_attn_f32", torch.float32, qkv, qkv_bias, relbias, B, H, W, nheads, shift, out)
+
+
+def patch_merge_ln(x, g, b, f16=True, f32=True, out16=None, out32=None):
+    """Swin PatchMerging up to its LayerNorm: x fp32 [B, H, W, C], g / b fp32 [4C] -> ([B * ceil(H/2) * ceil(W/2), 4C] fp16 or None,
+    the same in fp32 or None); `out16` / `out32` (at least that many rows) are written in place of fresh buffers."""
+    x, g, b = _cuda(x, torch.float32), _cuda(g, torch.float32), _cuda(b, torch.float32)
+    B, H, W, C = x.shape
+    rows = B * ((H + 1) // 2) * ((W + 1) // 2)
+    assert g.numel() == 4 * C and b.numel() == 4 * C
+    if f16 and out16 is None:
+        out16 = torch.empty((rows, 4 * C), dtype=torch.float16, device=x.device)
+    if f32 and out32 is None:
+        out32 = torch.empty((rows, 4 * C), dtype=torch.float32, device=x.device)
+    for o, dt in ((out16, torch.float16), (out32, torch.float32)):
+        assert o is None or (_cuda(o, dt) is o and o.shape[0] >= rows and o.shape[1] == 4 * C)
+    call("dvid_patch_merge_ln", ptr(x), ptr(g), ptr(b), ptr(out16), ptr(out32), B, H, W, C, stream_ptr())
+    return out16, out32
+
+
 def resize_u8_to_f32(src_hwc, oh, ow, ph, pw, xtab, ytab):
     """uint8 [H, W, 3] (device) -> fp32 [1, 3, ph, pw] in [0, 1]: Pillow-identical bilinear resize to (oh, ow), zero padding to
     (ph, pw).  xtab / ytab: (bounds, weights) int32 device tensors of data/transforms.resample_tables, None for an axis

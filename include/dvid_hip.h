@@ -180,6 +180,9 @@ int dvid_conv2d_nhwc_f32(const float* in, const float* w, const void* w_hi, cons
                          void* stream);
 int dvid_mha_f32(const float* q, const float* k, const float* v, float* out, int batch, int lq, int lk, int nheads, int q_ld, int kv_ld, int out_ld,
                  int64_t q_bs, int64_t kv_bs, int64_t out_bs, void* stream);
+/* Swin (shifted-)window attention, fp32 form of dvid_swin_window_attn_f16 below: qkv fp32 [batch*H*W][3C], qkv_bias fp32 [3C], out fp32. */
+int dvid_swin_window_attn_f32(const float* qkv, const float* qkv_bias, const float* relbias, float* out, int batch, int H, int W, int C,
+                              int nheads, int shift, void* stream);
 int dvid_dynconv_f32(const float* roi, const float* params, const float* g1, const float* b1, const float* g2, const float* b2, float* out,
                      int rows, void* stream);
 int dvid_select_topk_features(const float* logits, int n_frames, int m, int num_classes, int k1, int k2, const float* feats,
@@ -235,6 +238,20 @@ int dvid_dynconv(const void* roi, const void* params, const float* g1, const flo
                  void* out, int rows, void* stream);
 int dvid_add_layernorm(const float* x, const float* r, const float* g, const float* b, float* y, int rows, int d, int relu,
                        void* stream);
+/* The Swin backbone's own kernels (swintransformer.py:135-176 and :216-270 without the two Linears; :296-319 without the reduction).
+ * dvid_swin_pack_relbias (host only): relative_position_bias_table [169][nheads] -> the table the attention kernels read,
+ * out [nheads][49][64] floats, out[h][i][j] = table[relative_position_index(i, j)][h], columns 49..63 zero.
+ * dvid_swin_window_attn_f16: qkv fp16 [batch*H*W][3C] (q | k | v, head h at columns [32h, 32h+32) of each third; C = 32 * nheads), the
+ * token map H x W of each image is padded to multiples of 7 with tokens whose q/k/v equal qkv_bias16 [3C], rolled by -shift on both axes
+ * (0 <= shift < 7; shift > 0 adds the -100 mask between shift regions), attended per 7x7 window with the packed bias, and mapped back:
+ * out fp16 [batch*H*W][C], padded positions write nothing.
+ * dvid_patch_merge_ln: x fp32 [B][H][W][C] -> LayerNorm (eps 1e-5, g / b [4C]) of [x(2i,2j) | x(2i+1,2j) | x(2i,2j+1) | x(2i+1,2j+1)]
+ * (zeros beyond an odd H / W), [B][ceil(H/2)][ceil(W/2)][4C] as fp16 (y16) and / or fp32 (y32); either may be NULL, not both.
+ * C % 4 == 0 and C <= 512, DVID_ERR_UNSUPPORTED otherwise. */
+int dvid_swin_pack_relbias(const float* table, int nheads, float* out);
+int dvid_swin_window_attn_f16(const void* qkv, const void* qkv_bias16, const float* relbias, void* out, int batch, int H, int W, int C,
+                              int nheads, int shift, void* stream);
+int dvid_patch_merge_ln(const float* x, const float* g, const float* b, void* y16, float* y32, int B, int H, int W, int C, void* stream);
 int dvid_nhwc_from_nchw(const float* in, void* out_f16, int n, int h, int w, int c, void* stream);
 int dvid_nchw_from_nhwc(const void* in_f16, float* out, int n, int h, int w, int c, void* stream);
 int dvid_f32_to_f16(const float* x, void* y, int64_t n, void* stream);

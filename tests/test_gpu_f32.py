@@ -304,24 +304,28 @@ def test_f32_backbone_small(dv):
     model.close()
 
 
-def test_f32_backbone_swin_small(dv):
-    """Swin-Transformer + FPN with DTYPE float32 (reduced widths / depths; odd token maps, padded windows, shifted-window masks, GELU MLP,
-    PatchMerging) against the fp32 oracle (oracle/swin.py, itself bit-exact against the reference's module: golden g8).  The fp16 path's
-    bound on the same test is 3e-2."""
+@pytest.mark.parametrize("size", [(160, 224), (160, 192)], ids=["160x224", "160x192"])
+def test_f32_backbone_swin_small(dv, size):
+    """Swin-Transformer + FPN with DTYPE float32 (reduced widths / depths; padded windows, shifted-window masks, GELU MLP, PatchMerging)
+    against the fp32 oracle (oracle/swin.py, itself bit-exact against the reference's module: golden g8).  The fp16 path's bound on the
+    same test is 3e-2.  160 x 224: token maps 40x56 -> 20x28 -> 10x14 -> 5x7, windows pad along H only (42, 21, 14, 7 rows).  160 x 192:
+    40x48 -> 20x24 -> 10x12 -> 5x6, windows pad along H and, at every stage, along W (49, 28, 14, 7 columns); the last map is smaller
+    than a window on both axes.  Every merged map is even: merging an odd map and the window kernel at 2e-5 are tests/test_gpu_swin.py's."""
     from diffusionvid_amd.utils import synthetic
     from oracle import swin as oswin
     sw = dict(embed_dim=64, depths=(2, 2, 2, 1), heads=(2, 4, 8, 16), window=7)
     sd = synthetic.make_state_dict(0, swin=sw)
     g = torch.Generator().manual_seed(15)
-    imgs = torch.rand(2, 3, 160, 224, generator=g)        # tokens 40x56 -> 20x28 -> 10x14 -> 5x7 (pads to 42x56, 21x28, 14x14, 7x7)
+    imgs = torch.rand(2, 3, size[0], size[1], generator=g)
     mean, std = (123.675, 116.280, 103.530), (58.395, 57.120, 57.375)
     ref = oswin.backbone_swin_fpn(backbone_r101.normalizer(imgs, mean, std), sd, "backbone.", embed_dim=64, depths=sw["depths"], num_heads=sw["heads"])
     model = dv.Model(sd, res_blocks=(0, 0, 0, 0), backbone="swin", swin_embed_dim=64, swin_depths=sw["depths"], swin_heads=sw["heads"], precision="float32")
-    model.reserve(2, 160, 224, 300)
+    model.reserve(2, size[0], size[1], 300)
     p3, p4, p5 = model.backbone(imgs.cuda())
     assert p3.dtype == torch.float32
+    tag = "f32_backbone_swin_small" if size == (160, 224) else "f32_backbone_swin_small[%dx%d]" % size
     for name, got in (("p3", p3), ("p4", p4), ("p5", p5)):
-        check(f"f32_backbone_swin_small.{name}", dv.nchw_from_nhwc(got), ref[name], 2e-4, 2e-4)
+        check(f"{tag}.{name}", dv.nchw_from_nhwc(got), ref[name], 2e-4, 2e-4)
     model.close()
 
 

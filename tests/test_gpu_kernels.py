@@ -744,25 +744,31 @@ def test_stem_pool_fusion_bit_identical(dv, size):
     model.close()
 
 
-def test_backbone_swin_small(dv):
+@pytest.mark.parametrize("size", [(160, 224), (160, 192)], ids=["160x224", "160x192"])
+def test_backbone_swin_small(dv, size):
     """Swin-Transformer + FPN (same kernels/graph as Swin-B, reduced widths/depths) vs the CPU oracle:
     patch embed, (shifted-)window MFMA attention with padding + relative-position bias + shift mask,
-    GELU MLP, fp32 residual stream, odd-size PatchMerging, per-output LayerNorm, FPN."""
+    GELU MLP, fp32 residual stream, PatchMerging, per-output LayerNorm, FPN.
+    160 x 224: token maps 40x56 -> 20x28 -> 10x14 -> 5x7, windows pad along H only (to 42, 21, 14, 7 rows; every width is a multiple
+    of 7).  160 x 192: 40x48 -> 20x24 -> 10x12 -> 5x6, windows pad along H as before AND along W at every stage (48 -> 49, 24 -> 28,
+    12 -> 14, 6 -> 7); the last map is smaller than a window on both axes.  Every merged map here is even (a frame is padded to a
+    multiple of 32): merging an odd map, and the window kernels on their own at single-kernel bounds, are tests/test_gpu_swin.py's."""
     from diffusionvid_amd.utils import synthetic
     from oracle import swin as oswin
     sw = dict(embed_dim=64, depths=(2, 2, 2, 1), heads=(2, 4, 8, 16), window=7)
     sd = synthetic.make_state_dict(0, swin=sw)
     g = torch.Generator().manual_seed(15)
-    imgs = torch.rand(2, 3, 160, 224, generator=g)        # tokens 40x56 -> 20x28 -> 10x14 -> 5x7 (pads to 42x56, 21x28, 14x14, 7x7)
+    imgs = torch.rand(2, 3, size[0], size[1], generator=g)
     mean, std = (123.675, 116.280, 103.530), (58.395, 57.120, 57.375)
     ref = oswin.backbone_swin_fpn(backbone_r101.normalizer(imgs, mean, std), sd, "backbone.", embed_dim=64, depths=sw["depths"],
                                   num_heads=sw["heads"])
     model = dv.Model(sd, res_blocks=(0, 0, 0, 0), backbone="swin", swin_embed_dim=64, swin_depths=sw["depths"],
                      swin_heads=sw["heads"])
-    model.reserve(2, 160, 224, 300)
+    model.reserve(2, size[0], size[1], 300)
     p3, p4, p5 = model.backbone(imgs.cuda())
+    tag = "backbone_swin_small" if size == (160, 224) else "backbone_swin_small[%dx%d]" % size
     for name, got in (("p3", p3), ("p4", p4), ("p5", p5)):
-        check(f"backbone_swin_small.{name}", dv.nchw_from_nhwc(got), ref[name], 3e-2, 3e-2)
+        check(f"{tag}.{name}", dv.nchw_from_nhwc(got), ref[name], 3e-2, 3e-2)
     model.close()
 
 
