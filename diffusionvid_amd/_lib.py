@@ -56,6 +56,7 @@ SIGNATURES = {
     "dvid_conv2d_nhwc_f32": (c_int, [c_void_p] * 8 + [c_int] * 12 + [c_void_p]),
     "dvid_mha_f32": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_int64] * 3 + [c_void_p]),
     "dvid_swin_window_attn_f32": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
+    "dvid_swin_window_attn_f32_ws": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
     "dvid_dynconv_f32": (c_int, [c_void_p] * 7 + [c_int, c_void_p]),
     "dvid_select_topk_features": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                           c_void_p]),
@@ -75,6 +76,8 @@ SIGNATURES = {
     "dvid_add_layernorm": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_void_p]),
     "dvid_swin_pack_relbias": (c_int, [c_void_p, c_int, c_void_p]),
     "dvid_swin_window_attn_f16": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
+    "dvid_swin_pack_relbias_ws": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "dvid_swin_window_attn_f16_ws": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
     "dvid_patch_merge_ln": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "dvid_nhwc_from_nchw": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "dvid_nchw_from_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

@@ -1,7 +1,7 @@
 // Multi-head attention on MFMA (fp16 operands, fp32 softmax / accumulate), head_dim 32.
 //
 // Used for the 300x300 per-frame self-attention of RCNNHead (box_head.py:514-518), the 2400x900 global-memory
-// cross-attention of DynamicHead (box_head.py:366-380) and Swin's 7x7 window attention (swintransformer.py:98-176); the
+// cross-attention of DynamicHead (box_head.py:366-380) and Swin's 7x7 / 12x12 window attention (swintransformer.py:98-176); the
 // in/out projections are igemm launches.  (The round-1 fp32 VALU kernel is in this file's history.)
 #include <stdlib.h>
 
@@ -312,6 +312,174 @@ int dvid_swin_window_attn_launch(const half_t* qkv, const half_t* qkv_bias16, co
     // four windows per workgroup, head-major order (one window per workgroup and window-major order were measured slower: profiles/r02e_*)
     hipLaunchKernelGGL(swin_window_attn_kernel<4>, dim3((unsigned)((nwin + 3) / 4 * nheads)), dim3(256), 0, s, qkv, qkv_bias16, relbias, out,
                        H, W, C, nheads, shift, 1.0f / sqrtf(32.f), (int)nwin, 1);
+    LAUNCH_CHECK();
+    return DVID_OK;
+}
+
+// =============================================================================================
+// Swin (shifted-)window attention, window 12x12 (144 tokens), shift 0 or 6, head_dim 32, MFMA: the 384-pretrained sizes
+// (B-22k-384, L-22k-384).  Same conventions as the 7x7 kernel above -- gather addresses resolve padding and roll, a padded position
+// holds the qkv bias and writes nothing, region ids from Hp / Wp / shift, -100 between regions, online fp32 softmax, P rounded to fp16
+// in registers -- on a different decomposition:
+//   144 queries are nine 16-row tiles exactly, so a workgroup is NINE waves (576 threads), one tile each, and no lane idles; the 576
+//   (key, 16-byte chunk) pairs of K and of V are one pair per thread.
+//   144 keys are 4.5 k-steps of 32: K rows and V^T columns 144..159 are zeroed once per workgroup (P is 0 there, but 0 x stale LDS
+//   bits could be 0 x NaN), scores of keys >= 144 are masked as the 7x7 kernel masks keys >= 49.
+//   LDS: K [160][32] 10 KB + V^T [32][168] 10.5 KB + token / region ids 1.1 KB = 21.8 KB.  (Registers, not LDS, set the occupancy:
+//   120 VGPRs with the bias row resident = 4 waves per SIMD = one nine-wave workgroup per CU at a time.)
+//   V^T pitch 168 halves = 84 dwords: the 16 rows a ds_read_b64 group touches start 20 banks apart (mod 64), conflict-free.
+//   A lane's bias (its query's 160-float row, 40 floats per lane) is the largest read of a (window, head) pair: 92 KB against 27 KB
+//   of q / k / v.  WPB consecutive windows of ONE head share it in registers, as above.
+// =============================================================================================
+namespace {
+
+template <int WPB>
+__global__ __launch_bounds__(576) void swin_window12_attn_kernel(const half_t* __restrict__ qkv, const half_t* __restrict__ qkv_bias16,
+                                                                  const float* __restrict__ relbias, half_t* __restrict__ out, int H,
+                                                                  int W, int C, int nheads, int shift, float scaling, int nwin) {
+    constexpr int WS = 12, NT = 144, NK = 160, RB_PITCH = SWIN12_RELBIAS_PITCH, VP = 168;
+    static_assert(RB_PITCH == NK, "one bias float per padded key");
+    __shared__ __attribute__((aligned(16))) half_t Ks[NK * 32];      // [key][32 dims], rows 144.. zero
+    __shared__ __attribute__((aligned(16))) half_t Vt[32 * VP];      // [dim][key], columns 144..159 zero
+    __shared__ int tok[NT];                                          // token row or -1 (padded position)
+    __shared__ int region[NT];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // head innermost, one contiguous run of (window group, head) pairs per XCD: see the 7x7 kernel
+    const int ngrp = (nwin + WPB - 1) / WPB;
+    const int lid = igemm_xcd_remap((int)blockIdx.x, ngrp * nheads);
+    const int grp = lid / nheads;
+    const int h = lid - grp * nheads;
+    const int Hp = (H + WS - 1) / WS * WS, Wp = (W + WS - 1) / WS * WS;
+    const int nwx = Wp / WS, nwy = Hp / WS;
+    const int qi = lane & 15, g = lane >> 4;
+    const int qpos = wave * 16 + qi;                                   // query position inside the window, < 144
+    const float* brow = relbias + ((long)h * NT + qpos) * RB_PITCH + 4 * g;
+    float4v bias4[NK / 16];                                            // keys 16 i + 4g .. + 3 of the query's row
+#pragma unroll
+    for (int i = 0; i < NK / 16; ++i) bias4[i] = *reinterpret_cast<const float4v*>(brow + 16 * i);
+    // the padded keys, once: no window writes them
+    if (tid < 64) *reinterpret_cast<half8*>(Ks + NT * 32 + tid * 8) = (half8){0, 0, 0, 0, 0, 0, 0, 0};
+    else if (tid < 192) *reinterpret_cast<half4*>(Vt + ((tid - 64) >> 2) * VP + NT + ((tid - 64) & 3) * 4) = (half4){0, 0, 0, 0};
+
+    for (int w = 0; w < WPB; ++w) {
+    int wid = grp * WPB + w;
+    if (wid >= nwin) break;                                            // (uniform over the workgroup)
+    if (w) __syncthreads();                                            // the previous window's LDS reads are done
+    const int wx = wid % nwx;
+    wid /= nwx;
+    const int wy = wid % nwy;
+    const int b = wid / nwy;
+
+    if (tid < NT) {
+        const int py = tid / WS, px = tid - py * WS;
+        const int ys = wy * WS + py, xs = wx * WS + px;                  // coordinates in the shifted, padded map
+        int y = ys + shift, x = xs + shift;                              // source coordinates before the roll
+        if (y >= Hp) y -= Hp;
+        if (x >= Wp) x -= Wp;
+        int reg = 0;
+        if (shift > 0) {
+            const int hr = ys < Hp - WS ? 0 : (ys < Hp - shift ? 1 : 2);
+            const int wr = xs < Wp - WS ? 0 : (xs < Wp - shift ? 1 : 2);
+            reg = hr * 3 + wr;
+        }
+        tok[tid] = (y < H && x < W) ? (b * H + y) * W + x : -1;
+        region[tid] = reg;
+    }
+    __syncthreads();
+    // ---- the window's global reads, ahead of the LDS staging and its barrier: K / V of the thread's (key, 16-byte chunk) and the
+    // lane's query fragment
+    const int tq = tok[qpos];
+    const int qreg = region[qpos];
+    const int key_s = tid >> 2, ch = tid & 3;                          // 576 threads = 144 keys x 4 chunks
+    const int tk = tok[key_s];
+    const half_t* src = tk >= 0 ? qkv + (long)tk * 3 * C : qkv_bias16;
+    const half8 kv = *reinterpret_cast<const half8*>(src + C + h * 32 + ch * 8);
+    const half8 vv = *reinterpret_cast<const half8*>(src + 2 * C + h * 32 + ch * 8);
+    const half_t* qsrc = tq >= 0 ? qkv + (long)tq * 3 * C : qkv_bias16;
+    const half8 qf = *reinterpret_cast<const half8*>(qsrc + h * 32 + g * 8);
+    // ---- stage K rows and V^T ----
+    *reinterpret_cast<half8*>(Ks + key_s * 32 + ch * 8) = kv;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) Vt[(ch * 8 + e) * VP + key_s] = vv[e];
+    __syncthreads();
+
+    float4v o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
+    float m = -1e30f, l = 0.f;
+#pragma unroll
+    for (int k0 = 0; k0 < NK; k0 += 32) {
+        const half8 kf0 = *reinterpret_cast<const half8*>(Ks + (k0 + qi) * 32 + g * 8);
+        const half8 kf1 = *reinterpret_cast<const half8*>(Ks + (k0 + 16 + qi) * 32 + g * 8);
+        float4v s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+        s0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf0, qf, s0, 0, 0, 0);
+        s1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf1, qf, s1, 0, 0, 0);
+        float sc[8];
+        float cmax = -1e30f;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int key = k0 + (r < 4 ? 4 * g + r : 16 + 4 * g + (r - 4));
+            float v = -1e30f;
+            if (key < NT) {
+                v = (r < 4 ? s0[r] * scaling + bias4[k0 / 16][r] : s1[r - 4] * scaling + bias4[k0 / 16 + 1][r - 4]);
+                if (shift > 0 && region[key] != qreg) v += -100.0f;
+            }
+            sc[r] = v;
+            cmax = fmaxf(cmax, v);
+        }
+        cmax = fmaxf(cmax, __shfl_xor(cmax, 16, 64));
+        cmax = fmaxf(cmax, __shfl_xor(cmax, 32, 64));
+        const float mn = fmaxf(m, cmax);
+        const float f = __expf(m - mn);
+        float psum = 0.f;
+        half8 pf;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float pj = (sc[j] > -1e29f) ? __expf(sc[j] - mn) : 0.f;
+            psum += pj;
+            pf[j] = (half_t)pj;
+        }
+        l = l * f + psum;
+        m = mn;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            o0[r] *= f;
+            o1[r] *= f;
+        }
+        const half_t* v0 = Vt + qi * VP + k0 + 4 * g;
+        const half_t* v1 = v0 + 16 * VP;
+        const half4 a00 = *reinterpret_cast<const half4*>(v0), a01 = *reinterpret_cast<const half4*>(v0 + 16);
+        const half4 a10 = *reinterpret_cast<const half4*>(v1), a11 = *reinterpret_cast<const half4*>(v1 + 16);
+        const half8 vf0 = {a00[0], a00[1], a00[2], a00[3], a01[0], a01[1], a01[2], a01[3]};
+        const half8 vf1 = {a10[0], a10[1], a10[2], a10[3], a11[0], a11[1], a11[2], a11[3]};
+        o0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf0, pf, o0, 0, 0, 0);
+        o1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf1, pf, o1, 0, 0, 0);
+    }
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    if (tq >= 0) {                                                     // padded positions produce no output
+        const float inv = 1.f / l;
+        half_t* op = out + (long)tq * C + h * 32 + 4 * g;
+        const half4 w0 = {(half_t)(o0[0] * inv), (half_t)(o0[1] * inv), (half_t)(o0[2] * inv), (half_t)(o0[3] * inv)};
+        const half4 w1 = {(half_t)(o1[0] * inv), (half_t)(o1[1] * inv), (half_t)(o1[2] * inv), (half_t)(o1[3] * inv)};
+        *reinterpret_cast<half4*>(op) = w0;
+        *reinterpret_cast<half4*>(op + 16) = w1;
+    }
+    }      // windows of the workgroup
+}
+
+}  // namespace
+
+// the 12x12 form of dvid_swin_window_attn_launch: relbias fp32 [nheads][144][SWIN12_RELBIAS_PITCH] (rows padded to 160 keys), shift 0 or 6
+int dvid_swin_window12_attn_launch(const half_t* qkv, const half_t* qkv_bias16, const float* relbias, half_t* out, int batch, int H,
+                                   int W, int C, int nheads, int shift, hipStream_t s) {
+    if (C != nheads * 32) return DVID_ERR_UNSUPPORTED;
+    const int nwy = (H + 11) / 12, nwx = (W + 11) / 12;
+    const long nwin = (long)batch * nwy * nwx;
+    if (nwin * nheads > 0x7fffffffL) return DVID_ERR_UNSUPPORTED;
+    if (nwin == 0) return DVID_OK;
+    // two windows per workgroup: halves the bias traffic and still leaves the deeper stages (6 windows x 32 heads per frame in the last)
+    // more workgroups than four would
+    hipLaunchKernelGGL(swin_window12_attn_kernel<2>, dim3((unsigned)((nwin + 1) / 2 * nheads)), dim3(576), 0, s, qkv, qkv_bias16, relbias, out,
+                       H, W, C, nheads, shift, 1.0f / sqrtf(32.f), (int)nwin);
     LAUNCH_CHECK();
     return DVID_OK;
 }

@@ -764,6 +764,119 @@ __global__ __launch_bounds__(64) void f32_swin_window_attn_kernel(const float* _
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// The same with 12 x 12 windows (144 tokens, shift 0 or 6).  One query per lane of one wave no longer covers a window, and 144 scores
+// per lane would not stay in registers: a workgroup is nine waves (576 threads) for one (window, head), FOUR lanes per query, lane
+// `part` of a query taking keys part, part + 4, ... (36 scores per lane).  The four partial maxima, sums and 32-float accumulators meet
+// in two xor-shuffles inside the quad; lane 0 of the quad writes the row.  K and V rows have a pitch of 36 floats (2 x 20.25 KB of
+// LDS): the four rows a quad reads in one ds_read_b128 start 36 banks apart, conflict-free.
+// ---------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(576) void f32_swin_window12_attn_kernel(const float* __restrict__ qkv, const float* __restrict__ qkv_bias,
+                                                                     const float* __restrict__ relbias, float* __restrict__ out, int H, int W, int C,
+                                                                     int nheads, int shift, float scaling, int nwin) {
+    constexpr int WS = 12, NT = 144, KP = 36, NPART = 4, NS = NT / NPART;
+    __shared__ __attribute__((aligned(16))) float Ks[NT * KP];
+    __shared__ __attribute__((aligned(16))) float Vs[NT * KP];
+    __shared__ int tok[NT];
+    __shared__ int region[NT];
+    const int tid = threadIdx.x;
+    const int lid = igemm_xcd_remap((int)blockIdx.x, nwin * nheads);
+    int wid = lid / nheads;
+    const int h = lid - wid * nheads;
+    const int Hp = (H + WS - 1) / WS * WS, Wp = (W + WS - 1) / WS * WS;
+    const int nwx = Wp / WS, nwy = Hp / WS;
+    const int wx = wid % nwx;
+    wid /= nwx;
+    const int wy = wid % nwy;
+    const int b = wid / nwy;
+    if (tid < NT) {
+        const int py = tid / WS, px = tid - py * WS;
+        const int ys = wy * WS + py, xs = wx * WS + px;          // coordinates in the shifted, padded map
+        int y = ys + shift, x = xs + shift;                      // source coordinates before the roll
+        if (y >= Hp) y -= Hp;
+        if (x >= Wp) x -= Wp;
+        int reg = 0;
+        if (shift > 0) {
+            const int hr = ys < Hp - WS ? 0 : (ys < Hp - shift ? 1 : 2);
+            const int wr = xs < Wp - WS ? 0 : (xs < Wp - shift ? 1 : 2);
+            reg = hr * 3 + wr;
+        }
+        tok[tid] = (y < H && x < W) ? (b * H + y) * W + x : -1;
+        region[tid] = reg;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < NT * 8; idx += 576) {
+        const int key = idx >> 3, c4 = (idx & 7) * 4;
+        const int t = tok[key];
+        const float* src = t >= 0 ? qkv + (long)t * 3 * C : qkv_bias;
+        *reinterpret_cast<float4v*>(&Ks[key * KP + c4]) = *reinterpret_cast<const float4v*>(src + C + h * 32 + c4);
+        *reinterpret_cast<float4v*>(&Vs[key * KP + c4]) = *reinterpret_cast<const float4v*>(src + 2 * C + h * 32 + c4);
+    }
+    const int qp = tid >> 2, part = tid & 3;                     // query position (< 144) and which quarter of its keys
+    const int tq = tok[qp], qreg = region[qp];
+    float qv[32];
+    {
+        const float* qsrc = (tq >= 0 ? qkv + (long)tq * 3 * C : qkv_bias) + h * 32;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float4v t = *reinterpret_cast<const float4v*>(qsrc + j * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) qv[j * 4 + e] = t[e] * scaling;
+        }
+    }
+    __syncthreads();
+    const float* brow = relbias + ((long)h * NT + qp) * SWIN12_RELBIAS_PITCH + part;
+    float sc[NS];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int key = i * NPART + part;
+        float d = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float4v t = *reinterpret_cast<const float4v*>(&Ks[key * KP + j * 4]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) d = __builtin_fmaf(qv[j * 4 + e], t[e], d);
+        }
+        d += brow[i * NPART];
+        if (shift > 0 && region[key] != qreg) d += -100.0f;
+        sc[i] = d;
+        mx = fmaxf(mx, d);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
+    float acc[32];
+#pragma unroll
+    for (int e = 0; e < 32; ++e) acc[e] = 0.f;
+    float den = 0.f;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int key = i * NPART + part;
+        const float pr = expf(sc[i] - mx);
+        den += pr;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float4v t = *reinterpret_cast<const float4v*>(&Vs[key * KP + j * 4]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[j * 4 + e] = __builtin_fmaf(pr, t[e], acc[j * 4 + e]);
+        }
+    }
+    den += __shfl_xor(den, 1, 64);
+    den += __shfl_xor(den, 2, 64);
+#pragma unroll
+    for (int e = 0; e < 32; ++e) {
+        acc[e] += __shfl_xor(acc[e], 1, 64);
+        acc[e] += __shfl_xor(acc[e], 2, 64);
+    }
+    if (part == 0 && tq >= 0) {         // padded positions produce no output
+        const float inv = 1.f / den;
+        float* op = out + (long)tq * C + h * 32;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            *reinterpret_cast<float4v*>(op + j * 4) = (float4v){acc[j * 4] * inv, acc[j * 4 + 1] * inv, acc[j * 4 + 2] * inv, acc[j * 4 + 3] * inv};
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // DynamicConv (box_head.py:687-711), one workgroup per box: F1 = roi[49 x 256] . param1[256 x 64] -> LayerNorm(64) + ReLU ->
 // F2 = F1 . param2[64 x 256] -> LayerNorm(256) + ReLU -> out[49 x 256].  The per-box parameters arrive as P1T[64][256] | P2T[256][64]
 // ([N][K] rows, the row order csrc/model.hip gives dynamic_layer), so both MFMA operands are K-contiguous rows read straight from
@@ -1223,6 +1336,18 @@ int dvid_f32_swin_window_attn_launch(const float* qkv, const float* qkv_bias, co
     if (nwin == 0) return DVID_OK;
     hipLaunchKernelGGL(f32_swin_window_attn_kernel, dim3((unsigned)(nwin * nheads)), dim3(64), 0, s, qkv, qkv_bias, relbias, out, H, W, C, nheads, shift,
                        0.17677669529663688110f, (int)nwin);
+    LAUNCH_CHECK();
+    return DVID_OK;
+}
+
+int dvid_f32_swin_window12_attn_launch(const float* qkv, const float* qkv_bias, const float* relbias, float* out, int batch, int H, int W, int C,
+                                       int nheads, int shift, hipStream_t s) {
+    if (C != nheads * 32) return DVID_ERR_UNSUPPORTED;
+    const long nwin = (long)batch * ((H + 11) / 12) * ((W + 11) / 12);
+    if (nwin * nheads > 0x7fffffffL) return DVID_ERR_UNSUPPORTED;
+    if (nwin == 0) return DVID_OK;
+    hipLaunchKernelGGL(f32_swin_window12_attn_kernel, dim3((unsigned)(nwin * nheads)), dim3(576), 0, s, qkv, qkv_bias, relbias, out, H, W, C, nheads,
+                       shift, 0.17677669529663688110f, (int)nwin);
     LAUNCH_CHECK();
     return DVID_OK;
 }

@@ -106,6 +106,10 @@ int dvid_outproj_ln_launch(const OutProjLnParams& p, hipStream_t s);
 constexpr int SWIN_RELBIAS_PITCH = 64;     // floats per query row of the relative-position bias table [heads][49][64] (keys 49..63 = 0)
 int dvid_swin_window_attn_launch(const half_t* qkv, const half_t* qkv_bias16, const float* relbias, half_t* out, int batch, int H,
                                  int W, int C, int nheads, int shift, hipStream_t s);
+// 12 x 12 windows (144 tokens, shift 0 or 6): relbias [heads][144][160] (keys 144..159 = 0)
+constexpr int SWIN12_RELBIAS_PITCH = 160;
+int dvid_swin_window12_attn_launch(const half_t* qkv, const half_t* qkv_bias16, const float* relbias, half_t* out, int batch, int H,
+                                   int W, int C, int nheads, int shift, hipStream_t s);
 int dvid_patch_merge_ln_launch(const float* x, const float* g, const float* b, half_t* y16, int B, int H, int W, int C, hipStream_t s,
                                float* y32 = nullptr);          // y32: an fp32 copy of the result (DTYPE float32: y16 null)
 
@@ -222,6 +226,9 @@ int dvid_f32_mha_launch(const float* q, const float* k, const float* v, float* o
 // padded window position), relbias [nheads][49][SWIN_RELBIAS_PITCH], out [B*H*W][C]
 int dvid_f32_swin_window_attn_launch(const float* qkv, const float* qkv_bias, const float* relbias, float* out, int batch, int H, int W, int C,
                                      int nheads, int shift, hipStream_t s);
+// the same with 12 x 12 windows: relbias [nheads][144][SWIN12_RELBIAS_PITCH]
+int dvid_f32_swin_window12_attn_launch(const float* qkv, const float* qkv_bias, const float* relbias, float* out, int batch, int H, int W, int C,
+                                       int nheads, int shift, hipStream_t s);
 // roi [R][49][256], params [R][32768] as P1T[64][256] | P2T[256][64], out [R][49][256]; range_flag (device int or null): the split-operand
 // form ORs 1 into it when a RoI / parameter magnitude exceeds the fp16 range
 int dvid_f32_dynconv_launch(const float* roi, const float* params, const float* g1, const float* b1, const float* g2, const float* b2,

@@ -259,7 +259,7 @@ struct SwinBlockW {
     LNW norm1, norm2;
     ConvW qkv, proj, fc1, fc2;
     half_t* qkv_bias16 = nullptr;   // q/k/v of a padded window position = the qkv bias
-    float* relbias = nullptr;       // [heads][49][SWIN_RELBIAS_PITCH] relative-position bias, gathered from the table at load
+    float* relbias = nullptr;       // [heads][w*w][swin_relbias_pitch(w)] relative-position bias, gathered from the table at load
 };
 struct SwinStageW {
     std::vector<SwinBlockW> blocks;
@@ -1125,17 +1125,20 @@ int backbone_swin_f32(dvid_model* m, const float* const* frames, int n, int heig
     float* attn = m->sw_attn16.as<float>();
     float* hid = m->sw_h16.as<float>();
     float* stage_out[4] = {nullptr, m->c3.as<float>(), m->c4.as<float>(), m->c5.as<float>()};
+    const int ws = m->cfg.swin_window;                           // 7 or 12 (dvid_model_finalize)
     int sh[4], sw[4];
     for (int st = 0; st < 4; ++st) {
         const SwinStageW& S = m->swin[st];
         const int C = S.dim, M = n * H * W;
         for (size_t b = 0; b < S.blocks.size(); ++b) {
             const SwinBlockW& B = S.blocks[b];
-            const int shift = (b % 2 == 0) ? 0 : 3;
+            const int shift = (b % 2 == 0) ? 0 : ws / 2;
             TRY(dvid_add_layernorm_launch(x, nullptr, B.norm1.g, B.norm1.b, ln, nullptr, M, C, 0, s));
             TRY(linear_run32(B.qkv, ln, M, qkv, 0, s));
-            TRY(prof_other("swin_attn_f32", M, C, 49, 4.0 * M * 49.0 * C, (double)M * C * 4.0 * 4.0, s,
-                           [&] { return dvid_f32_swin_window_attn_launch(qkv, B.qkv.bias, B.relbias, attn, n, H, W, C, S.heads, shift, s); }));
+            TRY(prof_other("swin_attn_f32", M, C, ws * ws, 4.0 * M * (double)(ws * ws) * C, (double)M * C * 4.0 * 4.0, s, [&] {
+                return ws == 12 ? dvid_f32_swin_window12_attn_launch(qkv, B.qkv.bias, B.relbias, attn, n, H, W, C, S.heads, shift, s)
+                                : dvid_f32_swin_window_attn_launch(qkv, B.qkv.bias, B.relbias, attn, n, H, W, C, S.heads, shift, s);
+            }));
             TRY(conv_run32(B.proj, attn, M, 1, 1, x, 0, x, 1, s));                                // x += proj(attn)
             TRY(dvid_add_layernorm_launch(x, nullptr, B.norm2.g, B.norm2.b, ln, nullptr, M, C, 0, s));
             TRY(linear_run32(B.fc1, ln, M, hid, 2, s));                                           // exact GELU
@@ -1190,17 +1193,22 @@ const std::vector<float>& time_embedding(dvid_model* m, int64_t t) {
     return m->time_cache.emplace(t, std::move(out)).first->second;
 }
 
-// Relative-position bias of a 7x7 window as the Swin attention kernels read it: table [169][nheads] (relative_position_bias_table)
-// -> out [nheads][49][SWIN_RELBIAS_PITCH], out[h][i][j] = table[index(i, j)][h] with the relative position index of
-// swintransformer.py:122-131, keys 49.. zero.  One 256-byte row per (head, query): a lane fetches the bias of its 16 keys as four
-// aligned 16-byte loads.
-void pack_swin_relbias(const float* table, int nheads, float* out) {
-    std::fill(out, out + (size_t)nheads * 49 * SWIN_RELBIAS_PITCH, 0.f);
+// Floats per query row of the packed bias: w*w keys rounded up to a multiple of 32 (the MFMA k-step), 64 for 7x7, 160 for 12x12.
+int swin_relbias_pitch(int w) { return (w * w + 31) / 32 * 32; }
+static_assert(SWIN_RELBIAS_PITCH == (7 * 7 + 31) / 32 * 32 && SWIN12_RELBIAS_PITCH == (12 * 12 + 31) / 32 * 32, "the kernels' pitches");
+
+// Relative-position bias of a w x w window as the Swin attention kernels read it: table [(2w-1)^2][nheads] (relative_position_bias_table)
+// -> out [nheads][w*w][pitch], out[h][i][j] = table[index(i, j)][h] with the relative position index of swintransformer.py:122-131,
+// keys w*w.. zero.  One 256-byte (7x7) or 640-byte (12x12) row per (head, query): a lane fetches the bias of its keys as aligned
+// 16-byte loads.
+void pack_swin_relbias(const float* table, int nheads, int w, float* out) {
+    const int nt = w * w, pitch = swin_relbias_pitch(w), span = 2 * w - 1;
+    std::fill(out, out + (size_t)nheads * nt * pitch, 0.f);
     for (int h = 0; h < nheads; ++h)
-        for (int i = 0; i < 49; ++i)
-            for (int j = 0; j < 49; ++j) {
-                const int relidx = ((i / 7 - j / 7) + 6) * 13 + ((i % 7 - j % 7) + 6);
-                out[((size_t)h * 49 + i) * SWIN_RELBIAS_PITCH + j] = table[(size_t)relidx * nheads + h];
+        for (int i = 0; i < nt; ++i)
+            for (int j = 0; j < nt; ++j) {
+                const int relidx = ((i / w - j / w) + w - 1) * span + ((i % w - j % w) + w - 1);
+                out[((size_t)h * nt + i) * pitch + j] = table[(size_t)relidx * nheads + h];
             }
 }
 
@@ -1278,7 +1286,8 @@ int dvid_model_finalize(dvid_model* m) {
         }
     }
     if (m->has_backbone && c.backbone_type == 1) {
-        if (c.swin_window != 7) FAIL(DVID_ERR_UNSUPPORTED, "Swin window size %d (only 7 is built)", c.swin_window);
+        if (c.swin_window != 7 && c.swin_window != 12) FAIL(DVID_ERR_UNSUPPORTED, "Swin window size %d (7 and 12 are built)", c.swin_window);
+        const int ws = c.swin_window, span = 2 * ws - 1;
         const std::string bu = "backbone.bottom_up.";
         {
             NEED(pw, bu + "patch_embed.proj.weight");
@@ -1307,9 +1316,9 @@ int dvid_model_finalize(dvid_model* m) {
                 for (size_t i = 0; i < qb16.size(); ++i) qb16[i] = f2h(qb->v[i]);
                 TRY(m->upload(qb16.data(), qb16.size() * sizeof(half_t), reinterpret_cast<void**>(&B.qkv_bias16)));
                 NEED(tb, p + ".attn.relative_position_bias_table");
-                if (tb->shape[0] != 169 || tb->shape[1] != S.heads) FAIL(DVID_ERR_ARG, "%s: bad bias table shape", p.c_str());
-                std::vector<float> rb((size_t)S.heads * 49 * SWIN_RELBIAS_PITCH);
-                pack_swin_relbias(tb->v.data(), S.heads, rb.data());
+                if (tb->shape[0] != span * span || tb->shape[1] != S.heads) FAIL(DVID_ERR_ARG, "%s: bad bias table shape", p.c_str());
+                std::vector<float> rb((size_t)S.heads * ws * ws * swin_relbias_pitch(ws));
+                pack_swin_relbias(tb->v.data(), S.heads, ws, rb.data());
                 TRY(upload_f32(m, rb, &B.relbias));
             }
             S.has_down = st < 3;
@@ -1783,16 +1792,18 @@ int dvid_backbone_swin_fpn_frames(dvid_model* m, const float* const* frames, int
     half_t* attn16 = m->sw_attn16.as<half_t>();
     half_t* h16 = m->sw_h16.as<half_t>();
     half_t* stage_out[4] = {nullptr, m->c3.as<half_t>(), m->c4.as<half_t>(), m->c5.as<half_t>()};
+    const int ws = m->cfg.swin_window;                           // 7 or 12 (dvid_model_finalize)
     int sh[4], sw[4];
     for (int st = 0; st < 4; ++st) {
         const SwinStageW& S = m->swin[st];
         const int C = S.dim, M = n * H * W;
         for (size_t b = 0; b < S.blocks.size(); ++b) {
             const SwinBlockW& B = S.blocks[b];
-            const int shift = (b % 2 == 0) ? 0 : 3;                                             // window_size // 2
+            const int shift = (b % 2 == 0) ? 0 : ws / 2;                                        // window_size // 2
             TRY(dvid_add_layernorm_launch(x, nullptr, B.norm1.g, B.norm1.b, nullptr, ln16, M, C, 0, s));
             TRY(linear_run(B.qkv, ln16, M, qkv16, 0, 0, s));
-            TRY(dvid_swin_window_attn_launch(qkv16, B.qkv_bias16, B.relbias, attn16, n, H, W, C, S.heads, shift, s));
+            if (ws == 12) TRY(dvid_swin_window12_attn_launch(qkv16, B.qkv_bias16, B.relbias, attn16, n, H, W, C, S.heads, shift, s));
+            else TRY(dvid_swin_window_attn_launch(qkv16, B.qkv_bias16, B.relbias, attn16, n, H, W, C, S.heads, shift, s));
             TRY(conv_run(B.proj, attn16, M, 1, 1, x, 0, 1, x, 1, 1, s));                         // x += proj(attn)   (fp32 stream)
             TRY(dvid_add_layernorm_launch(x, nullptr, B.norm2.g, B.norm2.b, nullptr, ln16, M, C, 0, s));
             TRY(linear_run(B.fc1, ln16, M, h16, 2, 0, s));                                       // GELU epilogue
@@ -2093,6 +2104,19 @@ int dvid_swin_window_attn_f32(const float* qkv, const float* qkv_bias, const flo
     return DVID_OK;
 }
 
+int dvid_swin_window_attn_f32_ws(const float* qkv, const float* qkv_bias, const float* relbias, float* out, int batch, int H, int W, int C,
+                                 int nheads, int shift, int window, void* stream) {
+    if (window == 7) return dvid_swin_window_attn_f32(qkv, qkv_bias, relbias, out, batch, H, W, C, nheads, shift, stream);
+    g_err[0] = 0;
+    if (window != 12) FAIL(DVID_ERR_UNSUPPORTED, "swin window attention: window size %d (7 and 12 are built)", window);
+    if (!qkv || !qkv_bias || !relbias || !out) FAIL(DVID_ERR_ARG, "swin window attention: null pointer");
+    if (batch <= 0 || H <= 0 || W <= 0 || nheads <= 0 || shift < 0 || shift >= window)
+        FAIL(DVID_ERR_ARG, "swin window attention: bad sizes (batch %d, %d x %d tokens, %d heads, shift %d, window %d)", batch, H, W, nheads, shift, window);
+    const int rc = dvid_f32_swin_window12_attn_launch(qkv, qkv_bias, relbias, out, batch, H, W, C, nheads, shift, reinterpret_cast<hipStream_t>(stream));
+    if (rc != DVID_OK) FAIL(rc, "swin window attention (fp32, window 12): C %d with %d heads on %d x %d x %d tokens is not supported", C, nheads, batch, H, W);
+    return DVID_OK;
+}
+
 int dvid_dynconv_f32(const float* roi, const float* params, const float* g1, const float* b1, const float* g2, const float* b2, float* out,
                      int rows, void* stream) {
     g_err[0] = 0;
@@ -2234,7 +2258,15 @@ int dvid_add_layernorm(const float* x, const float* r, const float* g, const flo
 int dvid_swin_pack_relbias(const float* table, int nheads, float* out) {
     g_err[0] = 0;
     if (!table || !out || nheads <= 0) FAIL(DVID_ERR_ARG, "swin relative-position bias: null pointer or %d heads", nheads);
-    pack_swin_relbias(table, nheads, out);
+    pack_swin_relbias(table, nheads, 7, out);
+    return DVID_OK;
+}
+
+int dvid_swin_pack_relbias_ws(const float* table, int nheads, int window, float* out) {
+    g_err[0] = 0;
+    if (!table || !out || nheads <= 0) FAIL(DVID_ERR_ARG, "swin relative-position bias: null pointer or %d heads", nheads);
+    if (window != 7 && window != 12) FAIL(DVID_ERR_UNSUPPORTED, "swin relative-position bias: window size %d (7 and 12 are built)", window);
+    pack_swin_relbias(table, nheads, window, out);
     return DVID_OK;
 }
 
@@ -2247,6 +2279,20 @@ int dvid_swin_window_attn_f16(const void* qkv, const void* qkv_bias16, const flo
     const int rc = dvid_swin_window_attn_launch(reinterpret_cast<const half_t*>(qkv), reinterpret_cast<const half_t*>(qkv_bias16), relbias,
                                                 reinterpret_cast<half_t*>(out), batch, H, W, C, nheads, shift, reinterpret_cast<hipStream_t>(stream));
     if (rc != DVID_OK) FAIL(rc, "swin window attention: C %d with %d heads on %d x %d x %d tokens is not supported", C, nheads, batch, H, W);
+    return DVID_OK;
+}
+
+int dvid_swin_window_attn_f16_ws(const void* qkv, const void* qkv_bias16, const float* relbias, void* out, int batch, int H, int W, int C,
+                                 int nheads, int shift, int window, void* stream) {
+    if (window == 7) return dvid_swin_window_attn_f16(qkv, qkv_bias16, relbias, out, batch, H, W, C, nheads, shift, stream);
+    g_err[0] = 0;
+    if (window != 12) FAIL(DVID_ERR_UNSUPPORTED, "swin window attention: window size %d (7 and 12 are built)", window);
+    if (!qkv || !qkv_bias16 || !relbias || !out) FAIL(DVID_ERR_ARG, "swin window attention: null pointer");
+    if (batch <= 0 || H <= 0 || W <= 0 || nheads <= 0 || shift < 0 || shift >= window)
+        FAIL(DVID_ERR_ARG, "swin window attention: bad sizes (batch %d, %d x %d tokens, %d heads, shift %d, window %d)", batch, H, W, nheads, shift, window);
+    const int rc = dvid_swin_window12_attn_launch(reinterpret_cast<const half_t*>(qkv), reinterpret_cast<const half_t*>(qkv_bias16), relbias,
+                                                  reinterpret_cast<half_t*>(out), batch, H, W, C, nheads, shift, reinterpret_cast<hipStream_t>(stream));
+    if (rc != DVID_OK) FAIL(rc, "swin window attention (window 12): C %d with %d heads on %d x %d x %d tokens is not supported", C, nheads, batch, H, W);
     return DVID_OK;
 }
 

@@ -29,13 +29,16 @@ from ...utils import synthetic
 from ..roi_heads.box_head.box_head import DynamicHead
 
 _DEPTH_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
-# size2config of mega_core/modeling/backbone/swintransformer.py:655-712 (window-7 variants; head dim 32 in all of them)
+# size2config of mega_core/modeling/backbone/swintransformer.py:655-712 (head dim 32 in all of them; the 384-pretrained sizes use
+# 12x12 windows)
 _SWIN_SIZES = {
     "T": dict(embed_dim=96, depths=(2, 2, 6, 2), heads=(3, 6, 12, 24), window=7),
     "S": dict(embed_dim=96, depths=(2, 2, 18, 2), heads=(3, 6, 12, 24), window=7),
     "B": dict(embed_dim=128, depths=(2, 2, 18, 2), heads=(4, 8, 16, 32), window=7),
     "B-22k": dict(embed_dim=128, depths=(2, 2, 18, 2), heads=(4, 8, 16, 32), window=7),
     "L-22k": dict(embed_dim=192, depths=(2, 2, 18, 2), heads=(6, 12, 24, 48), window=7),
+    "B-22k-384": dict(embed_dim=128, depths=(2, 2, 18, 2), heads=(4, 8, 16, 32), window=12),
+    "L-22k-384": dict(embed_dim=192, depths=(2, 2, 18, 2), heads=(6, 12, 24, 48), window=12),
 }
 
 
@@ -126,7 +129,7 @@ class DiffusionDet(nn.Module):
         self.swin = None
         if cfg.MODEL.BACKBONE.NAME == "build_swintransformer_fpn_backbone":
             if cfg.MODEL.SWIN.SIZE not in _SWIN_SIZES:
-                raise NotImplementedError("Swin size %r is not built (window-7 sizes only)" % cfg.MODEL.SWIN.SIZE)
+                raise NotImplementedError("Swin size %r is not built (known: %s)" % (cfg.MODEL.SWIN.SIZE, ", ".join(_SWIN_SIZES)))
             if tuple(cfg.MODEL.SWIN.OUT_FEATURES) != (1, 2, 3):
                 raise NotImplementedError("MODEL.SWIN.OUT_FEATURES must be (1, 2, 3)")
             self.swin = dict(getattr(cfg.MODEL.SWIN, "CONFIG_OVERRIDE", None) or _SWIN_SIZES[cfg.MODEL.SWIN.SIZE])

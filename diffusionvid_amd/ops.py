@@ -225,39 +225,51 @@ def add_layernorm(x, r, g, b, relu=False):
     return y
 
 
-def swin_pack_relbias(table):
-    """relative_position_bias_table fp32 [169, heads] (host) -> the table the Swin attention kernels read, fp32 [heads, 49, 64] (host;
-    keys 49..63 zero), packed by the library's own loader code."""
+def _swin_relbias_pitch(window):
+    return (window * window + 31) // 32 * 32
+
+
+def swin_pack_relbias(table, window=7):
+    """relative_position_bias_table fp32 [(2w-1)^2, heads] (host) -> the table the Swin attention kernels read, fp32 [heads, w*w, pitch]
+    (host; pitch = w*w rounded up to a multiple of 32: [heads, 49, 64] for window 7, [heads, 144, 160] for window 12; keys w*w.. zero),
+    packed by the library's own loader code."""
     table = table.detach().cpu().contiguous()
-    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[0] != 169:
-        raise TypeError(f"expected a float32 [169, heads] table, got {table.dtype} {tuple(table.shape)}")
-    out = torch.empty((table.shape[1], 49, 64), dtype=torch.float32)
-    call("dvid_swin_pack_relbias", ptr(table), table.shape[1], ptr(out))
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[0] != (2 * window - 1) ** 2:
+        raise TypeError(f"expected a float32 [{(2 * window - 1) ** 2}, heads] table, got {table.dtype} {tuple(table.shape)}")
+    out = torch.empty((table.shape[1], window * window, _swin_relbias_pitch(window)), dtype=torch.float32)
+    if window == 7:
+        call("dvid_swin_pack_relbias", ptr(table), table.shape[1], ptr(out))
+    else:
+        call("dvid_swin_pack_relbias_ws", ptr(table), table.shape[1], window, ptr(out))
     return out
 
 
-def _swin_window_attn(name, dtype, qkv, qkv_bias, relbias, B, H, W, nheads, shift, out):
+def _swin_window_attn(name, dtype, qkv, qkv_bias, relbias, B, H, W, nheads, shift, out, window):
     qkv, qkv_bias, relbias = _cuda(qkv, dtype), _cuda(qkv_bias, dtype), _cuda(relbias, torch.float32)
     C = qkv.shape[1] // 3
-    assert tuple(qkv.shape) == (B * H * W, 3 * C) and qkv_bias.numel() == 3 * C and tuple(relbias.shape) == (nheads, 49, 64)
+    assert tuple(qkv.shape) == (B * H * W, 3 * C) and qkv_bias.numel() == 3 * C
+    assert tuple(relbias.shape) == (nheads, window * window, _swin_relbias_pitch(window))
     if out is None:
         out = torch.empty((B * H * W, C), dtype=dtype, device=qkv.device)
     out = _cuda(out, dtype)
     assert out.shape[0] >= B * H * W and out.shape[1] == C
-    call(name, ptr(qkv), ptr(qkv_bias), ptr(relbias), ptr(out), B, H, W, C, nheads, shift, stream_ptr())
+    if window == 7:
+        call(name, ptr(qkv), ptr(qkv_bias), ptr(relbias), ptr(out), B, H, W, C, nheads, shift, stream_ptr())
+    else:
+        call(name + "_ws", ptr(qkv), ptr(qkv_bias), ptr(relbias), ptr(out), B, H, W, C, nheads, shift, window, stream_ptr())
     return out
 
 
-def swin_window_attn_f16(qkv16, qkv_bias16, relbias, B, H, W, nheads, shift, out=None):
+def swin_window_attn_f16(qkv16, qkv_bias16, relbias, B, H, W, nheads, shift, out=None, window=7):
     """Swin (shifted-)window attention on a [B, H, W] token map: qkv fp16 [B*H*W, 3C] (C = 32 * heads), qkv_bias16 fp16 [3C] (what a
-    padded window position holds), relbias fp32 [heads, 49, 64] (swin_pack_relbias) -> fp16 [B*H*W, C], written into `out`'s first
-    B*H*W rows when one is given."""
-    return _swin_window_attn("dvid_swin_window_attn_f16", torch.float16, qkv16, qkv_bias16, relbias, B, H, W, nheads, shift, out)
+    padded window position holds), relbias fp32 [heads, w*w, pitch] (swin_pack_relbias with the same `window`, 7 or 12) -> fp16
+    [B*H*W, C], written into `out`'s first B*H*W rows when one is given."""
+    return _swin_window_attn("dvid_swin_window_attn_f16", torch.float16, qkv16, qkv_bias16, relbias, B, H, W, nheads, shift, out, window)
 
 
-def swin_window_attn_f32(qkv, qkv_bias, relbias, B, H, W, nheads, shift, out=None):
+def swin_window_attn_f32(qkv, qkv_bias, relbias, B, H, W, nheads, shift, out=None, window=7):
     """the fp32 form of swin_window_attn_f16 (csrc/f32.hip)"""
-    return _swin_window_attn("dvid_swin_window_attn_f32", torch.float32, qkv, qkv_bias, relbias, B, H, W, nheads, shift, out)
+    return _swin_window_attn("dvid_swin_window_attn_f32", torch.float32, qkv, qkv_bias, relbias, B, H, W, nheads, shift, out, window)
 
 
 def patch_merge_ln(x, g, b, f16=True, f32=True, out16=None, out32=None):

@@ -67,7 +67,7 @@ typedef struct dvid_config {
     int swin_embed_dim;    /* size2config[MODEL.SWIN.SIZE]: 128 for B */
     int swin_depths[4];    /* {2,2,18,2} */
     int swin_heads[4];     /* {4,8,16,32}; head dim must be 32 */
-    int swin_window;       /* 7 */
+    int swin_window;       /* 7, or 12 for the 384-pretrained sizes (B-22k-384, L-22k-384) */
 } dvid_config;
 
 const char* dvid_last_error(void);
@@ -183,6 +183,9 @@ int dvid_mha_f32(const float* q, const float* k, const float* v, float* out, int
 /* Swin (shifted-)window attention, fp32 form of dvid_swin_window_attn_f16 below: qkv fp32 [batch*H*W][3C], qkv_bias fp32 [3C], out fp32. */
 int dvid_swin_window_attn_f32(const float* qkv, const float* qkv_bias, const float* relbias, float* out, int batch, int H, int W, int C,
                               int nheads, int shift, void* stream);
+/* The same with the window size as an argument: the fp32 form of dvid_swin_window_attn_f16_ws below. */
+int dvid_swin_window_attn_f32_ws(const float* qkv, const float* qkv_bias, const float* relbias, float* out, int batch, int H, int W, int C,
+                                 int nheads, int shift, int window, void* stream);
 int dvid_dynconv_f32(const float* roi, const float* params, const float* g1, const float* b1, const float* g2, const float* b2, float* out,
                      int rows, void* stream);
 int dvid_select_topk_features(const float* logits, int n_frames, int m, int num_classes, int k1, int k2, const float* feats,
@@ -251,6 +254,14 @@ int dvid_add_layernorm(const float* x, const float* r, const float* g, const flo
 int dvid_swin_pack_relbias(const float* table, int nheads, float* out);
 int dvid_swin_window_attn_f16(const void* qkv, const void* qkv_bias16, const float* relbias, void* out, int batch, int H, int W, int C,
                               int nheads, int shift, void* stream);
+/* The two entries above with the window size w as an argument, 7 or 12 (DVID_ERR_UNSUPPORTED otherwise; nothing is written on a refusal).
+ * w = 7 forwards to them.  w = 12 (the 384-pretrained Swin sizes): table [(2w-1)^2 = 529][nheads] -> out [nheads][144][160] floats
+ * (pitch = w*w rounded up to a multiple of 32), columns 144..159 zero; the token map is padded to multiples of 12 and rolled by -shift,
+ * 0 <= shift < w (DVID_ERR_ARG otherwise), attended per 12x12 window (csrc/attention.hip: swin_window12_attn_kernel; fp32:
+ * csrc/f32.hip: f32_swin_window12_attn_kernel).  C = 32 * nheads, DVID_ERR_UNSUPPORTED otherwise. */
+int dvid_swin_pack_relbias_ws(const float* table, int nheads, int window, float* out);
+int dvid_swin_window_attn_f16_ws(const void* qkv, const void* qkv_bias16, const float* relbias, void* out, int batch, int H, int W, int C,
+                                 int nheads, int shift, int window, void* stream);
 int dvid_patch_merge_ln(const float* x, const float* g, const float* b, void* y16, float* y32, int B, int H, int W, int C, void* stream);
 int dvid_nhwc_from_nchw(const float* in, void* out_f16, int n, int h, int w, int c, void* stream);
 int dvid_nchw_from_nhwc(const void* in_f16, float* out, int n, int h, int w, int c, void* stream);
