@@ -416,7 +416,7 @@ int launch_c64(IgemmParams p, hipStream_t s) {
 }
 
 // ---- the space-to-depth stem: 4x4 taps / stride 1 over 16 channels (32 bytes per pixel), 64 output channels -------------------------
-// (model.hip make_stem_s2d: the 7x7 / stride-2 stem over the 2x2 space-to-depth image; window rows y - 2 .. y + 1, columns x - 2 .. x + 1.)
+// (weights.hip make_stem_s2d: the 7x7 / stride-2 stem over the 2x2 space-to-depth image; window rows y - 2 .. y + 1, columns x - 2 .. x + 1.)
 // One MFMA K step (16 halves) is one tap.  Per 8 x 32 patch: the 11 x 35 halo (12 KB) and all 16 taps' weights (32 KB, tap-major) are
 // staged in the prologue -- 44 KB of DMA per 256 rows against 192 KB in igemm2 -- and 48 KB of LDS put three workgroups on a CU, which
 // cover each other's prologue and epilogue.  32-byte rows: two 16-byte slots per pixel / weight row, slot = half ^ bit 3 of the

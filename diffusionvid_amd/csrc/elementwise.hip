@@ -28,7 +28,7 @@ __global__ void prep_images_kernel(FrameTable in, half_t* __restrict__ out, long
 
 // The same normaliser with a 2x2 space-to-depth layout: out[n][Y][X][(dy*2 + dx)*3 + c] (12 channels + 4 zero = 32 bytes per
 // 2x2 pixel block).  The 7x7 / stride-2 stem convolution over 3 channels is then a 4x4 / stride-1 convolution over these 16
-// channels (csrc/model.hip: make_stem_s2d): K = 256 instead of 448 padded columns and half the input bytes.
+// channels (csrc/weights.hip: make_stem_s2d): K = 256 instead of 448 padded columns and half the input bytes.
 __global__ void prep_images_s2d_kernel(FrameTable in, half_t* __restrict__ out, long nblk, int h2, int w2, float m0,
                                        float m1, float m2, float s0, float s1, float s2) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

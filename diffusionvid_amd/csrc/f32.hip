@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // lo = fp16(v - hi), and a product row is accumulated as  lo_a * hi_b + hi_a * lo_b + hi_a * hi_b  on v_mfma_f32_32x32x16_f16 (exact
 // fp16 x fp16 products, fp32 accumulation): three passes of the fp16 MFMA, 16 / 3 = 5.3 x the fp32 MFMA's rate.  What is dropped is
 // lo_a * lo_b (2^-22 of the product) and the rounding of lo (2^-22 relative while lo is a normal fp16 number, i.e. |v| >= 2^-3; an absolute
-// 3e-8 below that).  The packed weight rows are scaled by a power of two so that each row's largest magnitude lies in [0.5, 1) (csrc/model.hip:
+// 3e-8 below that).  The packed weight rows are scaled by a power of two so that each row's largest magnitude lies in [0.5, 1) (csrc/weights.hip:
 // make_conv; undone exactly by `wscale` in the epilogue) -- a weight of 0.02 would otherwise carry its lo part as an fp16 subnormal.
 // Activations need |v| < 65504 (true of every tensor on this path by orders of magnitude).  Library option f32_split (default 1) selects
 // it; 0 = the exact-fp32 kernel above.  Both are held to the same bounds by tests/test_gpu_f32.py and the end-to-end float32 tests.
@@ -879,7 +879,7 @@ __global__ __launch_bounds__(576) void f32_swin_window12_attn_kernel(const float
 // ---------------------------------------------------------------------------------------------------------------------------------
 // DynamicConv (box_head.py:687-711), one workgroup per box: F1 = roi[49 x 256] . param1[256 x 64] -> LayerNorm(64) + ReLU ->
 // F2 = F1 . param2[64 x 256] -> LayerNorm(256) + ReLU -> out[49 x 256].  The per-box parameters arrive as P1T[64][256] | P2T[256][64]
-// ([N][K] rows, the row order csrc/model.hip gives dynamic_layer), so both MFMA operands are K-contiguous rows read straight from
+// ([N][K] rows, the row order csrc/weights.hip gives dynamic_layer), so both MFMA operands are K-contiguous rows read straight from
 // global as float4 fragments; F1 / F2 cross LDS for the row statistics.
 // ---------------------------------------------------------------------------------------------------------------------------------
 constexpr int DC_P1 = 68, DC_P2 = 260;

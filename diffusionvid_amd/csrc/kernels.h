@@ -1,5 +1,5 @@
 // Internal launcher declarations (C++), one per HIP kernel family.  The public C ABI is
-// include/dvid_hip.h; these are what the runtime (model.hip) and the C-ABI op wrappers call.
+// include/dvid_hip.h; these are what the runtime (runtime.h and its files) and the C-ABI op wrappers (ops_abi.hip) call.
 #pragma once
 #include "common.h"
 
@@ -73,11 +73,14 @@ int dvid_modulate_launch(const float* x, const float* scale, int scale_ld, const
 int dvid_silu_f16_launch(const float* x, half_t* y, long n, hipStream_t s);
 
 // roialign.hip
-struct RoiLevels {
-    const half_t* feat[3];
+template <typename T>          // the three FPN levels' maps: fp16 (RoiLevels) or fp32 (RoiLevels32, f32.hip)
+struct RoiLevelsT {
+    const T* feat[3];
     int h[3], w[3];
     float scale[3];
 };
+using RoiLevels = RoiLevelsT<half_t>;
+using RoiLevels32 = RoiLevelsT<float>;
 int dvid_roialign_launch(const RoiLevels& lv, int channels, const float* boxes, int n_img, int boxes_per_img, half_t* roi_out,
                          float* mean_out, hipStream_t s);
 
@@ -90,7 +93,7 @@ int dvid_mha_mfma_launch(const half_t* q, const half_t* k, const half_t* v, half
 struct OutProjLnParams {
     const void* x;          // [rows, 256]: fp16 (mode 0) or fp32 (modes 1, 2)
     int mode;               // 0: fp16 MFMA; 1: fp32 rows as split (hi, lo) fp16 operands, three fp16-MFMA passes; 2: fp32 MFMA
-    const half_t* wf_hi;    // [256][256] in MFMA fragment order (model.hip: make_frags): the fp16 weights (mode 0) / the hi plane (mode 1)
+    const half_t* wf_hi;    // [256][256] in MFMA fragment order (weights.hip: make_frags): the fp16 weights (mode 0) / the hi plane (mode 1)
     const half_t* wf_lo;    // mode 1: the lo plane, same order
     const float* w32;       // mode 2: the scaled fp32 rows [256][256]
     const float* wscale;    // modes 1, 2: [256], channel n's sum is multiplied by wscale[n]
@@ -121,7 +124,7 @@ int dvid_dynconv_roi_launch(const RoiLevels& lv, int channels, const float* boxe
                             const float* g1, const float* b1, const float* g2, const float* b2, half_t* out, hipStream_t s);
 
 // headtail.hip: FFN + norm3 + modulation + cls / reg towers + class_logits + bboxes_delta + apply_deltas of one RCNNHead pass as one
-// row-tile kernel.  Every `*f` weight is in MFMA fragment order (model.hip: make_frags): [n-tile of 32 rows][K step of 16][lane][8].
+// row-tile kernel.  Every `*f` weight is in MFMA fragment order (weights.hip: make_frags): [n-tile of 32 rows][K step of 16][lane][8].
 struct HeadTailParams {
     const half_t* x16;          // [R, 256] fp16   norm2 output (operand of linear1)
     const float* obj32;         // [R, 256] fp32   the same rows, the FFN's residual
@@ -207,11 +210,6 @@ int dvid_f32_wstat_launch_tiles(const F32GemmParams& p, hipStream_t s);
 // csrc/f32_conv3x3.hip: 3x3 / stride-1 layers with the halo staged and split once per channel chunk (another summation order than the tiled kernel)
 bool dvid_f32_conv3x3_supported(const F32GemmParams& p);
 int dvid_f32_conv3x3_launch(const F32GemmParams& p, hipStream_t s);
-struct RoiLevels32 {
-    const float* feat[3];
-    int h[3], w[3];
-    float scale[3];
-};
 int dvid_f32_prep_images_launch(const float* const* frames, float* nhwc4, int n, int h, int w, const float* mean, const float* std_, hipStream_t s);
 int dvid_f32_maxpool3x3s2_launch(const float* in, float* out, int n, int h, int w, int c, hipStream_t s);
 int dvid_f32_silu_launch(const float* x, float* y, long n, hipStream_t s);

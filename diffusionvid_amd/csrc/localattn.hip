@@ -7,12 +7,12 @@
 // lane's own registers plus ONE shuffle, and the pre-LayerNorm rows never leave the registers (the layer-by-layer form writes
 // them to HBM as fp32 and reads them back).  Two-pass statistics (mean, then centred squares), eps 1e-5.
 //
-// MODE 0 (DTYPE float16): fp16 rows, fp16 weights in fragment order (model.hip: make_frags), v_mfma_f32_32x32x16_f16, fp32 sums.
+// MODE 0 (DTYPE float16): fp16 rows, fp16 weights in fragment order (weights.hip: make_frags), v_mfma_f32_32x32x16_f16, fp32 sums.
 // MODE 1 (DTYPE float32, option f32_split = 1): fp32 rows split in the kernel into (hi, lo) fp16 parts, the scaled weight rows as
 //         (hi, lo) fragment planes, three MFMA passes lo*hi + hi*lo + hi*hi as in csrc/f32.hip; a row value beyond the fp16 range
 //         sets `range_flag`.
 // MODE 2 (DTYPE float32, f32_split = 0): exact fp32 products on v_mfma_f32_32x32x2f32, the scaled fp32 rows [256][256] read in place.
-// MODE 1 / 2 multiply channel n's sum by wscale[n] (the power of two the packed row was divided by, model.hip: make_conv).
+// MODE 1 / 2 multiply channel n's sum by wscale[n] (the power of two the packed row was divided by, weights.hip: make_conv).
 #include "kernels.h"
 
 namespace {

@@ -1,0 +1,277 @@
+// The stand-alone ops of the C ABI (include/dvid_hip.h): one thin wrapper per kernel launcher, for the tests and for callers that
+// run a single layer -- argument checks, pointer casts, the error message.  No model state.
+#include "runtime.h"
+
+extern "C" {
+int dvid_roialign_v2_multilevel(const void* p3, const void* p4, const void* p5, int n_frames, int height, int width, int channels,
+                                const float* boxes, int boxes_per_frame, void* roi_out, float* mean_out, void* stream) {
+    g_err[0] = 0;
+    if (height % 32 || width % 32) FAIL(DVID_ERR_ARG, "height/width must be multiples of 32");
+    TRY(dvid_roialign_launch(roi_levels<half_t>(p3, p4, p5, height, width, 0, channels), channels, boxes, n_frames, boxes_per_frame, reinterpret_cast<half_t*>(roi_out), mean_out,
+                             reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_roialign_v2_multilevel_f32(const float* p3, const float* p4, const float* p5, int n_frames, int height, int width, int channels,
+                                    const float* boxes, int boxes_per_frame, float* roi_out, float* mean_out, void* stream) {
+    g_err[0] = 0;
+    if (height % 32 || width % 32) FAIL(DVID_ERR_ARG, "height/width must be multiples of 32");
+    TRY(dvid_f32_roialign_launch(roi_levels<float>(p3, p4, p5, height, width, 0, channels), channels, boxes, n_frames, boxes_per_frame, roi_out, mean_out, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_conv2d_nhwc_f32(const float* in, const float* w, const void* w_hi, const void* w_lo, const float* bias, const float* row_scale, const float* residual,
+                         float* out, int n, int h, int wd, int cin, int cout, int kh, int kw, int stride, int pad, int kpad, int relu, int residual_mode,
+                         void* stream) {
+    g_err[0] = 0;
+    if (cin % 4 || kpad % 16 || kpad < kh * kw * cin || pad < 0) FAIL(DVID_ERR_ARG, "fp32 conv: cin %% 4 == 0, kpad %% 16 == 0, kpad >= kh*kw*cin, pad >= 0");
+    ConvW cw;
+    cw.w32 = const_cast<float*>(w);
+    cw.w16hi = reinterpret_cast<half_t*>(const_cast<void*>(w_hi));
+    cw.w16lo = reinterpret_cast<half_t*>(const_cast<void*>(w_lo));
+    cw.bias = const_cast<float*>(bias);
+    cw.wscale32 = const_cast<float*>(row_scale);
+    cw.cin32 = cin;
+    cw.cin_real = cin;
+    cw.cout = cout;
+    cw.kh = kh;
+    cw.kw = kw;
+    cw.stride = stride;
+    cw.pad = pad;
+    cw.kpad32 = kpad;
+    TRY(conv_run32(cw, in, n, h, wd, out, reinterpret_cast<hipStream_t>(stream), {.relu = relu, .res = residual, .res_mode = residual_mode}));
+    return DVID_OK;
+}
+
+int dvid_mha_f32(const float* q, const float* k, const float* v, float* out, int batch, int lq, int lk, int nheads, int q_ld, int kv_ld, int out_ld,
+                 int64_t q_bs, int64_t kv_bs, int64_t out_bs, void* stream) {
+    g_err[0] = 0;
+    TRY(dvid_f32_mha_launch(q, k, v, out, batch, lq, lk, nheads, q_ld, kv_ld, out_ld, (long)q_bs, (long)kv_bs, (long)out_bs,
+                            reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_swin_window_attn_f32(const float* qkv, const float* qkv_bias, const float* relbias, float* out, int batch, int H, int W, int C,
+                              int nheads, int shift, void* stream) {
+    g_err[0] = 0;
+    if (!qkv || !qkv_bias || !relbias || !out) FAIL(DVID_ERR_ARG, "swin window attention: null pointer");
+    if (batch <= 0 || H <= 0 || W <= 0 || nheads <= 0 || shift < 0 || shift >= 7)
+        FAIL(DVID_ERR_ARG, "swin window attention: bad sizes (batch %d, %d x %d tokens, %d heads, shift %d)", batch, H, W, nheads, shift);
+    const int rc = dvid_f32_swin_window_attn_launch(qkv, qkv_bias, relbias, out, batch, H, W, C, nheads, shift, reinterpret_cast<hipStream_t>(stream));
+    if (rc != DVID_OK) FAIL(rc, "swin window attention (fp32): C %d with %d heads on %d x %d x %d tokens is not supported", C, nheads, batch, H, W);
+    return DVID_OK;
+}
+
+int dvid_swin_window_attn_f32_ws(const float* qkv, const float* qkv_bias, const float* relbias, float* out, int batch, int H, int W, int C,
+                                 int nheads, int shift, int window, void* stream) {
+    if (window == 7) return dvid_swin_window_attn_f32(qkv, qkv_bias, relbias, out, batch, H, W, C, nheads, shift, stream);
+    g_err[0] = 0;
+    if (window != 12) FAIL(DVID_ERR_UNSUPPORTED, "swin window attention: window size %d (7 and 12 are built)", window);
+    if (!qkv || !qkv_bias || !relbias || !out) FAIL(DVID_ERR_ARG, "swin window attention: null pointer");
+    if (batch <= 0 || H <= 0 || W <= 0 || nheads <= 0 || shift < 0 || shift >= window)
+        FAIL(DVID_ERR_ARG, "swin window attention: bad sizes (batch %d, %d x %d tokens, %d heads, shift %d, window %d)", batch, H, W, nheads, shift, window);
+    const int rc = dvid_f32_swin_window12_attn_launch(qkv, qkv_bias, relbias, out, batch, H, W, C, nheads, shift, reinterpret_cast<hipStream_t>(stream));
+    if (rc != DVID_OK) FAIL(rc, "swin window attention (fp32, window 12): C %d with %d heads on %d x %d x %d tokens is not supported", C, nheads, batch, H, W);
+    return DVID_OK;
+}
+
+int dvid_dynconv_f32(const float* roi, const float* params, const float* g1, const float* b1, const float* g2, const float* b2, float* out,
+                     int rows, void* stream) {
+    g_err[0] = 0;
+    TRY(dvid_f32_dynconv_launch(roi, params, g1, b1, g2, b2, out, rows, nullptr, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_select_topk_features(const float* logits, int n_frames, int mm, int num_classes, int k1, int k2, const float* feats,
+                              int hidden, float* out_k1, float* out_k2, void* stream) {
+    g_err[0] = 0;
+    TRY(dvid_topk_mask_launch(logits, n_frames, mm, num_classes, k1, k2, feats, hidden, out_k1, out_k2,
+                              reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_counter_normal(float* out, int64_t per_image, int n_images, uint64_t key0, void* stream) {
+    g_err[0] = 0;
+    if (!out || per_image < 0 || n_images < 0 || n_images > 65535) FAIL(DVID_ERR_ARG, "dvid_counter_normal: bad arguments");
+    TRY(dvid_counter_normal_launch(out, (long)per_image, n_images, key0, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_noise_to_boxes(const float* x, float* boxes, int n, float snr_scale, float img_w, float img_h, void* stream) {
+    g_err[0] = 0;
+    TRY(dvid_noise_to_boxes_launch(x, boxes, n, snr_scale, img_w, img_h, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_ddim_renew_step(const float* logits, const float* boxes, const float* x_t, const float* noise, const float* fresh,
+                         float* x_next, int n_frames, int mm, int c, float img_w, float img_h, float snr_scale,
+                         float sqrt_recip_ac, float sqrt_recipm1_ac, float sqrt_ac_next, float coef_c, float sigma, float keep_thr,
+                         void* stream) {
+    g_err[0] = 0;
+    TRY(dvid_ddim_renew_launch(logits, boxes, x_t, noise, fresh, x_next, n_frames, mm, c, img_w, img_h, snr_scale, sqrt_recip_ac,
+                               sqrt_recipm1_ac, sqrt_ac_next, coef_c, sigma, keep_thr, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_postproc_topk_nms(const float* logits, const float* boxes, int nsets, int n_frames, int mm, int c, float img_w, float img_h,
+                           float iou_threshold, int use_nms, float* out_boxes, float* out_scores, int* out_labels, int* out_counts,
+                           void* scratch, void* stream) {
+    g_err[0] = 0;
+    if (!scratch) FAIL(DVID_ERR_ARG, "scratch required");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t ncand = (size_t)n_frames * nsets * mm;
+    float* cb = reinterpret_cast<float*>(scratch);
+    float* cs = cb + ncand * 4;
+    int* cl = reinterpret_cast<int*>(cs + ncand);
+    TRY(dvid_topk_candidates_launch(logits, boxes, n_frames, nsets, mm, c, cb, cs, cl, s));
+    TRY(dvid_nms_frames_launch(cb, cs, cl, n_frames, nsets * mm, img_w, img_h, iou_threshold, use_nms, nsets * mm, out_boxes,
+                               out_scores, out_labels, out_counts, s));
+    return DVID_OK;
+}
+
+int dvid_cdist(const float* x, int n, int d, float* dist, void* stream) {
+    g_err[0] = 0;
+    TRY(dvid_cdist_launch(x, n, d, dist, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+int dvid_fps_greedy(const float* dist, int n, int mm, int bs_emul, int* idx, void* stream) {
+    g_err[0] = 0;
+    TRY(dvid_fps_launch(dist, n, mm, bs_emul, idx, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+int dvid_gather_rows(const float* x, const int* idx, float* y, int mm, int d, void* stream) {
+    g_err[0] = 0;
+    TRY(dvid_gather_rows_launch(x, idx, y, mm, d, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_conv2d_nhwc_f16(const void* in, const void* w, const float* bias, const void* residual, void* out, int n, int h, int wd,
+                         int cin, int cout, int kh, int kw, int stride, int pad, int kpad, int relu, int out_f32, int residual_mode,
+                         void* stream) {
+    g_err[0] = 0;
+    ConvW cw;
+    cw.w = reinterpret_cast<half_t*>(const_cast<void*>(w));
+    cw.bias = const_cast<float*>(bias);
+    cw.cin = cin;
+    cw.cout = cout;
+    cw.kh = kh;
+    cw.kw = kw;
+    cw.stride = stride;
+    cw.pad = pad < 0 ? -pad : pad;
+    cw.same_size = pad < 0;          // pad < 0: |pad| before, as many after as keep the output at the input's size (stride 1)
+    cw.kpad = kpad;
+    if (pad < 0 && stride != 1) FAIL(DVID_ERR_ARG, "same-size padding needs stride 1");
+    TRY(conv_run(cw, reinterpret_cast<const half_t*>(in), n, h, wd, out, reinterpret_cast<hipStream_t>(stream),
+                 {.relu = relu, .out_f32 = out_f32, .res = residual, .res_mode = residual_mode}));
+    return DVID_OK;
+}
+
+int dvid_bottleneck64_tail_f16(const void* t1, const void* w2, const float* b2, const void* w3, const float* b3, const void* residual,
+                               const void* w_shortcut, const float* b_shortcut, const void* w1_next, const float* b1_next, int next_channels,
+                               void* out, void* t1_next, int n, int h, int wd, void* stream) {
+    g_err[0] = 0;
+    const int rc = bneck_tail(reinterpret_cast<const half_t*>(t1), reinterpret_cast<const half_t*>(w2), b2, reinterpret_cast<const half_t*>(w3),
+                              b3, reinterpret_cast<const half_t*>(residual), reinterpret_cast<const half_t*>(w_shortcut), b_shortcut,
+                              reinterpret_cast<const half_t*>(w1_next), b1_next, next_channels, reinterpret_cast<half_t*>(out),
+                              reinterpret_cast<half_t*>(t1_next), n, h, wd, reinterpret_cast<hipStream_t>(stream));
+    if (rc != DVID_OK) FAIL(rc, "bottleneck tail: bad argument (n %d, %d x %d, next conv1 with %d channels)", n, h, wd, next_channels);
+    return DVID_OK;
+}
+
+int dvid_bottleneck128_tail_f16(const void* t1, const void* w2, const float* b2, const void* w3, const float* b3, const void* residual,
+                                const void* w1_next, const float* b1_next, void* out, void* t1_next, int n, int h, int wd, void* stream) {
+    g_err[0] = 0;
+    const int rc = bneck128_tail(reinterpret_cast<const half_t*>(t1), reinterpret_cast<const half_t*>(w2), b2, reinterpret_cast<const half_t*>(w3),
+                                 b3, reinterpret_cast<const half_t*>(residual), reinterpret_cast<const half_t*>(w1_next), b1_next,
+                                 reinterpret_cast<half_t*>(out), reinterpret_cast<half_t*>(t1_next), n, h, wd,
+                                 reinterpret_cast<hipStream_t>(stream));
+    if (rc != DVID_OK) FAIL(rc, "bottleneck tail (128): bad argument (n %d, %d x %d)", n, h, wd);
+    return DVID_OK;
+}
+
+int dvid_mha_f16(const void* q, const void* k, const void* v, void* out, void* vt_scratch, int batch, int lq, int lk, int nheads,
+                 int q_ld, int kv_ld, int out_ld, int64_t q_bs, int64_t kv_bs, int64_t out_bs, void* stream) {
+    g_err[0] = 0;
+    TRY(dvid_mha_mfma_launch(reinterpret_cast<const half_t*>(q), reinterpret_cast<const half_t*>(k), reinterpret_cast<const half_t*>(v),
+                             reinterpret_cast<half_t*>(out), reinterpret_cast<half_t*>(vt_scratch), batch, lq, lk, nheads, q_ld, kv_ld,
+                             out_ld, q_bs, kv_bs, out_bs, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_dynconv(const void* roi, const void* params, const float* g1, const float* b1, const float* g2, const float* b2, void* out,
+                 int rows, void* stream) {
+    g_err[0] = 0;
+    TRY(dvid_dynconv_launch(reinterpret_cast<const half_t*>(roi), reinterpret_cast<const half_t*>(params), g1, b1, g2, b2,
+                            reinterpret_cast<half_t*>(out), rows, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_add_layernorm(const float* x, const float* r, const float* g, const float* b, float* y, int rows, int d, int relu,
+                       void* stream) {
+    g_err[0] = 0;
+    TRY(dvid_add_layernorm_launch(x, r, g, b, y, nullptr, rows, d, relu, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_swin_window_attn_f16(const void* qkv, const void* qkv_bias16, const float* relbias, void* out, int batch, int H, int W, int C,
+                              int nheads, int shift, void* stream) {
+    g_err[0] = 0;
+    if (!qkv || !qkv_bias16 || !relbias || !out) FAIL(DVID_ERR_ARG, "swin window attention: null pointer");
+    if (batch <= 0 || H <= 0 || W <= 0 || nheads <= 0 || shift < 0 || shift >= 7)
+        FAIL(DVID_ERR_ARG, "swin window attention: bad sizes (batch %d, %d x %d tokens, %d heads, shift %d)", batch, H, W, nheads, shift);
+    const int rc = dvid_swin_window_attn_launch(reinterpret_cast<const half_t*>(qkv), reinterpret_cast<const half_t*>(qkv_bias16), relbias,
+                                                reinterpret_cast<half_t*>(out), batch, H, W, C, nheads, shift, reinterpret_cast<hipStream_t>(stream));
+    if (rc != DVID_OK) FAIL(rc, "swin window attention: C %d with %d heads on %d x %d x %d tokens is not supported", C, nheads, batch, H, W);
+    return DVID_OK;
+}
+
+int dvid_swin_window_attn_f16_ws(const void* qkv, const void* qkv_bias16, const float* relbias, void* out, int batch, int H, int W, int C,
+                                 int nheads, int shift, int window, void* stream) {
+    if (window == 7) return dvid_swin_window_attn_f16(qkv, qkv_bias16, relbias, out, batch, H, W, C, nheads, shift, stream);
+    g_err[0] = 0;
+    if (window != 12) FAIL(DVID_ERR_UNSUPPORTED, "swin window attention: window size %d (7 and 12 are built)", window);
+    if (!qkv || !qkv_bias16 || !relbias || !out) FAIL(DVID_ERR_ARG, "swin window attention: null pointer");
+    if (batch <= 0 || H <= 0 || W <= 0 || nheads <= 0 || shift < 0 || shift >= window)
+        FAIL(DVID_ERR_ARG, "swin window attention: bad sizes (batch %d, %d x %d tokens, %d heads, shift %d, window %d)", batch, H, W, nheads, shift, window);
+    const int rc = dvid_swin_window12_attn_launch(reinterpret_cast<const half_t*>(qkv), reinterpret_cast<const half_t*>(qkv_bias16), relbias,
+                                                  reinterpret_cast<half_t*>(out), batch, H, W, C, nheads, shift, reinterpret_cast<hipStream_t>(stream));
+    if (rc != DVID_OK) FAIL(rc, "swin window attention (window 12): C %d with %d heads on %d x %d x %d tokens is not supported", C, nheads, batch, H, W);
+    return DVID_OK;
+}
+
+int dvid_patch_merge_ln(const float* x, const float* g, const float* b, void* y16, float* y32, int B, int H, int W, int C, void* stream) {
+    g_err[0] = 0;
+    if (!x || !g || !b || (!y16 && !y32)) FAIL(DVID_ERR_ARG, "patch merge: null pointer (at least one of y16 / y32 is needed)");
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0) FAIL(DVID_ERR_ARG, "patch merge: bad sizes (%d x %d x %d tokens, C %d)", B, H, W, C);
+    const int rc = dvid_patch_merge_ln_launch(x, g, b, reinterpret_cast<half_t*>(y16), B, H, W, C, reinterpret_cast<hipStream_t>(stream), y32);
+    if (rc != DVID_OK) FAIL(rc, "patch merge: C %d is not supported (a multiple of 4, at most 512)", C);
+    return DVID_OK;
+}
+
+int dvid_nhwc_from_nchw(const float* in, void* out_f16, int n, int h, int w, int c, void* stream) {
+    g_err[0] = 0;
+    TRY(dvid_nhwc_from_nchw_launch(in, reinterpret_cast<half_t*>(out_f16), n, h, w, c, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+int dvid_nchw_from_nhwc(const void* in_f16, float* out, int n, int h, int w, int c, void* stream) {
+    g_err[0] = 0;
+    TRY(dvid_nchw_from_nhwc_launch(reinterpret_cast<const half_t*>(in_f16), out, n, h, w, c, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+int dvid_f32_to_f16(const float* x, void* y, int64_t n, void* stream) {
+    g_err[0] = 0;
+    TRY(dvid_f32_to_f16_launch(x, reinterpret_cast<half_t*>(y), (long)n, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_resize_u8_to_f32(const void* src_hwc, int h, int w, void* tmp, float* out_chw, int oh, int ow, int ph, int pw,
+                          const int* xbounds, const int* xk, int xksize, const int* ybounds, const int* yk, int yksize, void* stream) {
+    g_err[0] = 0;
+    if (!src_hwc || !out_chw) FAIL(DVID_ERR_ARG, "null image");
+    const int rc = dvid_resize_u8_launch(reinterpret_cast<const unsigned char*>(src_hwc), h, w, reinterpret_cast<unsigned char*>(tmp),
+                                         out_chw, oh, ow, ph, pw, xbounds, xk, xksize, ybounds, yk, yksize,
+                                         reinterpret_cast<hipStream_t>(stream));
+    if (rc != DVID_OK) FAIL(rc, "resize %dx%d -> %dx%d (padded %dx%d): bad sizes or missing tables / scratch", h, w, oh, ow, ph, pw);
+    return DVID_OK;
+}
+}  // extern "C"

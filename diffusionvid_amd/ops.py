@@ -74,7 +74,7 @@ def conv2d_nhwc(x, w_packed, kpad, bias, cout, kh, kw, stride, pad, relu=False, 
 def pack_conv_weight_f32(w, scale_rows=False):
     """OIHW fp32 (or [out, in]) -> fp32 [cout, kpad], k = (ky*kw+kx)*cin4 + c with cin4 = cin rounded up to 4, kpad to 16 (zeros).
     scale_rows: additionally multiply each row by the power of two that puts its largest magnitude in [0.5, 1) and return
-    (packed, kpad, row_scale) with row_scale = 2^-e for conv2d_nhwc_f32 (what csrc/model.hip: make_conv does for DTYPE float32)."""
+    (packed, kpad, row_scale) with row_scale = 2^-e for conv2d_nhwc_f32 (what csrc/weights.hip: make_conv does for DTYPE float32)."""
     w = w.detach().float().cpu()
     if w.dim() == 2:
         w = w[:, :, None, None]

@@ -11,7 +11,7 @@ Mirrors the behaviour of the reference's loader for the DiffusionVID path:
                                         under detectron2 names (`stem.conv1.weight`, `res2.0.conv1.norm.weight`, ...)
 
 What happens after the merge is this package's own: `DiffusionDet.load_state_dict` drops the repacked engine, and the
-next forward folds FrozenBN, rounds to fp16 and repacks into the MFMA operand layouts (csrc/model.hip,
+next forward folds FrozenBN, rounds to fp16 and repacks into the MFMA operand layouts (csrc/weights.hip,
 dvid_model_finalize).  Caffe2 blob renaming (c2_model_loading.py:12-129) targets torchvision-style module names that
 the DiffusionVID backbone (detectron2 names) never matches; it is not built and asking for it raises.
 """

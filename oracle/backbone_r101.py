@@ -32,7 +32,7 @@ def _frozen_bn(x, sd, name, eps=1e-5):
 
 def _conv_bn(x, sd, name, stride=1, padding=0, relu=False, residual=None):
     if precision.is_fp16():
-        # the runtime's repack (csrc/model.hip make_conv_bn): FrozenBN folded into the weights before the fp16 rounding,
+        # the runtime's repack (csrc/weights.hip make_conv_bn): FrozenBN folded into the weights before the fp16 rounding,
         # fp32 bias; one fp16 store after bias (+ residual) (+ ReLU)
         eps = 1e-5
         sc = sd[name + ".norm.weight"] / torch.sqrt(sd[name + ".norm.running_var"] + eps)

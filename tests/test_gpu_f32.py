@@ -184,7 +184,7 @@ def test_f32_dynconv(dv, split):
     f = F.relu(F.layer_norm(f, (dd,), sd[pfx + ".norm1.weight"].double(), sd[pfx + ".norm1.bias"].double()))
     f = torch.bmm(f, p2.double())
     ref = F.relu(F.layer_norm(f, (d,), sd[pfx + ".norm2.weight"].double(), sd[pfx + ".norm2.bias"].double())).float()
-    packed = torch.cat([p1.transpose(1, 2).reshape(R, -1), p2.transpose(1, 2).reshape(R, -1)], dim=1).contiguous()      # P1T | P2T (model.hip: make_head)
+    packed = torch.cat([p1.transpose(1, 2).reshape(R, -1), p2.transpose(1, 2).reshape(R, -1)], dim=1).contiguous()      # P1T | P2T (weights.hip: make_head)
     dv.set_option("f32_split", split)
     try:
         out = dv.dynconv_f32(roi.cuda(), packed.cuda(), *(sd[pfx + k].cuda() for k in (".norm1.weight", ".norm1.bias", ".norm2.weight", ".norm2.bias")))

@@ -331,7 +331,7 @@ def test_head_kernels_against_full_dimension_reference_fixture(dv):
     params = T32("dc_params")
     p1 = params[:, :d * dd].view(R, d, dd)
     p2 = params[:, d * dd:].view(R, dd, d)
-    packed = torch.cat([p1.transpose(1, 2).reshape(R, -1), p2.transpose(1, 2).reshape(R, -1)], dim=1)   # P1T | P2T (model.hip: make_head)
+    packed = torch.cat([p1.transpose(1, 2).reshape(R, -1), p2.transpose(1, 2).reshape(R, -1)], dim=1)   # P1T | P2T (weights.hip: make_head)
     out = dv.dynconv(roi.cuda().half(), packed.cuda().half(), sd[pfx + ".norm1.weight"].cuda(), sd[pfx + ".norm1.bias"].cuda(),
                      sd[pfx + ".norm2.weight"].cuda(), sd[pfx + ".norm2.bias"].cuda())
     check("reference_fixture[dynconv]", out, T32("dc_mid"), 4e-3, 4e-3)

@@ -134,7 +134,7 @@ def test_frozen_bn_known_answer():
     want = torch.tensor([1.0, -1.25]).view(1, 2, 1, 1).expand(1, 2, 2, 2)
     assert torch.allclose(obb._conv_bn(x, sd, "c"), want, atol=1e-6)
     assert torch.allclose(obb._conv_bn(x, sd, "c", relu=True), want.clamp(min=0), atol=1e-6)
-    with precision.use("fp16"):          # the folded form (what csrc/model.hip: make_conv_bn packs), weights rounded to fp16 (exact here)
+    with precision.use("fp16"):          # the folded form (what csrc/weights.hip: make_conv_bn packs), weights rounded to fp16 (exact here)
         assert torch.allclose(obb._conv_bn(x, sd, "c"), want, atol=2e-3)
     res = torch.full((1, 2, 2, 2), 0.5)
     assert torch.allclose(obb._conv_bn(x, sd, "c", relu=True, residual=res), (want + 0.5).clamp(min=0), atol=1e-6)          # relu(conv3 + shortcut)
