@@ -65,6 +65,9 @@ SIGNATURES = {
     "dvid_ddim_renew_step": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_float] * 9 + [c_void_p]),
     "dvid_postproc_topk_nms": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dvid_postproc_scratch_bytes": (c_int64, [c_int, c_int, c_int]),
+    "dvid_nms_frames_tiled": (c_int, [c_void_p] * 3 + [c_int, c_int, c_float, c_float, c_float, c_int, c_int] + [c_void_p] * 6),
+    "dvid_nms_tiled_scratch_bytes": (c_int64, [c_int, c_int]),
     "dvid_cdist": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "dvid_fps_greedy": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dvid_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

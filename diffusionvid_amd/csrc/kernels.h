@@ -179,6 +179,12 @@ int dvid_topk_candidates_launch(const float* logits, const float* boxes, int n_i
 int dvid_nms_frames_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n, float img_w,
                            float img_h, float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels,
                            int* out_counts, hipStream_t s);
+// the tiled form of the same step (nms_tiled_*_kernel): any 1 <= n <= DVID_NMS_MAX_CANDIDATES; `scratch` holds dvid_nms_tiled_scratch_size bytes
+bool dvid_nms_frames_fits_lds(int n);          // nms_frame_kernel holds n candidates in LDS: THE dispatch rule between the two forms
+size_t dvid_nms_tiled_scratch_size(int n_img, int n);
+int dvid_nms_frames_tiled_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n, float img_w,
+                                 float img_h, float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels,
+                                 int* out_counts, void* scratch, hipStream_t s);
 
 // fps.hip
 int dvid_cdist_launch(const float* x, int n, int d, float* dist, hipStream_t s);

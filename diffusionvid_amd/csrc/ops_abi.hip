@@ -113,19 +113,57 @@ int dvid_ddim_renew_step(const float* logits, const float* boxes, const float* x
     return DVID_OK;
 }
 
+// bytes of the candidate lists (boxes, scores, labels) at the head of dvid_postproc_topk_nms's scratch
+static size_t postproc_cand_bytes(int nsets, int n_frames, int mm) { return (size_t)n_frames * nsets * mm * 6 * 4; }
+
+int64_t dvid_postproc_scratch_bytes(int nsets, int n_frames, int mm) {
+    if (nsets <= 0 || n_frames <= 0 || mm <= 0) return 0;
+    const size_t cand = postproc_cand_bytes(nsets, n_frames, mm);
+    const long n = (long)nsets * mm;
+    if (n > DVID_NMS_MAX_CANDIDATES || dvid_nms_frames_fits_lds((int)n)) return (int64_t)cand;
+    return (int64_t)(cand + dvid_nms_tiled_scratch_size(n_frames, (int)n));
+}
+
+int64_t dvid_nms_tiled_scratch_bytes(int n_frames, int n) { return (int64_t)dvid_nms_tiled_scratch_size(n_frames, n); }
+
 int dvid_postproc_topk_nms(const float* logits, const float* boxes, int nsets, int n_frames, int mm, int c, float img_w, float img_h,
                            float iou_threshold, int use_nms, float* out_boxes, float* out_scores, int* out_labels, int* out_counts,
                            void* scratch, void* stream) {
     g_err[0] = 0;
     if (!scratch) FAIL(DVID_ERR_ARG, "scratch required");
+    if (nsets <= 0 || n_frames < 0 || mm <= 0) FAIL(DVID_ERR_ARG, "postproc: bad sizes (%d sets, %d frames, %d boxes)", nsets, n_frames, mm);
+    const long n = (long)nsets * mm;
+    if (n > DVID_NMS_MAX_CANDIDATES)
+        FAIL(DVID_ERR_UNSUPPORTED,
+             "postproc: %ld candidates per frame (%d sets x %d boxes) exceed the limit of %d: (SAMPLE_STEP - 1) * NUM_PROPOSALS, or NUM_PROPOSALS "
+             "at SAMPLE_STEP 1, must stay within %d",
+             n, nsets, mm, DVID_NMS_MAX_CANDIDATES, DVID_NMS_MAX_CANDIDATES);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t ncand = (size_t)n_frames * nsets * mm;
     float* cb = reinterpret_cast<float*>(scratch);
     float* cs = cb + ncand * 4;
     int* cl = reinterpret_cast<int*>(cs + ncand);
     TRY(dvid_topk_candidates_launch(logits, boxes, n_frames, nsets, mm, c, cb, cs, cl, s));
-    TRY(dvid_nms_frames_launch(cb, cs, cl, n_frames, nsets * mm, img_w, img_h, iou_threshold, use_nms, nsets * mm, out_boxes,
-                               out_scores, out_labels, out_counts, s));
+    if (dvid_nms_frames_fits_lds((int)n))
+        TRY(dvid_nms_frames_launch(cb, cs, cl, n_frames, nsets * mm, img_w, img_h, iou_threshold, use_nms, nsets * mm, out_boxes,
+                                   out_scores, out_labels, out_counts, s));
+    else          // the shapes nms_frame_kernel cannot hold in LDS: the tiled form, its scratch behind the candidate lists
+        TRY(dvid_nms_frames_tiled_launch(cb, cs, cl, n_frames, nsets * mm, img_w, img_h, iou_threshold, use_nms, nsets * mm, out_boxes,
+                                         out_scores, out_labels, out_counts, reinterpret_cast<char*>(scratch) + postproc_cand_bytes(nsets, n_frames, mm), s));
+    return DVID_OK;
+}
+
+int dvid_nms_frames_tiled(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_frames, int n, float img_w,
+                          float img_h, float iou_threshold, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels,
+                          int* out_counts, void* scratch, void* stream) {
+    g_err[0] = 0;
+    if (!cand_boxes || !cand_scores || !cand_labels || !out_boxes || !out_scores || !out_labels || !out_counts || !scratch)
+        FAIL(DVID_ERR_ARG, "tiled NMS: null pointer");
+    if (n_frames < 0 || n < 1 || out_cap < n) FAIL(DVID_ERR_ARG, "tiled NMS: bad sizes (%d frames, %d candidates, out_cap %d)", n_frames, n, out_cap);
+    if (n > DVID_NMS_MAX_CANDIDATES)
+        FAIL(DVID_ERR_UNSUPPORTED, "tiled NMS: %d candidates per frame exceed the limit of %d ((SAMPLE_STEP - 1) * NUM_PROPOSALS)", n, DVID_NMS_MAX_CANDIDATES);
+    TRY(dvid_nms_frames_tiled_launch(cand_boxes, cand_scores, cand_labels, n_frames, n, img_w, img_h, iou_threshold, use_nms, out_cap, out_boxes,
+                                     out_scores, out_labels, out_counts, scratch, reinterpret_cast<hipStream_t>(stream)));
     return DVID_OK;
 }
 

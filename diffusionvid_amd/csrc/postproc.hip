@@ -7,6 +7,10 @@
 //             without +1, `>` threshold, fp32, same operation order as torchvision's kernels),
 //             clip_to_image (bounding_box.py:214-224), compacted outputs + count.
 //
+//   kernels C  nms_tiled_{sort,mask,sweep}: kernel B for the frames whose candidates do not fit its LDS (more than 997), up to
+//             DVID_NMS_MAX_CANDIDATES = 4096: the suppression bit matrix lives in global scratch and is built by many workgroups per
+//             frame.  Same inputs, outputs and bits as kernel B.
+//
 // Integer work (ordering, suppression) is exact given the scores/boxes; no D2H copies.
 #include <stdlib.h>
 
@@ -287,6 +291,205 @@ __global__ __launch_bounds__(1024) void nms_frame_kernel(const float* __restrict
     }
 }
 
+// ---- the tiled form -------------------------------------------------------------------------------------------------------------------
+// Three launches per chunk of frames, all on the caller's stream:
+//   sort   one workgroup per frame: the stable order (score desc, position asc), max_coord, the offset boxes and their areas -> scratch
+//   mask   grid (frame, 64-row tile, 4-word tile): the upper-triangular bit words mask[i][w]; tiles wholly below the diagonal return
+//          at once and their words stay unwritten -- the sweep reads word w of row i only for w >= i / 64
+//   sweep  one workgroup per frame: wave 0 sweeps (lane w owns word w of the removed set: at most 4096 candidates = 64 words) while all
+//          four waves stage the next block of mask rows from global memory into the other half of an LDS double buffer; then the
+//          outputs as kernel B writes them.
+// Every pair is tested, cross-class pairs included: the boxes are unclipped, so with negative coordinates the offset boxes of
+// neighbouring classes can overlap, and torchvision's batched_nms suppresses across classes then.
+//
+// Arithmetic: the operations of nms_frame_kernel as the compiler builds them (-ffp-contract=fast, hipcc's default): there the union
+// ia + area[j] - inter is one fused multiply-add, fma(-ww, hh, ia + area[j]), and nothing else contracts.  Written out here under
+// contract(off), so both kernels give the same bits whatever the optimiser sees around the expression.
+constexpr int NMS_TILE_ROWS = 64;        // mask: rows per workgroup
+constexpr int NMS_TILE_WORDS = 4;        // mask: 64-bit words per workgroup (256 columns)
+constexpr int NMS_SWEEP_ROWS = 32;       // sweep: mask rows per staged block
+constexpr int NMS_SWEEP_THREADS = 256;
+
+__global__ __launch_bounds__(1024) void nms_tiled_sort_kernel(const float* __restrict__ cand_boxes, const float* __restrict__ cand_scores,
+                                                               const int* __restrict__ cand_labels, int n, int npad,
+                                                               float* __restrict__ sbox, float* __restrict__ sarea, int* __restrict__ sorder) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    u64* keys = reinterpret_cast<u64*>(smem);                          // [npad]
+    __shared__ float redf[16];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const float* cb = cand_boxes + (long)f * n * 4;
+    const float* cs = cand_scores + (long)f * n;
+    const int* cl = cand_labels + (long)f * n;
+    float mx = -INFINITY;
+    for (int i = tid; i < npad; i += blockDim.x) {
+        u64 key = ~0ull;
+        if (i < n) {
+            key = ((u64)(~f2u(cs[i])) << 32) | (unsigned)i;
+            const float4v b = *reinterpret_cast<const float4v*>(cb + i * 4);
+            mx = fmaxf(mx, fmaxf(fmaxf(b[0], b[1]), fmaxf(b[2], b[3])));
+        }
+        keys[i] = key;
+    }
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) redf[tid >> 6] = mx;
+    __syncthreads();
+    bitonic_sort_u64(keys, npad);
+    float max_coord = redf[0];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) max_coord = fmaxf(max_coord, redf[w]);
+    const float off_unit = max_coord + 1.0f;
+    for (int r = tid; r < n; r += blockDim.x) {
+        const int i = (int)(unsigned)keys[r];
+        sorder[(long)f * n + r] = i;
+        const float4v b = *reinterpret_cast<const float4v*>(cb + i * 4);
+        const float off = (float)cl[i] * off_unit;
+        const float4v o = {b[0] + off, b[1] + off, b[2] + off, b[3] + off};
+        *reinterpret_cast<float4v*>(sbox + ((long)f * n + r) * 4) = o;
+        sarea[(long)f * n + r] = (o[2] - o[0]) * (o[3] - o[1]);           // from the OFFSET coordinates, as kernel B
+    }
+}
+
+// grid (frames, row tiles, word tiles), 256 threads: thread t computes word (t / 64) of row (t % 64) of its tile, so a wave reads one
+// column box at a time from LDS (a broadcast); the 64 x 4 words go through LDS once more so that a row's 4 words leave as 32 bytes.
+__global__ __launch_bounds__(256) void nms_tiled_mask_kernel(const float* __restrict__ sbox, const float* __restrict__ sarea, int n, int words,
+                                                              float iou_thr, u64* __restrict__ mask) {
+#pragma clang fp contract(off)
+    const int f = blockIdx.x, row0 = blockIdx.y * NMS_TILE_ROWS, word0 = blockIdx.z * NMS_TILE_WORDS, col0 = word0 * 64;
+    if (col0 + NMS_TILE_WORDS * 64 - 1 <= row0) return;                // every column j of the tile is <= every row i: no bit can be set
+    __shared__ float4v cbx[NMS_TILE_WORDS * 64];
+    __shared__ float car[NMS_TILE_WORDS * 64];
+    __shared__ u64 tile[NMS_TILE_ROWS * NMS_TILE_WORDS];
+    const int tid = threadIdx.x;
+    const float* bx = sbox + (long)f * n * 4;
+    const float* area = sarea + (long)f * n;
+    {
+        const int j = col0 + tid;
+        float4v b = {0.f, 0.f, 0.f, 0.f};
+        float a = 0.f;
+        if (j < n) {
+            b = *reinterpret_cast<const float4v*>(bx + (long)j * 4);
+            a = area[j];
+        }
+        cbx[tid] = b;
+        car[tid] = a;
+    }
+    __syncthreads();
+    const int r = tid & 63, wl = tid >> 6, i = row0 + r;
+    u64 bits = 0;
+    if (i < n) {
+        const float4v ib = *reinterpret_cast<const float4v*>(bx + (long)i * 4);
+        const float ia = area[i];
+        const int j0 = col0 + wl * 64;
+        const int jend = min(64, n - j0);
+        for (int jj = 0; jj < jend; ++jj) {
+            if (j0 + jj <= i) continue;
+            const float4v jb = cbx[wl * 64 + jj];
+            const float xx1 = fmaxf(ib[0], jb[0]), yy1 = fmaxf(ib[1], jb[1]);
+            const float xx2 = fminf(ib[2], jb[2]), yy2 = fminf(ib[3], jb[3]);
+            const float ww = fmaxf(0.f, xx2 - xx1), hh = fmaxf(0.f, yy2 - yy1);
+            const float inter = ww * hh;
+            const float ovr = inter / __builtin_fmaf(-ww, hh, ia + car[wl * 64 + jj]);      // inter / (ia + area[j] - inter), see above
+            if (ovr > iou_thr) bits |= 1ull << jj;
+        }
+    }
+    tile[r * NMS_TILE_WORDS + wl] = bits;
+    __syncthreads();
+    const int orow = row0 + (tid >> 2), ow = word0 + (tid & 3);
+    if (orow < n && ow < words) mask[((long)f * n + orow) * words + ow] = tile[tid];
+}
+
+// one workgroup (256 threads) per frame; dynamic LDS: two blocks of NMS_SWEEP_ROWS x words mask words, then keep_slot[n]
+__global__ __launch_bounds__(NMS_SWEEP_THREADS) void nms_tiled_sweep_kernel(
+    const float* __restrict__ cand_boxes, const float* __restrict__ cand_scores, const int* __restrict__ cand_labels,
+    const int* __restrict__ sorder, const u64* __restrict__ mask, int n, int words, float img_w, float img_h, int use_nms, int out_cap,
+    float* __restrict__ out_boxes, float* __restrict__ out_scores, int* __restrict__ out_labels, int* __restrict__ out_counts) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int PER = NMS_SWEEP_ROWS * 64 / NMS_SWEEP_THREADS;       // staged words per thread at the widest matrix (64 words)
+    const int blk = NMS_SWEEP_ROWS * words;
+    u64* stage = reinterpret_cast<u64*>(smem);                         // [2][blk]
+    int* keep_slot = reinterpret_cast<int*>(stage + 2 * blk);          // [n]
+    __shared__ int s_nkeep;
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const float* cb = cand_boxes + (long)f * n * 4;
+    const float* cs = cand_scores + (long)f * n;
+    const int* cl = cand_labels + (long)f * n;
+    const int* order = sorder + (long)f * n;
+    const u64* mrow = mask + (long)f * n * words;
+    if (!use_nms) {
+        for (int i = tid; i < n; i += NMS_SWEEP_THREADS) keep_slot[i] = i;
+        if (tid == 0) s_nkeep = n;
+    } else {
+        u64 regs[PER];
+        // block b of the matrix -> registers; words below the diagonal (never written by the mask kernel) and rows past n read as 0
+        auto fetch = [&](int b) {
+#pragma unroll
+            for (int k = 0; k < PER; ++k) {
+                const int idx = tid + k * NMS_SWEEP_THREADS;
+                const int r = idx / words, w = idx - r * words, i = b * NMS_SWEEP_ROWS + r;
+                regs[k] = (idx < blk && i < n && w >= (i >> 6)) ? mrow[(long)i * words + w] : 0ull;
+            }
+        };
+        auto put = [&](u64* dst) {
+#pragma unroll
+            for (int k = 0; k < PER; ++k) {
+                const int idx = tid + k * NMS_SWEEP_THREADS;
+                if (idx < blk) dst[idx] = regs[k];
+            }
+        };
+        const int nblk = (n + NMS_SWEEP_ROWS - 1) / NMS_SWEEP_ROWS;
+        fetch(0);
+        put(stage);
+        __syncthreads();
+        u64 removed = 0;                                               // wave 0: lane w owns word w of the removed set
+        int nkeep = 0;
+        for (int b = 0; b < nblk; ++b) {
+            const bool more = b + 1 < nblk;
+            if (more) fetch(b + 1);                                    // in flight while wave 0 sweeps block b
+            if (tid < 64) {
+                const u64* cur_blk = stage + (b & 1) * blk;
+                const int i0 = b * NMS_SWEEP_ROWS, rows = min(NMS_SWEEP_ROWS, n - i0);
+                u64 cur = tid < words ? cur_blk[tid] : 0ull;
+                for (int r = 0; r < rows; ++r) {
+                    const u64 nxt = (r + 1 < rows && tid < words) ? cur_blk[(r + 1) * words + tid] : 0ull;      // ahead of the keep decision
+                    const int i = i0 + r;
+                    const unsigned half = (i & 32) ? (unsigned)(removed >> 32) : (unsigned)removed;
+                    const unsigned wrd = __builtin_amdgcn_readlane(half, i >> 6);
+                    if (!((wrd >> (i & 31)) & 1u)) {
+                        if (tid == 0) keep_slot[nkeep] = i;
+                        ++nkeep;
+                        removed |= cur;
+                    }
+                    cur = nxt;
+                }
+            }
+            if (more) put(stage + ((b + 1) & 1) * blk);                // that half was last read while block b - 1 was swept
+            __syncthreads();
+        }
+        if (tid == 0) s_nkeep = nkeep;
+    }
+    __syncthreads();
+    const int nkeep = s_nkeep;
+    if (tid == 0) out_counts[f] = nkeep;
+    for (int s = tid; s < out_cap; s += NMS_SWEEP_THREADS) {
+        float4v b = {0.f, 0.f, 0.f, 0.f};
+        float sc = 0.f;
+        int lb = 0;
+        if (s < nkeep) {
+            const int i = order[keep_slot[s]];
+            b = *reinterpret_cast<const float4v*>(cb + i * 4);
+            b[0] = fminf(fmaxf(b[0], 0.f), img_w - 1.f);
+            b[1] = fminf(fmaxf(b[1], 0.f), img_h - 1.f);
+            b[2] = fminf(fmaxf(b[2], 0.f), img_w - 1.f);
+            b[3] = fminf(fmaxf(b[3], 0.f), img_h - 1.f);
+            sc = cs[i];
+            lb = cl[i];
+        }
+        *reinterpret_cast<float4v*>(out_boxes + ((long)f * out_cap + s) * 4) = b;
+        out_scores[(long)f * out_cap + s] = sc;
+        out_labels[(long)f * out_cap + s] = lb;
+    }
+}
+
 int next_pow2(int x) {
     int p = 1;
     while (p < x) p <<= 1;
@@ -330,15 +533,22 @@ int dvid_topk_candidates_launch(const float* logits, const float* boxes, int n_i
     return DVID_OK;
 }
 
+// LDS of nms_frame_kernel for n candidates: the keys, the boxes and the whole bit matrix
+static size_t nms_frame_lds_bytes(int n) {
+    const int npad = next_pow2(n), words = (n + 63) / 64;
+    return (size_t)npad * 8 + (size_t)n * (16 + 4 + 4) + 64 + (size_t)((n + 1) & ~1) * 4 + (size_t)n * words * 8;
+}
+
+// THE dispatch rule of the two NMS forms: nms_frame_kernel runs every shape it holds in LDS, the tiled form the others
+bool dvid_nms_frames_fits_lds(int n) { return n <= 1024 && nms_frame_lds_bytes(n) <= 160 * 1024; }
+
 int dvid_nms_frames_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n, float img_w,
                            float img_h, float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels,
                            int* out_counts, hipStream_t s) {
     if (n_img == 0) return DVID_OK;
-    if (n > 1024 || out_cap < n) return DVID_ERR_UNSUPPORTED;
+    if (!dvid_nms_frames_fits_lds(n) || out_cap < n) return DVID_ERR_UNSUPPORTED;
     const int npad = next_pow2(n);
-    const int words = (n + 63) / 64;
-    const size_t smem = (size_t)npad * 8 + (size_t)n * (16 + 4 + 4) + 64 + (size_t)((n + 1) & ~1) * 4 + (size_t)n * words * 8;
-    if (smem > 160 * 1024) return DVID_ERR_UNSUPPORTED;
+    const size_t smem = nms_frame_lds_bytes(n);
     static std::atomic<unsigned long long> attr{0};          // one bit per device: the attribute belongs to (function, device)
     if (first_on_device(attr)) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&nms_frame_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -348,5 +558,53 @@ int dvid_nms_frames_launch(const float* cand_boxes, const float* cand_scores, co
     hipLaunchKernelGGL(nms_frame_kernel, dim3(n_img), dim3(1024), smem, s, cand_boxes, cand_scores, cand_labels, n, npad, img_w, img_h,
                        iou, use_nms, out_cap, out_boxes, out_scores, out_labels, out_counts);
     LAUNCH_CHECK();
+    return DVID_OK;
+}
+
+// Frames per chunk of the tiled form: as many as keep the chunk's bit matrices within NMS_TILED_MATRIX_CEILING (2 MiB per frame at
+// 4096 candidates, 0.53 MiB at 2100: a 304-frame group would need 160 MiB at once), at least one.
+static const size_t NMS_TILED_MATRIX_CEILING = (size_t)64 << 20;
+static int nms_tiled_chunk_frames(int n_img, int n) {
+    const size_t per = (size_t)n * ((n + 63) / 64) * 8;
+    const size_t fit = NMS_TILED_MATRIX_CEILING / per;
+    return (int)(fit < 1 ? 1 : fit > (size_t)n_img ? (size_t)n_img : fit);
+}
+
+size_t dvid_nms_tiled_scratch_size(int n_img, int n) {
+    if (n_img <= 0 || n <= 0 || n > DVID_NMS_MAX_CANDIDATES) return 0;
+    const size_t fc = (size_t)nms_tiled_chunk_frames(n_img, n);
+    return 256 + fc * n * (16 + 4 + 4 + (size_t)((n + 63) / 64) * 8);          // 256: the launcher aligns its base
+}
+
+int dvid_nms_frames_tiled_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n, float img_w,
+                                 float img_h, float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels,
+                                 int* out_counts, void* scratch, hipStream_t s) {
+    if (n_img == 0) return DVID_OK;
+    if (n < 1 || n > DVID_NMS_MAX_CANDIDATES || out_cap < n || !scratch) return DVID_ERR_UNSUPPORTED;
+    const int npad = next_pow2(n), words = (n + 63) / 64;
+    const int fc = nms_tiled_chunk_frames(n_img, n);
+    char* base = reinterpret_cast<char*>(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
+    float* sbox = reinterpret_cast<float*>(base);                                  // [fc][n][4]
+    float* sarea = sbox + (size_t)fc * n * 4;                                      // [fc][n]
+    int* sorder = reinterpret_cast<int*>(sarea + (size_t)fc * n);                  // [fc][n]
+    u64* mask = reinterpret_cast<u64*>(sorder + (size_t)fc * n);                   // [fc][n][words]; fc * n * 24 bytes in: 8-byte aligned
+    const size_t sweep_lds = (size_t)2 * NMS_SWEEP_ROWS * words * 8 + (size_t)n * 4;          // <= 48 KiB
+    for (int f0 = 0; f0 < n_img; f0 += fc) {
+        const int nf = n_img - f0 < fc ? n_img - f0 : fc;
+        const float* cb = cand_boxes + (size_t)f0 * n * 4;
+        const float* cs = cand_scores + (size_t)f0 * n;
+        const int* cl = cand_labels + (size_t)f0 * n;
+        hipLaunchKernelGGL(nms_tiled_sort_kernel, dim3(nf), dim3(1024), (size_t)npad * 8, s, cb, cs, cl, n, npad, sbox, sarea, sorder);
+        LAUNCH_CHECK();
+        if (use_nms) {
+            hipLaunchKernelGGL(nms_tiled_mask_kernel, dim3(nf, ceil_div(n, NMS_TILE_ROWS), ceil_div(words, NMS_TILE_WORDS)), dim3(256), 0, s, sbox,
+                               sarea, n, words, iou, mask);
+            LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(nms_tiled_sweep_kernel, dim3(nf), dim3(NMS_SWEEP_THREADS), sweep_lds, s, cb, cs, cl, sorder, mask, n, words, img_w, img_h,
+                           use_nms, out_cap, out_boxes + (size_t)f0 * out_cap * 4, out_scores + (size_t)f0 * out_cap,
+                           out_labels + (size_t)f0 * out_cap, out_counts + f0);
+        LAUNCH_CHECK();
+    }
     return DVID_OK;
 }

@@ -156,6 +156,12 @@ class DiffusionDet(nn.Module):
         if self.local_active:
             self.skip_unobservable = False
         assert self.sampling_timesteps <= timesteps
+        # every step but the last feeds its NUM_PROPOSALS candidates into one NMS per frame (diffusion_det.py:598-627)
+        candidates = max(1, d.SAMPLE_STEP - 1) * d.NUM_PROPOSALS
+        if candidates > ops.NMS_MAX_CANDIDATES:
+            raise NotImplementedError(
+                "SAMPLE_STEP %d with NUM_PROPOSALS %d gives the NMS %d candidates per frame: the limit is %d = max(1, SAMPLE_STEP - 1) * NUM_PROPOSALS"
+                % (d.SAMPLE_STEP, d.NUM_PROPOSALS, candidates, ops.NMS_MAX_CANDIDATES))
         self.ddim_sampling_eta = 1.0
         self.scale = d.SNR_SCALE
         self.box_renewal = True

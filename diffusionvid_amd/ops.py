@@ -347,6 +347,16 @@ def select_topk_features(logits, feats, k1, k2):
     return o1, o2
 
 
+# Candidates per frame the NMS takes (DVID_NMS_MAX_CANDIDATES of include/dvid_hip.h): (SAMPLE_STEP - 1) * NUM_PROPOSALS with the ensemble,
+# NUM_PROPOSALS at SAMPLE_STEP 1.  torchvision's batched_nms keeps the coordinate trick the kernels reproduce only below 5000 boxes.
+NMS_MAX_CANDIDATES = 4096
+
+
+def postproc_scratch_bytes(nsets, n_frames, m):
+    """bytes of scratch dvid_postproc_topk_nms needs for [nsets, n_frames, m, C] logits"""
+    return int(_lib.load().dvid_postproc_scratch_bytes(int(nsets), int(n_frames), int(m)))
+
+
 def postproc_topk_nms(logits, boxes, img_w, img_h, iou=0.5, use_nms=True):
     """logits [S, n, M, C] (or [n, M, C]), boxes [S, n, M, 4] -> (boxes [n,S*M,4], scores, labels int32, counts int32)."""
     if logits.dim() == 3:
@@ -355,9 +365,24 @@ def postproc_topk_nms(logits, boxes, img_w, img_h, iou=0.5, use_nms=True):
     S, n, M, c = logits.shape
     dev = logits.device
     ob, osc, ol, oc = split_detection_buffer(torch.empty((n * S * M * 6 + n,), dtype=torch.float32, device=dev), n, S * M)
-    scratch = torch.empty((n * S * M * 6,), dtype=torch.float32, device=dev)
+    scratch = torch.empty(((postproc_scratch_bytes(S, n, M) + 3) // 4,), dtype=torch.float32, device=dev)
     call("dvid_postproc_topk_nms", ptr(logits), ptr(boxes), S, n, M, c, float(img_w), float(img_h), float(iou), int(use_nms),
          ptr(ob), ptr(osc), ptr(ol), ptr(oc), ptr(scratch), stream_ptr())
+    return ob, osc, ol, oc
+
+
+def nms_frames_tiled(cand_boxes, cand_scores, cand_labels, img_w, img_h, iou=0.5, use_nms=True):
+    """The tiled NMS on its own, at any 1 <= N <= NMS_MAX_CANDIDATES: cand_boxes [n, N, 4] (unclipped xyxy), cand_scores [n, N], cand_labels
+    [n, N] int32 -> (boxes [n, N, 4], scores, labels int32, counts int32) as postproc_topk_nms returns them."""
+    cand_boxes, cand_scores = _cuda(cand_boxes, torch.float32), _cuda(cand_scores, torch.float32)
+    cand_labels = _cuda(cand_labels, torch.int32)
+    n, N = cand_scores.shape
+    assert cand_boxes.shape == (n, N, 4) and cand_labels.shape == (n, N)
+    dev = cand_boxes.device
+    ob, osc, ol, oc = split_detection_buffer(torch.empty((n * N * 6 + n,), dtype=torch.float32, device=dev), n, N)
+    scratch = torch.empty((max(1, (int(_lib.load().dvid_nms_tiled_scratch_bytes(n, N)) + 3) // 4),), dtype=torch.float32, device=dev)
+    call("dvid_nms_frames_tiled", ptr(cand_boxes), ptr(cand_scores), ptr(cand_labels), n, N, float(img_w), float(img_h), float(iou),
+         int(use_nms), N, ptr(ob), ptr(osc), ptr(ol), ptr(oc), ptr(scratch), stream_ptr())
     return ob, osc, ol, oc
 
 

@@ -202,10 +202,27 @@ int dvid_ddim_renew_step(const float* logits, const float* boxes, const float* x
                          float sqrt_recip_ac, float sqrt_recipm1_ac, float sqrt_ac_next, float coef_c, float sigma, float keep_thr,
                          void* stream);
 /* logits [nsets, n_frames, m, c], boxes [nsets, n_frames, m, 4]; outputs [n_frames, nsets*m, ...] sorted by
- * descending score, first counts[f] entries valid.  scratch: >= n_frames*nsets*m*24 bytes. */
+ * descending score, first counts[f] entries valid.  scratch: >= dvid_postproc_scratch_bytes(nsets, n_frames, m) bytes, 16-byte aligned.
+ * nsets * m candidates per frame, at most DVID_NMS_MAX_CANDIDATES (DVID_ERR_UNSUPPORTED beyond: torchvision's batched_nms itself
+ * leaves the coordinate trick this step reproduces for a per-class NMS from 5000 boxes on).  Frames whose candidates fit one
+ * workgroup's LDS (up to 997) run one kernel; the others a tiled form whose bit matrix lives in the scratch,
+ * in chunks of frames of at most 64 MiB of matrix, every launch on `stream`. */
+#define DVID_NMS_MAX_CANDIDATES 4096
 int dvid_postproc_topk_nms(const float* logits, const float* boxes, int nsets, int n_frames, int m, int c, float img_w,
                            float img_h, float iou_threshold, int use_nms, float* out_boxes, float* out_scores,
                            int* out_labels, int* out_counts, void* scratch, void* stream);
+/* Bytes of scratch dvid_postproc_topk_nms needs for that shape: n_frames*nsets*m*24 where the single-kernel NMS runs, more where the
+ * tiled form does (0 for a shape with no work). */
+int64_t dvid_postproc_scratch_bytes(int nsets, int n_frames, int m);
+/* The tiled NMS on its own, at any 1 <= n <= DVID_NMS_MAX_CANDIDATES: cand_boxes [n_frames, n, 4] (unclipped xyxy), cand_scores
+ * [n_frames, n], cand_labels [n_frames, n] (int32, >= 1) -> per frame the survivors of the class-aware NMS in (score desc, position
+ * asc) order, clipped to the image: out_boxes [n_frames, out_cap, 4], out_scores, out_labels [n_frames, out_cap] (zero behind
+ * out_counts[f]), out_cap >= n.  The same bits as dvid_postproc_topk_nms's NMS wherever both run.
+ * scratch: >= dvid_nms_tiled_scratch_bytes(n_frames, n) bytes. */
+int dvid_nms_frames_tiled(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_frames, int n, float img_w,
+                          float img_h, float iou_threshold, int use_nms, int out_cap, float* out_boxes, float* out_scores,
+                          int* out_labels, int* out_counts, void* scratch, void* stream);
+int64_t dvid_nms_tiled_scratch_bytes(int n_frames, int n);
 int dvid_cdist(const float* x, int n, int d, float* dist, void* stream);
 /* bs_emul: block size of the reference CUDA launch to emulate for tie-breaking (0 = fps.cu's own rule) */
 int dvid_fps_greedy(const float* dist, int n, int m, int bs_emul, int* idx, void* stream);
