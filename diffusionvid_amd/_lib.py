@@ -66,6 +66,7 @@ SIGNATURES = {
     "dvid_postproc_topk_nms": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dvid_postproc_scratch_bytes": (c_int64, [c_int, c_int, c_int]),
+    "dvid_topk_candidates_stream": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dvid_nms_frames_tiled": (c_int, [c_void_p] * 3 + [c_int, c_int, c_float, c_float, c_float, c_int, c_int] + [c_void_p] * 6),
     "dvid_nms_tiled_scratch_bytes": (c_int64, [c_int, c_int]),
     "dvid_cdist": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),

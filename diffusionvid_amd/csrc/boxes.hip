@@ -87,21 +87,40 @@ __global__ void apply_deltas_kernel(const float* __restrict__ deltas, int delta_
     if (bad_flag && !(o[2] >= o[0] && o[3] >= o[1])) atomicOr(bad_flag, 1);
 }
 
+// The class maximum of a box row for wide vocabularies (c > ROWMAX_SERIAL_CLASSES; up to DVID_MAX_CLASSES = 1280): one wave per row,
+// lanes stride the classes (coalesced 256-byte reads), then a cross-lane fmaxf.  The kernels below run it as their WIDE form with 16
+// waves per frame; up to 64 classes one thread walks a row, as before.  A maximum is exact and independent of the order, so both forms
+// give the same bits (a NaN logit is skipped by fmaxf in either; a row of NaNs only gives NaN in both).
+constexpr int ROWMAX_SERIAL_CLASSES = 64;
+constexpr int ROWMAX_WIDE_THREADS = 1024;
+
 // One workgroup per frame.  rank by (max logit desc, index asc); emit rows of the top-k1 / top-k2
 // sets in ascending box-index order ("mask order", box_head.py:315-317).
-__global__ __launch_bounds__(256) void topk_mask_kernel(const float* __restrict__ logits, int m, int c, int k1, int k2,
-                                                         const float* __restrict__ feats, int d, float* __restrict__ out1,
-                                                         float* __restrict__ out2) {
+template <bool WIDE>
+__global__ __launch_bounds__(WIDE ? ROWMAX_WIDE_THREADS : 256) void topk_mask_kernel(const float* __restrict__ logits, int m, int c, int k1, int k2,
+                                                                                      const float* __restrict__ feats, int d,
+                                                                                      float* __restrict__ out1, float* __restrict__ out2) {
     extern __shared__ float sm[];
     float* val = sm;                                   // [m]
     int* sel1 = reinterpret_cast<int*>(sm + m);        // [m] output slot or -1
     int* sel2 = sel1 + m;
     const int f = blockIdx.x, tid = threadIdx.x;
-    for (int i = tid; i < m; i += blockDim.x) {
-        const float* lp = logits + ((long)f * m + i) * c;
-        float mx = lp[0];
-        for (int j = 1; j < c; ++j) mx = fmaxf(mx, lp[j]);
-        val[i] = mx;
+    if (WIDE) {
+        const int lane = tid & 63, nwave = blockDim.x >> 6;
+        for (int i = tid >> 6; i < m; i += nwave) {
+            const float* lp = logits + ((long)f * m + i) * c;
+            float mx = lp[lane];                       // c > 64: every lane has a first element
+            for (int j = lane + 64; j < c; j += 64) mx = fmaxf(mx, lp[j]);
+            mx = wave_max(mx);
+            if (lane == 0) val[i] = mx;
+        }
+    } else {
+        for (int i = tid; i < m; i += blockDim.x) {
+            const float* lp = logits + ((long)f * m + i) * c;
+            float mx = lp[0];
+            for (int j = 1; j < c; ++j) mx = fmaxf(mx, lp[j]);
+            val[i] = mx;
+        }
     }
     __syncthreads();
     for (int i = tid; i < m; i += blockDim.x) {
@@ -142,19 +161,32 @@ __global__ __launch_bounds__(256) void topk_mask_kernel(const float* __restrict_
 // :666-672 (x_start from the predicted boxes; NB divided by the frame size for every frame) and
 // :649-653 (predict_noise_from_start).  Kept boxes are compacted in index order; the j-th kept box
 // consumes noise row j; the tail is replenished with fresh N(0,1) rows.
-__global__ __launch_bounds__(256) void ddim_renew_kernel(const float* __restrict__ logits, const float* __restrict__ boxes,
-                                                          const float* __restrict__ xt, const float* __restrict__ noise,
-                                                          const float* __restrict__ fresh, float* __restrict__ out, int m, int c,
-                                                          float w, float h, float scale, float sra, float srm1, float sqrt_an,
-                                                          float cc, float sigma, float thr) {
+// WIDE (c > ROWMAX_SERIAL_CLASSES): the largest score of a row by one wave, see above -- still the sigmoid of every element first, then the maximum.
+template <bool WIDE>
+__global__ __launch_bounds__(WIDE ? ROWMAX_WIDE_THREADS : 256) void ddim_renew_kernel(const float* __restrict__ logits, const float* __restrict__ boxes,
+                                                                                       const float* __restrict__ xt, const float* __restrict__ noise,
+                                                                                       const float* __restrict__ fresh, float* __restrict__ out, int m,
+                                                                                       int c, float w, float h, float scale, float sra, float srm1,
+                                                                                       float sqrt_an, float cc, float sigma, float thr) {
     extern __shared__ int pos[];   // [m] compacted slot or -1
     __shared__ int s_remain;
     const int f = blockIdx.x, tid = threadIdx.x;
-    for (int i = tid; i < m; i += blockDim.x) {
-        const float* lp = logits + ((long)f * m + i) * c;
-        float mx = -INFINITY;
-        for (int j = 0; j < c; ++j) mx = fmaxf(mx, 1.f / (1.f + expf(-lp[j])));
-        pos[i] = mx > thr ? 1 : 0;
+    if (WIDE) {
+        const int lane = tid & 63, nwave = blockDim.x >> 6;
+        for (int i = tid >> 6; i < m; i += nwave) {
+            const float* lp = logits + ((long)f * m + i) * c;
+            float mx = -INFINITY;
+            for (int j = lane; j < c; j += 64) mx = fmaxf(mx, 1.f / (1.f + expf(-lp[j])));
+            mx = wave_max(mx);
+            if (lane == 0) pos[i] = mx > thr ? 1 : 0;
+        }
+    } else {
+        for (int i = tid; i < m; i += blockDim.x) {
+            const float* lp = logits + ((long)f * m + i) * c;
+            float mx = -INFINITY;
+            for (int j = 0; j < c; ++j) mx = fmaxf(mx, 1.f / (1.f + expf(-lp[j])));
+            pos[i] = mx > thr ? 1 : 0;
+        }
     }
     __syncthreads();
     if (tid == 0) {
@@ -225,7 +257,10 @@ int dvid_topk_mask_launch(const float* logits, int n_img, int m, int c, int k1, 
     if (n_img == 0) return DVID_OK;
     if (d % 4 || k2 > k1 || k1 > m) return DVID_ERR_ARG;
     const size_t smem = (size_t)m * 12;
-    hipLaunchKernelGGL(topk_mask_kernel, dim3(n_img), dim3(256), smem, s, logits, m, c, k1, k2, feats, d, out1, out2);
+    if (c > ROWMAX_SERIAL_CLASSES)
+        hipLaunchKernelGGL(topk_mask_kernel<true>, dim3(n_img), dim3(ROWMAX_WIDE_THREADS), smem, s, logits, m, c, k1, k2, feats, d, out1, out2);
+    else
+        hipLaunchKernelGGL(topk_mask_kernel<false>, dim3(n_img), dim3(256), smem, s, logits, m, c, k1, k2, feats, d, out1, out2);
     LAUNCH_CHECK();
     return DVID_OK;
 }
@@ -234,8 +269,12 @@ int dvid_ddim_renew_launch(const float* logits, const float* boxes, const float*
                            float* out, int n_img, int m, int c, float w, float h, float scale, float sra, float srm1, float sqrt_an,
                            float cc, float sigma, float thr, hipStream_t s) {
     if (n_img == 0) return DVID_OK;
-    hipLaunchKernelGGL(ddim_renew_kernel, dim3(n_img), dim3(256), (size_t)m * 4, s, logits, boxes, xt, noise, fresh, out, m, c, w, h,
-                       scale, sra, srm1, sqrt_an, cc, sigma, thr);
+    if (c > ROWMAX_SERIAL_CLASSES)
+        hipLaunchKernelGGL(ddim_renew_kernel<true>, dim3(n_img), dim3(ROWMAX_WIDE_THREADS), (size_t)m * 4, s, logits, boxes, xt, noise, fresh, out,
+                           m, c, w, h, scale, sra, srm1, sqrt_an, cc, sigma, thr);
+    else
+        hipLaunchKernelGGL(ddim_renew_kernel<false>, dim3(n_img), dim3(256), (size_t)m * 4, s, logits, boxes, xt, noise, fresh, out, m, c, w, h,
+                           scale, sra, srm1, sqrt_an, cc, sigma, thr);
     LAUNCH_CHECK();
     return DVID_OK;
 }

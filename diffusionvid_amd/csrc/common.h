@@ -19,6 +19,7 @@ typedef float float16v __attribute__((ext_vector_type(16)));
 #define DVID_ERR_UNSUPPORTED 3
 #define DVID_ERR_STATE 4
 #define DVID_NMS_MAX_CANDIDATES 4096          // as in include/dvid_hip.h
+#define DVID_MAX_CLASSES 1280                  // as in include/dvid_hip.h
 
 #define WAVE 64
 

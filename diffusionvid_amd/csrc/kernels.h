@@ -176,6 +176,10 @@ int dvid_ddim_renew_launch(const float* logits, const float* boxes, const float*
 // postproc.hip
 int dvid_topk_candidates_launch(const float* logits, const float* boxes, int n_img, int nsets, int m, int c, float* cand_boxes,
                                 float* cand_scores, int* cand_labels, hipStream_t s);
+// the streaming form of the same selection (topk_stream_kernel), forced at any 1 <= m <= DVID_NMS_MAX_CANDIDATES, 1 <= c <= DVID_MAX_CLASSES;
+// dvid_topk_candidates_launch takes it for the shapes its two LDS forms do not hold
+int dvid_topk_stream_launch(const float* logits, const float* boxes, int n_img, int nsets, int m, int c, float* cand_boxes,
+                            float* cand_scores, int* cand_labels, hipStream_t s);
 int dvid_nms_frames_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n, float img_w,
                            float img_h, float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels,
                            int* out_counts, hipStream_t s);

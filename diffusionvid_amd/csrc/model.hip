@@ -117,8 +117,9 @@ int dvid_model_create(const dvid_config* cfg, dvid_model** out) {
         cfg->sampling_ratio != 2)
         FAIL(DVID_ERR_UNSUPPORTED,
              "kernels are specialised for HIDDEN_DIM 256, NHEADS 8, DIM_DYNAMIC 64, POOLER_RESOLUTION 7, SAMPLING_RATIO 2");
-    if (cfg->dim_feedforward % 64 || cfg->num_classes < 1 || cfg->num_classes > 64)
-        FAIL(DVID_ERR_UNSUPPORTED, "DIM_FEEDFORWARD must be a multiple of 64 and 1 <= NUM_CLASSES <= 64");
+    if (cfg->dim_feedforward % 64) FAIL(DVID_ERR_UNSUPPORTED, "DIM_FEEDFORWARD must be a multiple of 64");
+    if (cfg->num_classes < 1 || cfg->num_classes > DVID_MAX_CLASSES)
+        FAIL(DVID_ERR_UNSUPPORTED, "NUM_CLASSES %d: 1 <= NUM_CLASSES <= DVID_MAX_CLASSES = %d", cfg->num_classes, DVID_MAX_CLASSES);
     int dev_count = 0;
     if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count == 0) FAIL(DVID_ERR_HIP, "no HIP device available");
     dvid_model* m = new dvid_model();

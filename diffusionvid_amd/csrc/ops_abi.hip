@@ -153,6 +153,19 @@ int dvid_postproc_topk_nms(const float* logits, const float* boxes, int nsets, i
     return DVID_OK;
 }
 
+int dvid_topk_candidates_stream(const float* logits, const float* boxes, int nsets, int n_frames, int mm, int c, float* cand_boxes,
+                                float* cand_scores, int* cand_labels, void* stream) {
+    g_err[0] = 0;
+    if (!logits || !boxes || !cand_boxes || !cand_scores || !cand_labels) FAIL(DVID_ERR_ARG, "streaming top-k: null pointer");
+    if (nsets <= 0 || n_frames < 0 || mm <= 0 || c <= 0)
+        FAIL(DVID_ERR_ARG, "streaming top-k: bad sizes (%d sets, %d frames, %d boxes, %d classes)", nsets, n_frames, mm, c);
+    if (mm > DVID_NMS_MAX_CANDIDATES || c > DVID_MAX_CLASSES)
+        FAIL(DVID_ERR_UNSUPPORTED, "streaming top-k: %d boxes x %d classes exceed the limits of %d boxes (DVID_NMS_MAX_CANDIDATES) and %d classes (DVID_MAX_CLASSES)",
+             mm, c, DVID_NMS_MAX_CANDIDATES, DVID_MAX_CLASSES);
+    TRY(dvid_topk_stream_launch(logits, boxes, n_frames, nsets, mm, c, cand_boxes, cand_scores, cand_labels, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
 int dvid_nms_frames_tiled(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_frames, int n, float img_w,
                           float img_h, float iou_threshold, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels,
                           int* out_counts, void* scratch, void* stream) {

@@ -180,6 +180,117 @@ __global__ __launch_bounds__(1024) void topk_select_kernel(const float* __restri
     }
 }
 
+// The same selection for the shapes whose M*C keys no LDS holds (wide class vocabularies: 300 x 1203 = 1.4 MB of keys per frame): the
+// keys are never stored.  Every pass recomputes ~bits(sigmoid(x)) from the logits in global memory -- the expression of the two kernels
+// above, so the same bits -- with lanes striding the flat index (coalesced; after the first pass the frame's logits come from L2).  LDS
+// holds sel[mpad], the histogram and the scan scratch: 8.2 KiB + 8 mpad bytes.
+//   passes 1-3  radix histograms over all keys (11 / 11 / 10 bits) -> thr, the M-th smallest key, and need_eq, how many keys equal to it
+//               belong to the top M
+//   pass 4      wave w walks its own contiguous range [w per_w, (w + 1) per_w): keys below thr go to sel in any order (sorted afterwards),
+//               keys equal to thr are counted per wave
+//   pass 5      the first need_eq keys equal to thr in flat-index order: rank = equal keys of the waves before + of this wave's earlier
+//               iterations + of the lower lanes of this iteration (a ballot); a wave stops once its rank reaches need_eq, so without ties
+//               beyond the M-th key only the waves up to the last taken key read anything
+// Exactly the set and order of the full sort: (score desc, flat index asc).  One workgroup of 1024 threads per (frame, set).
+__global__ __launch_bounds__(1024) void topk_stream_kernel(const float* __restrict__ logits, const float* __restrict__ boxes, int n_img,
+                                                            int m, int c, int mpad, float* __restrict__ cand_boxes,
+                                                            float* __restrict__ cand_scores, int* __restrict__ cand_labels) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    u64* sel = reinterpret_cast<u64*>(smem);                              // [mpad] selected keys
+    __shared__ int hist[2048];
+    __shared__ int s_bin, s_need, s_cnt, s_wave[16];
+    const int total = m * c;
+    const int f = blockIdx.x, set = blockIdx.y, nsets = gridDim.y, tid = threadIdx.x;
+    const long base = ((long)set * n_img + f) * m;
+    const float* lg = logits + base * c;
+    auto key_of = [&](int i) { return ~f2u(1.f / (1.f + expf(-lg[i]))); };          // torch.sigmoid; smaller key = larger score (scores > 0)
+    for (int i = tid; i < mpad; i += 1024) sel[i] = ~0ull;
+    if (tid == 0) {
+        s_need = m;
+        s_cnt = 0;
+    }
+    unsigned prefix = 0;
+    int decided = 0;                                                     // leading bits of the threshold known so far
+    const int bits_of[3] = {11, 11, 10};
+    for (int pass = 0; pass < 3; ++pass) {
+        const int bits = bits_of[pass], shift = 32 - decided - bits;
+        for (int i = tid; i < 2048; i += 1024) hist[i] = 0;
+        __syncthreads();
+        for (int i = tid; i < total; i += 1024) {
+            const unsigned k = key_of(i);
+            if (decided == 0 || (k >> (32 - decided)) == prefix) atomicAdd(&hist[(k >> shift) & ((1u << bits) - 1)], 1);
+        }
+        __syncthreads();
+        if (tid < 64) {                                                  // first wave: the bin that holds the s_need-th key
+            const int nb = 1 << bits, per = nb / 64;
+            int sum = 0;
+            for (int b = 0; b < per; ++b) sum += hist[tid * per + b];
+            int inc = sum;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int v = __shfl_up(inc, o, 64);
+                if (tid >= o) inc += v;
+            }
+            const int need = s_need, exc = inc - sum;
+            if (exc < need && need <= inc) {
+                int run = exc;
+                for (int b = 0; b < per; ++b) {
+                    const int h = hist[tid * per + b];
+                    if (need <= run + h) {
+                        s_bin = tid * per + b;
+                        s_need = need - run;
+                        break;
+                    }
+                    run += h;
+                }
+            }
+        }
+        __syncthreads();
+        prefix = (prefix << bits) | (unsigned)s_bin;
+        decided += bits;
+        __syncthreads();
+    }
+    const unsigned thr = prefix;                                         // the m-th smallest key; s_need of the keys equal to it belong to the top-m
+    const int need_eq = s_need;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int per_w = (total + 15) / 16, i0 = wave * per_w, i1 = min(total, i0 + per_w);          // this wave's range (empty when i0 >= total)
+    // slots are bounded by m on every write: m - need_eq keys are below thr and need_eq equal ones are taken as long as all passes see
+    // the same logits, and a caller that overwrites them meanwhile must not make this kernel write outside sel
+    int eq = 0;                                                          // wave-uniform: keys equal to thr in this wave's range
+    for (int i = i0 + lane; i - lane < i1; i += 64) {
+        const unsigned k = i < i1 ? key_of(i) : ~0u;
+        if (i < i1 && k < thr) {
+            const int slot = atomicAdd(&s_cnt, 1);
+            if (slot < m) sel[slot] = ((u64)k << 32) | (unsigned)i;
+        }
+        eq += __popcll(__ballot(i < i1 && k == thr));
+    }
+    if (lane == 0) s_wave[wave] = eq;
+    __syncthreads();
+    const int below = s_cnt;                                             // final: every k < thr has been counted before the barrier above
+    int rank = 0;                                                        // wave-uniform: equal keys in front of this wave's next iteration
+    for (int w = 0; w < wave; ++w) rank += s_wave[w];
+    if (eq > 0) {
+        for (int i = i0 + lane; i - lane < i1 && rank < need_eq; i += 64) {
+            const bool hit = i < i1 && key_of(i) == thr;
+            const unsigned long long mask = __ballot(hit);
+            const int r = rank + __popcll(mask & ((1ull << lane) - 1ull));
+            if (hit && r < need_eq && below + r < m) sel[below + r] = ((u64)thr << 32) | (unsigned)i;
+            rank += __popcll(mask);
+        }
+    }
+    __syncthreads();
+    bitonic_sort_u64(sel, mpad);
+    const long obase = ((long)f * nsets + set) * m;
+    for (int r = tid; r < m; r += 1024) {
+        const u64 key = sel[r];
+        const unsigned idx = min((unsigned)key, (unsigned)(total - 1));          // (an unfilled slot, see above, reads inside the frame)
+        cand_scores[obase + r] = __uint_as_float(~(unsigned)(key >> 32));
+        cand_labels[obase + r] = (int)(idx % c) + 1;
+        *reinterpret_cast<float4v*>(cand_boxes + (obase + r) * 4) = *reinterpret_cast<const float4v*>(boxes + (base + idx / c) * 4);
+    }
+}
+
 // one workgroup (1024 threads) per frame; n = nsets * m candidates (<= 1024)
 __global__ __launch_bounds__(1024) void nms_frame_kernel(const float* __restrict__ cand_boxes, const float* __restrict__ cand_scores,
                                                           const int* __restrict__ cand_labels, int n, int npad, float img_w,
@@ -498,6 +609,22 @@ int next_pow2(int x) {
 
 }  // namespace
 
+// topk_stream_kernel at any shape it takes: 1 <= m <= DVID_NMS_MAX_CANDIDATES (sel[mpad] is at most 32 KiB), 1 <= c <= DVID_MAX_CLASSES
+// (m * c stays far inside 32 bits)
+int dvid_topk_stream_launch(const float* logits, const float* boxes, int n_img, int nsets, int m, int c, float* cand_boxes,
+                            float* cand_scores, int* cand_labels, hipStream_t s) {
+    if (m < 1 || m > DVID_NMS_MAX_CANDIDATES || c < 1 || c > DVID_MAX_CLASSES || nsets < 1 || nsets > 65535) return DVID_ERR_UNSUPPORTED;
+    if (n_img == 0) return DVID_OK;
+    const int mpad = next_pow2(m);
+    hipLaunchKernelGGL(topk_stream_kernel, dim3(n_img, nsets), dim3(1024), (size_t)mpad * 8, s, logits, boxes, n_img, m, c, mpad, cand_boxes,
+                       cand_scores, cand_labels);
+    LAUNCH_CHECK();
+    return DVID_OK;
+}
+
+// THE dispatch rule of the three selection forms: topk_select_kernel runs every shape whose keys fit its LDS (mpad * 8 + m * c * 4 + 8 KiB
+// <= 150 KiB: 300 x 30, 300 x 80), topk_candidates_kernel (the full sort) the others up to 16384 padded keys, topk_stream_kernel the rest
+// (500 x 80, 1000 x 80, anything x 1203).  All three give the same bits.
 int dvid_topk_candidates_launch(const float* logits, const float* boxes, int n_img, int nsets, int m, int c, float* cand_boxes,
                                 float* cand_scores, int* cand_labels, hipStream_t s) {
     if (n_img == 0) return DVID_OK;
@@ -520,7 +647,7 @@ int dvid_topk_candidates_launch(const float* logits, const float* boxes, int n_i
     }
     const int npad = next_pow2(m * c);
     const size_t smem = (size_t)npad * 8;
-    if (smem > 160 * 1024) return DVID_ERR_UNSUPPORTED;
+    if (smem > 160 * 1024) return dvid_topk_stream_launch(logits, boxes, n_img, nsets, m, c, cand_boxes, cand_scores, cand_labels, s);
     static std::atomic<unsigned long long> attr{0};          // one bit per device: the attribute belongs to (function, device)
     if (first_on_device(attr)) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&topk_candidates_kernel),

@@ -162,6 +162,8 @@ class DiffusionDet(nn.Module):
             raise NotImplementedError(
                 "SAMPLE_STEP %d with NUM_PROPOSALS %d gives the NMS %d candidates per frame: the limit is %d = max(1, SAMPLE_STEP - 1) * NUM_PROPOSALS"
                 % (d.SAMPLE_STEP, d.NUM_PROPOSALS, candidates, ops.NMS_MAX_CANDIDATES))
+        if not 1 <= d.NUM_CLASSES <= ops.MAX_CLASSES:
+            raise NotImplementedError("NUM_CLASSES %d: the limit is 1 <= NUM_CLASSES <= %d (DVID_MAX_CLASSES)" % (d.NUM_CLASSES, ops.MAX_CLASSES))
         self.ddim_sampling_eta = 1.0
         self.scale = d.SNR_SCALE
         self.box_renewal = True

@@ -352,6 +352,11 @@ def select_topk_features(logits, feats, k1, k2):
 NMS_MAX_CANDIDATES = 4096
 
 
+# Largest MODEL.DiffusionDet.NUM_CLASSES a model is built with (DVID_MAX_CLASSES of include/dvid_hip.h): LVIS's 1203 rounded up to whole
+# 64-row tiles of class_logits.
+MAX_CLASSES = 1280
+
+
 def postproc_scratch_bytes(nsets, n_frames, m):
     """bytes of scratch dvid_postproc_topk_nms needs for [nsets, n_frames, m, C] logits"""
     return int(_lib.load().dvid_postproc_scratch_bytes(int(nsets), int(n_frames), int(m)))
@@ -369,6 +374,23 @@ def postproc_topk_nms(logits, boxes, img_w, img_h, iou=0.5, use_nms=True):
     call("dvid_postproc_topk_nms", ptr(logits), ptr(boxes), S, n, M, c, float(img_w), float(img_h), float(iou), int(use_nms),
          ptr(ob), ptr(osc), ptr(ol), ptr(oc), ptr(scratch), stream_ptr())
     return ob, osc, ol, oc
+
+
+def topk_candidates_stream(logits, boxes):
+    """The candidate selection on its own in its streaming form (topk_stream_kernel), forced at any M <= NMS_MAX_CANDIDATES and
+    C <= MAX_CLASSES: logits [S, n, M, C] (or [n, M, C]), boxes [S, n, M, 4] -> (cand_boxes [n, S*M, 4], cand_scores [n, S*M],
+    cand_labels int32 [n, S*M]): per (frame, set) the M largest sigmoid scores in (score desc, flat index asc) order."""
+    if logits.dim() == 3:
+        logits, boxes = logits[None], boxes[None]
+    logits, boxes = _cuda(logits, torch.float32), _cuda(boxes, torch.float32)
+    S, n, M, c = logits.shape
+    assert boxes.shape == (S, n, M, 4)
+    dev = logits.device
+    cb = torch.empty((n, S * M, 4), dtype=torch.float32, device=dev)
+    cs = torch.empty((n, S * M), dtype=torch.float32, device=dev)
+    cl = torch.empty((n, S * M), dtype=torch.int32, device=dev)
+    call("dvid_topk_candidates_stream", ptr(logits), ptr(boxes), S, n, M, c, ptr(cb), ptr(cs), ptr(cl), stream_ptr())
+    return cb, cs, cl
 
 
 def nms_frames_tiled(cand_boxes, cand_scores, cand_labels, img_w, img_h, iou=0.5, use_nms=True):

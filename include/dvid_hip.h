@@ -46,6 +46,12 @@ extern "C" {
 #define DVID_ERR_UNSUPPORTED 3
 #define DVID_ERR_STATE 4
 
+/* The largest MODEL.DiffusionDet.NUM_CLASSES a model is created with (DVID_ERR_UNSUPPORTED beyond): LVIS's 1203 rounded up to whole
+ * 64-row tiles of class_logits; COCO's 80 and Objects365's 365 lie inside.  Up to 64 classes the head's tail runs as one fused kernel
+ * (csrc/headtail.hip); above it class_logits and the layers in front of it run layer by layer, in both precisions.  The logits of one
+ * head output take n_frames * boxes_per_frame * num_classes * 4 bytes: 0.44 GB for 304 frames of 300 boxes at 1203 classes. */
+#define DVID_MAX_CLASSES 1280
+
 typedef struct dvid_model dvid_model;
 
 typedef struct dvid_config {
@@ -53,7 +59,7 @@ typedef struct dvid_config {
     int nheads;            /* MODEL.DiffusionDet.NHEADS          (8)   */
     int dim_feedforward;   /* MODEL.DiffusionDet.DIM_FEEDFORWARD (2048) */
     int dim_dynamic;       /* MODEL.DiffusionDet.DIM_DYNAMIC     (64)  */
-    int num_classes;       /* MODEL.DiffusionDet.NUM_CLASSES     (30)  */
+    int num_classes;       /* MODEL.DiffusionDet.NUM_CLASSES     (30)  1 .. DVID_MAX_CLASSES */
     int num_cls;           /* MODEL.DiffusionDet.NUM_CLS         (1)   */
     int num_reg;           /* MODEL.DiffusionDet.NUM_REG         (3)   */
     int num_heads;         /* MODEL.DiffusionDet.NUM_HEADS       (3)   head_series */
@@ -214,6 +220,16 @@ int dvid_postproc_topk_nms(const float* logits, const float* boxes, int nsets, i
 /* Bytes of scratch dvid_postproc_topk_nms needs for that shape: n_frames*nsets*m*24 where the single-kernel NMS runs, more where the
  * tiled form does (0 for a shape with no work). */
 int64_t dvid_postproc_scratch_bytes(int nsets, int n_frames, int m);
+/* The candidate selection of dvid_postproc_topk_nms on its own, in its streaming form (csrc/postproc.hip: topk_stream_kernel), forced at
+ * any 1 <= m <= DVID_NMS_MAX_CANDIDATES and 1 <= c <= DVID_MAX_CLASSES: logits [nsets, n_frames, m, c], boxes [nsets, n_frames, m, 4] ->
+ * per (frame, set) the m largest of the m * c sigmoid scores in (score desc, flat index asc) order: cand_boxes [n_frames, nsets * m, 4]
+ * (the box of the score's row, unclipped), cand_scores and cand_labels (int32, class + 1) [n_frames, nsets * m], set s at columns
+ * [s m, (s + 1) m).  dvid_postproc_topk_nms selects with one of three kernels that give the same bits: the keys of a (frame, set) held
+ * in LDS and radix-selected where m * c * 4 + 8 * next_pow2(m) + 8 KiB <= 150 KiB (300 x 30, 300 x 80), a full sort in LDS up to 16384
+ * padded keys, and this form, which recomputes the keys from the logits on every pass and holds none, for every other shape (500 x 80,
+ * any m x 1203). */
+int dvid_topk_candidates_stream(const float* logits, const float* boxes, int nsets, int n_frames, int m, int c, float* cand_boxes,
+                                float* cand_scores, int* cand_labels, void* stream);
 /* The tiled NMS on its own, at any 1 <= n <= DVID_NMS_MAX_CANDIDATES: cand_boxes [n_frames, n, 4] (unclipped xyxy), cand_scores
  * [n_frames, n], cand_labels [n_frames, n] (int32, >= 1) -> per frame the survivors of the class-aware NMS in (score desc, position
  * asc) order, clipped to the image: out_boxes [n_frames, out_cap, 4], out_scores, out_labels [n_frames, out_cap] (zero behind
