@@ -190,6 +190,11 @@ int dvid_nms_frames_tiled_launch(const float* cand_boxes, const float* cand_scor
                                  float img_h, float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels,
                                  int* out_counts, void* scratch, hipStream_t s);
 
+// seqnms.hip: Seq-NMS over videos, a workgroup per (video, class); class_counts / video_starts are host tables (include/dvid_hip.h)
+long long dvid_seq_nms_scratch_size(const int* class_counts, const int* video_starts, int n_videos, int num_classes);
+int dvid_seq_nms_launch(const float* dets, const int* counts, const int* class_counts, const int* video_starts, int n_videos, int cap, int num_classes,
+                        unsigned char* keep, float* scores, int* status, void* scratch, hipStream_t s);
+
 // fps.hip
 int dvid_cdist_launch(const float* x, int n, int d, float* dist, hipStream_t s);
 int dvid_fps_launch(const float* dist, int n, int m, int bs_emul, int* idx, hipStream_t s);

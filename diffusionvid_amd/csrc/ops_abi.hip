@@ -180,6 +180,33 @@ int dvid_nms_frames_tiled(const float* cand_boxes, const float* cand_scores, con
     return DVID_OK;
 }
 
+int64_t dvid_seq_nms_scratch_bytes(const int* class_counts, const int* video_starts, int n_videos, int num_classes) {
+    return (int64_t)dvid_seq_nms_scratch_size(class_counts, video_starts, n_videos, num_classes);
+}
+
+int dvid_seq_nms_video(const float* dets, const int* counts, const int* class_counts, const int* video_starts, int n_videos, int cap,
+                       int num_classes, unsigned char* keep, float* scores, int* status, void* scratch, int64_t scratch_bytes, void* stream) {
+    g_err[0] = 0;
+    if (!dets || !counts || !class_counts || !video_starts || !keep || !scores || !status) FAIL(DVID_ERR_ARG, "Seq-NMS: null pointer");
+    if (n_videos < 1 || cap < 1 || num_classes < 1) FAIL(DVID_ERR_ARG, "Seq-NMS: bad sizes (%d videos, %d rows per frame, %d classes)", n_videos, cap, num_classes);
+    if (video_starts[0] != 0) FAIL(DVID_ERR_ARG, "Seq-NMS: video_starts[0] is %d, not 0", video_starts[0]);
+    for (int v = 0; v < n_videos; ++v)
+        if (video_starts[v + 1] < video_starts[v]) FAIL(DVID_ERR_ARG, "Seq-NMS: video_starts decreases at video %d", v);
+    if (cap > DVID_NMS_MAX_CANDIDATES || num_classes > DVID_MAX_CLASSES)
+        FAIL(DVID_ERR_UNSUPPORTED, "Seq-NMS: %d rows per frame x %d classes exceed the limits of %d rows (DVID_NMS_MAX_CANDIDATES) and %d classes (DVID_MAX_CLASSES)",
+             cap, num_classes, DVID_NMS_MAX_CANDIDATES, DVID_MAX_CLASSES);
+    const long long need = dvid_seq_nms_scratch_size(class_counts, video_starts, n_videos, num_classes);
+    if (need < 0) FAIL(DVID_ERR_ARG, "Seq-NMS: a negative entry in class_counts");
+    if (need > DVID_SEQ_NMS_MAX_SCRATCH_BYTES)
+        FAIL(DVID_ERR_UNSUPPORTED, "Seq-NMS: %lld bytes of link rows and tables for %d frames x %d classes exceed the limit of %lld (DVID_SEQ_NMS_MAX_SCRATCH_BYTES): "
+             "run fewer videos per call", need, video_starts[n_videos], num_classes, (long long)DVID_SEQ_NMS_MAX_SCRATCH_BYTES);
+    if (need > 0 && (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 15)))
+        FAIL(DVID_ERR_ARG, "Seq-NMS: the scratch holds %lld bytes, %lld are needed (16-byte aligned)", (long long)scratch_bytes, need);
+    TRY(dvid_seq_nms_launch(dets, counts, class_counts, video_starts, n_videos, cap, num_classes, keep, scores, status, scratch,
+                            reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
 int dvid_cdist(const float* x, int n, int d, float* dist, void* stream) {
     g_err[0] = 0;
     TRY(dvid_cdist_launch(x, n, d, dist, reinterpret_cast<hipStream_t>(stream)));

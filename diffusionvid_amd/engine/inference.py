@@ -65,12 +65,69 @@ def lookahead_items(dataset, indices, infer_batch, lookahead):
         yield idx, item
 
 
-def compute_on_dataset(model, dataset, indices, device, timer=None):
+def seq_nms_boxlists(boxlists, num_classes, nms_thresh, seq_nms_fn=None, nms_fn=None):
+    """TEST.SEQ_NMS on ONE video (mega_core/engine/inference.py:54-69 around the reference's seq_nms.py): `boxlists` are the video's
+    per-frame results in frame order, exactly what the detector returned -- after its own top-k and, with USE_NMS, its per-frame NMS --
+    split by `labels` (the hand-over; the reference reads an attribute only its R-CNN post-processor has).  Steps: pack
+    (pack_predictions' layout) -> ops.seq_nms_video (links at IoU >= 0.5, best path by dynamic programming, rescored to its mean,
+    0.3-suppression around it, repeated) -> suppressed rows dropped, survivors in their order with the rescored `scores` -> the
+    trailing per-class NMS of :63-69 at `nms_thresh` through ops.nms_frames_tiled (class-aware, survivors in score order, clipped to
+    the image) -> new BoxLists of the same class.  The reference passes its post-processor's score threshold as that IoU threshold
+    (:60, :67); callers here pass MODEL.ROI_HEADS.NMS.  A video that compute_on_video_sharded spread over ranks is finished by calling
+    this on the gathered, frame-ordered result.
+    seq_nms_fn(dets, counts, num_classes) -> (keep, scores) and nms_fn(boxes, scores, labels, img_w, img_h, iou) -> (boxes, scores,
+    labels, counts), both on [frames, cap, ...] tensors: injected by tests without a GPU; default the two library ops."""
+    boxlists = list(boxlists)
+    if not boxlists:
+        return []
+    on_gpu = seq_nms_fn is None or nms_fn is None
+    if on_gpu:
+        from .. import ops
+    _, counts, dets, sizes = pack_predictions(dict(enumerate(boxlists)))
+    n, cap = dets.shape[:2]
+    if cap == 0:
+        return [bl.copy_with_fields(bl.fields()) for bl in boxlists]
+    dev = torch.device("cuda") if on_gpu else torch.device("cpu")
+    fn = seq_nms_fn if seq_nms_fn is not None else ops.seq_nms_video
+    keep, scores = fn(dets.to(dev) if seq_nms_fn is None else dets, counts.to(dev) if seq_nms_fn is None else counts, num_classes)
+    keep, scores = torch.as_tensor(keep).cpu().bool(), torch.as_tensor(scores).cpu()
+    # survivors to the front, in their order.  The trailing NMS takes the same number of candidates for every frame: the rows behind a
+    # frame's survivors are zero-area boxes at the origin with the smallest normal score, which neither suppress nor are suppressed
+    # (their IoU with anything is 0 or 0 / 0), sort behind every survivor, and leave the largest coordinate -- the class offset of the
+    # NMS -- as it was (the detector's boxes are clipped to the image, so it is >= 0)
+    left = keep.sum(dim=1).to(torch.int32)
+    order = torch.sort((~keep).to(torch.int8), dim=1, stable=True).indices
+    live = torch.arange(cap)[None, :] < left[:, None]
+    boxes = torch.where(live[:, :, None], torch.gather(dets[:, :, :4], 1, order[:, :, None].expand(n, cap, 4)), torch.zeros(()))
+    sc = torch.where(live, torch.gather(scores, 1, order), torch.full((), torch.finfo(torch.float32).tiny))
+    lab = torch.where(live, torch.gather(dets[:, :, 5], 1, order), torch.ones(())).to(torch.int32)
+    w, h = boxlists[0].size
+    nms = nms_fn if nms_fn is not None else ops.nms_frames_tiled
+    if nms_fn is None:
+        boxes, sc, lab = boxes.to(dev), sc.to(dev), lab.to(dev)
+    ob, osc, ol, oc = nms(boxes.contiguous(), sc.contiguous(), lab.contiguous(), w, h, nms_thresh)
+    ob, osc, ol = torch.as_tensor(ob).cpu(), torch.as_tensor(osc).cpu(), torch.as_tensor(ol).cpu()
+    oc = torch.as_tensor(oc).cpu().to(torch.int32) - (cap - left)          # the padding rows all survive, behind the frame's own
+    out = unpack_predictions(torch.arange(n), oc, torch.cat([ob, osc[:, :, None], ol.to(torch.float32)[:, :, None]], dim=2), sizes)
+    return [out[j] for j in range(n)]
+
+
+def compute_on_dataset(model, dataset, indices, device, timer=None, do_seq_nms=False, seq_nms=None):
     """mega_core/engine/inference.py:22-94.  With INPUT.LOOKAHEAD_BATCHES > 1 on the model the hand-over is built here
-    (`lookahead_items`), so any dataset that follows the reference's item protocol gets the grouped schedule."""
+    (`lookahead_items`), so any dataset that follows the reference's item protocol gets the grouped schedule.
+    do_seq_nms (TEST.SEQ_NMS, :54-69, :76-89): the image ids of a video's calls are collected from its frame_id 0 on, and on the call
+    with frame_id == seg_len - 1 the whole video's entries are replaced by `seq_nms(list of its BoxLists in frame order)`; results stay
+    keyed by image id, so the later frames a look-ahead group returns early are simply there when the video ends.  seq_nms: default
+    seq_nms_boxlists with the model's MODEL.DiffusionDet.NUM_CLASSES and MODEL.ROI_HEADS.NMS."""
     model.eval()
     results = {}
     cpu = torch.device("cpu")
+    video_ids = []
+    if do_seq_nms and seq_nms is None:
+        cfg = model.cfg
+
+        def seq_nms(bls):
+            return seq_nms_boxlists(bls, cfg.MODEL.DiffusionDet.NUM_CLASSES, cfg.MODEL.ROI_HEADS.NMS)
     la = int(getattr(model, "lookahead", 1) or 1)
     for idx, item in lookahead_items(dataset, indices, getattr(model, "infer_batch", 1), la):
         images, _, image_ids = item
@@ -83,6 +140,12 @@ def compute_on_dataset(model, dataset, indices, device, timer=None):
                 timer.append(time.perf_counter() - t0)
             output = [o.to(cpu) for o in output]
         results.update({img_id: r for img_id, r in zip(image_ids, output)})
+        if do_seq_nms:
+            if images["frame_id"] == 0:
+                video_ids = []
+            video_ids.append(image_ids[0])
+            if images["frame_id"] == images["seg_len"] - 1:
+                results.update(zip(video_ids, seq_nms([results[i] for i in video_ids])))
     return results
 
 
@@ -114,6 +177,7 @@ def compute_on_video_sharded(model, dataset, start, num_frames, device, rank=Non
     `video_shard_plan`: rank 0 runs the first call (24 global + the first local frames) and the memory it builds --
     [900, d] + [150, d] fp32, 1.07 MB -- is broadcast (RCCL over xGMI; the only data-path exchange of this mode);
     every rank then runs its own groups.  Returns this rank's {image id: BoxList}; merge with gather_predictions.
+    TEST.SEQ_NMS needs the whole video: it is not applied here -- call seq_nms_boxlists on the gathered result in frame order.
     `broadcast(tensors, src)`: injected for tests; default torch.distributed.broadcast of each tensor."""
     rank = comm.get_rank() if rank is None else rank
     world = comm.get_world_size() if world is None else world
@@ -230,9 +294,10 @@ def predictions_list(merged):
 
 
 def inference(model, dataset, indices, device, output_folder=None, gt_boxlists=None, max_det=None, motion_specific=False,
-              motion_ious=None, logger=None, class_module=None):
+              motion_ious=None, logger=None, class_module=None, seq_nms=None):
     """Reference `inference` (mega_core/engine/inference.py:118-181) for the in-scope path: run this rank's share, gather on
-    rank 0, write `predictions.pth` (`class_module`: see vid_eval.save_predictions) and evaluate as the reference's
+    rank 0, write `predictions.pth` -- `predictions_seq_nms.pth` instead when the model's config has TEST.SEQ_NMS (:165-168; the
+    step itself runs in compute_on_dataset, `seq_nms` as there) -- (`class_module`: see vid_eval.save_predictions) and evaluate as the reference's
     `evaluate` -> `do_vid_evaluation` does (vid_eval.py:14-78): when the dataset serves `get_img_info` / `get_groundtruth`
     the predictions are mapped from the resized frame to the annotation's original size first and `result.txt` is written;
     `gt_boxlists` (a list of BoxList, one per image id) stands in for a dataset without annotations -- each prediction is
@@ -242,14 +307,15 @@ def inference(model, dataset, indices, device, output_folder=None, gt_boxlists=N
 
     from ..data.evaluation import vid_eval
     from ..utils import comm
-    results = compute_on_dataset(model, dataset, indices, device)
+    do_seq_nms = bool(getattr(getattr(getattr(model, "cfg", None), "TEST", None), "SEQ_NMS", False))
+    results = compute_on_dataset(model, dataset, indices, device, do_seq_nms=do_seq_nms, seq_nms=seq_nms)
     merged = gather_predictions(results, max_det, device=device)
     if not comm.is_main_process():
         return None, None
     preds = predictions_list(merged)
     if output_folder:
         os.makedirs(output_folder, exist_ok=True)
-        vid_eval.save_predictions(preds, os.path.join(output_folder, "predictions.pth"), class_module)
+        vid_eval.save_predictions(preds, os.path.join(output_folder, "predictions_seq_nms.pth" if do_seq_nms else "predictions.pth"), class_module)
     source = None
     if gt_boxlists is not None:
         source = vid_eval.GroundTruthList(gt_boxlists, getattr(dataset, "map_class_id_to_class_name", None))

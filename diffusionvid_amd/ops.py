@@ -408,6 +408,52 @@ def nms_frames_tiled(cand_boxes, cand_scores, cand_labels, img_w, img_h, iou=0.5
     return ob, osc, ol, oc
 
 
+SEQ_NMS_ERR_ROUNDS, SEQ_NMS_ERR_COUNTS = 1 << 30, 1 << 29          # include/dvid_hip.h
+
+
+def seq_nms_class_counts(dets, counts, num_classes):
+    """[frames, num_classes] int32 on the host: the frame's detections with label c + 1 (the table dvid_seq_nms_video lays its scratch out from)"""
+    dets, counts = dets.detach().cpu(), counts.detach().cpu().to(torch.int64)
+    F, cap = dets.shape[:2]
+    lab = dets[:, :, 5].to(torch.int64)
+    ok = (torch.arange(cap)[None, :] < counts[:, None]) & (lab >= 1) & (lab <= num_classes)
+    table = torch.zeros((F, num_classes), dtype=torch.int32)
+    rows = torch.arange(F)[:, None].expand(F, cap)[ok]
+    table.index_put_((rows, lab[ok] - 1), torch.ones((), dtype=torch.int32), accumulate=True)
+    return table
+
+
+def seq_nms_video(dets, counts, num_classes, video_starts=None, return_status=False):
+    """Seq-NMS (TEST.SEQ_NMS, the reference's seq_nms.py) over one video in engine.pack_predictions' layout -- dets [frames, cap, 6] fp32
+    (box4, score, label), counts [frames] -- or over several at once: `video_starts` [n_videos + 1] splits the frames.  Returns (keep
+    [frames, cap] uint8, scores [frames, cap] fp32: the rescored values, 0 for a suppressed row), on the device; with return_status also
+    the [n_videos, num_classes] int32 status words (the rounds each class ran).  Independent of any model handle and of DTYPE."""
+    dets, counts = _cuda(dets, torch.float32), _cuda(counts, torch.int32)
+    F, cap = counts.shape[0], dets.shape[1] if dets.dim() == 3 else -1
+    assert dets.shape == (F, cap, 6), "dets is [frames, cap, 6]"
+    starts = torch.tensor([0, F] if video_starts is None else [int(v) for v in video_starts], dtype=torch.int32)
+    assert int(starts[-1]) == F and num_classes >= 1, "video_starts ends at the frame count"
+    nv = starts.numel() - 1
+    dev = dets.device
+    keep = torch.empty((F, cap), dtype=torch.uint8, device=dev)
+    scores = torch.empty((F, cap), dtype=torch.float32, device=dev)
+    status = torch.empty((nv, num_classes), dtype=torch.int32, device=dev)
+    if F == 0 or cap == 0:
+        return (keep, scores, status.zero_()) if return_status else (keep, scores)
+    table = seq_nms_class_counts(dets, counts, num_classes).contiguous() if cap <= NMS_MAX_CANDIDATES and num_classes <= MAX_CLASSES else \
+        torch.zeros((F, num_classes), dtype=torch.int32)          # over a limit: the library refuses before it reads the table
+    need = max(0, int(_lib.load().dvid_seq_nms_scratch_bytes(ptr(table), ptr(starts), nv, num_classes)))
+    scratch = torch.empty((max(16, need),), dtype=torch.uint8, device=dev) if need <= (1 << 30) else None
+    call("dvid_seq_nms_video", ptr(dets), ptr(counts), ptr(table), ptr(starts), nv, cap, num_classes, ptr(keep), ptr(scores), ptr(status),
+         ptr(scratch), need if scratch is not None else 0, stream_ptr())
+    st = status.cpu()
+    if int((st & (SEQ_NMS_ERR_ROUNDS | SEQ_NMS_ERR_COUNTS)).ne(0).sum()):
+        v, c = [int(x) for x in torch.nonzero(st & (SEQ_NMS_ERR_ROUNDS | SEQ_NMS_ERR_COUNTS))[0]]
+        raise _lib.DvidError("Seq-NMS: video %d class %d ended with status 0x%x (%s)" % (
+            v, c + 1, int(st[v, c]), "round bound reached" if int(st[v, c]) & SEQ_NMS_ERR_ROUNDS else "class_counts does not describe dets"))
+    return (keep, scores, st) if return_status else (keep, scores)
+
+
 def split_detection_buffer(buf, n, cap):
     """The four post-processing outputs are views of ONE flat fp32 buffer [boxes | scores | labels(int32) |
     counts(int32)], so a caller can bring a whole batch to the host with a single D2H copy

@@ -239,6 +239,32 @@ int dvid_nms_frames_tiled(const float* cand_boxes, const float* cand_scores, con
                           float img_h, float iou_threshold, int use_nms, int out_cap, float* out_boxes, float* out_scores,
                           int* out_labels, int* out_counts, void* scratch, void* stream);
 int64_t dvid_nms_tiled_scratch_bytes(int n_frames, int n);
+/* Seq-NMS (TEST.SEQ_NMS; the reference's seq_nms.py, its engine's inference.py:54-62) over the detections of n_videos videos, as one
+ * launch with a workgroup per (video, class) (csrc/seqnms.hip).  dets [frames, cap, 6] (device; a row = xyxy box, score, label as a float, labels 1 ..
+ * num_classes, the layout of engine.pack_predictions), counts [frames] (device): the rows in front of counts[f] are the frame's detections.
+ * video_starts [n_videos + 1] (host): video v is frames [video_starts[v], video_starts[v + 1]); video_starts[n_videos] = frames.
+ * class_counts [frames, num_classes] (host): the frame's detections with label c + 1; the scratch is sized and laid out from it, and a
+ * table that does not describe `dets` ends as DVID_SEQ_NMS_ERR_COUNTS in the class's status word, with nothing written outside the
+ * class's share.  Per class, and independently per class: boxes of adjacent frames link at IoU >= 0.5 (x2 - x1 + 1 extents); the
+ * highest-sum path through the links is found by dynamic programming (strictly greater improves, lowest predecessor and first
+ * (frame, box) on ties), its boxes are rescored to sum / length, every other box within IoU 0.3 of a path box in its frame is
+ * suppressed, and the search repeats until the best sum is below 1e-2 or no link is left.  float32 without contraction and an IEEE
+ * division: the reference's bits.  -> keep [frames, cap] (uint8: 0 for a suppressed row and behind counts[f]), scores [frames, cap]
+ * (rescored; 0 where keep is 0), status [n_videos, num_classes] (int32: the rounds the class ran, or an error word; the rounds are
+ * bounded by the class's box count + 1, DVID_SEQ_NMS_ERR_ROUNDS beyond).  One-frame videos and classes without a link leave the input
+ * as it is.  num_classes <= DVID_MAX_CLASSES, cap <= DVID_NMS_MAX_CANDIDATES and dvid_seq_nms_scratch_bytes(...) <=
+ * DVID_SEQ_NMS_MAX_SCRATCH_BYTES (DVID_ERR_UNSUPPORTED beyond, before anything is launched).  scratch: >= that many bytes, 16-byte
+ * aligned (may be NULL where it is 0).  The call uploads the layout and waits for that copy: it is synchronous with `stream`. */
+#define DVID_SEQ_NMS_MAX_SCRATCH_BYTES (1ll << 30)
+#define DVID_SEQ_NMS_ERR_ROUNDS (1 << 30)
+#define DVID_SEQ_NMS_ERR_COUNTS (1 << 29)
+int dvid_seq_nms_video(const float* dets, const int* counts, const int* class_counts, const int* video_starts, int n_videos, int cap,
+                       int num_classes, unsigned char* keep, float* scores, int* status, void* scratch, int64_t scratch_bytes, void* stream);
+/* Bytes of scratch for those tables (0: no class has a link to look for; -1: bad arguments).  Per (video, class) with at least one pair
+ * of boxes in adjacent frames, with F frames, n_f boxes in frame f, N = sum n_f, L = sum over frame pairs of n_f * ceil(n_{f+1} / 64)
+ * link words and M = sum ceil(n_f / 64): round16(12 (F + 1)) + round16(8 (L + M) + 36 N + 12 F) bytes, behind round16(40 n_videos
+ * num_classes) bytes of headers. */
+int64_t dvid_seq_nms_scratch_bytes(const int* class_counts, const int* video_starts, int n_videos, int num_classes);
 int dvid_cdist(const float* x, int n, int d, float* dist, void* stream);
 /* bs_emul: block size of the reference CUDA launch to emulate for tie-breaking (0 = fps.cu's own rule) */
 int dvid_fps_greedy(const float* dist, int n, int m, int bs_emul, int* idx, void* stream);
