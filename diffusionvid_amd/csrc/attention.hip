@@ -151,6 +151,27 @@ int dvid_mha_mfma_launch(const half_t* q, const half_t* k, const half_t* v, half
 // =============================================================================================
 namespace {
 
+// Position `pos` (< WS * WS) of window (wx, wy) of image b -> `tok`, the token row it gathers from (-1: a padded position), and `region`,
+// its region of the shifted map's attention mask (swintransformer.py:226-254; 0 without a shift).  Hp / Wp: the map padded to whole
+// windows.  The gather address resolves padding and roll.  Integer arithmetic, shared by the fp16 kernels of both window sizes; the fp32
+// kernels further down keep the same statements inline (through this helper the compiler allocates them one SGPR less, and this
+// file holds every kernel to the register table it had).
+template <int WS>
+__device__ __forceinline__ void swin_window_pos(int pos, int wx, int wy, int b, int H, int W, int Hp, int Wp, int shift, int& tok, int& region) {
+    const int py = pos / WS, px = pos - py * WS;
+    const int ys = wy * WS + py, xs = wx * WS + px;          // coordinates in the shifted, padded map
+    int y = ys + shift, x = xs + shift;                      // source coordinates before the roll
+    if (y >= Hp) y -= Hp;
+    if (x >= Wp) x -= Wp;
+    region = 0;
+    if (shift > 0) {
+        const int hr = ys < Hp - WS ? 0 : (ys < Hp - shift ? 1 : 2);
+        const int wr = xs < Wp - WS ? 0 : (xs < Wp - shift ? 1 : 2);
+        region = hr * 3 + wr;
+    }
+    tok = (y < H && x < W) ? (b * H + y) * W + x : -1;
+}
+
 template <int WPB>
 __global__ __launch_bounds__(256) void swin_window_attn_kernel(const half_t* __restrict__ qkv, const half_t* __restrict__ qkv_bias16,
                                                                 const float* __restrict__ relbias, half_t* __restrict__ out, int H,
@@ -200,19 +221,7 @@ __global__ __launch_bounds__(256) void swin_window_attn_kernel(const half_t* __r
 
     if (tid < 64) {
         int t = -1, reg = 0;
-        if (tid < NT) {
-            const int py = tid / WS, px = tid - py * WS;
-            const int ys = wy * WS + py, xs = wx * WS + px;                  // coordinates in the shifted, padded map
-            int y = ys + shift, x = xs + shift;                              // source coordinates before the roll
-            if (y >= Hp) y -= Hp;
-            if (x >= Wp) x -= Wp;
-            if (y < H && x < W) t = (b * H + y) * W + x;
-            if (shift > 0) {
-                const int hr = ys < Hp - WS ? 0 : (ys < Hp - shift ? 1 : 2);
-                const int wr = xs < Wp - WS ? 0 : (xs < Wp - shift ? 1 : 2);
-                reg = hr * 3 + wr;
-            }
-        }
+        if (tid < NT) swin_window_pos<WS>(tid, wx, wy, b, H, W, Hp, Wp, shift, t, reg);
         tok[tid] = t;
         region[tid] = reg;
     }
@@ -371,18 +380,9 @@ __global__ __launch_bounds__(576) void swin_window12_attn_kernel(const half_t* _
     const int b = wid / nwy;
 
     if (tid < NT) {
-        const int py = tid / WS, px = tid - py * WS;
-        const int ys = wy * WS + py, xs = wx * WS + px;                  // coordinates in the shifted, padded map
-        int y = ys + shift, x = xs + shift;                              // source coordinates before the roll
-        if (y >= Hp) y -= Hp;
-        if (x >= Wp) x -= Wp;
-        int reg = 0;
-        if (shift > 0) {
-            const int hr = ys < Hp - WS ? 0 : (ys < Hp - shift ? 1 : 2);
-            const int wr = xs < Wp - WS ? 0 : (xs < Wp - shift ? 1 : 2);
-            reg = hr * 3 + wr;
-        }
-        tok[tid] = (y < H && x < W) ? (b * H + y) * W + x : -1;
+        int t, reg;
+        swin_window_pos<WS>(tid, wx, wy, b, H, W, Hp, Wp, shift, t, reg);
+        tok[tid] = t;
         region[tid] = reg;
     }
     __syncthreads();
@@ -480,6 +480,352 @@ int dvid_swin_window12_attn_launch(const half_t* qkv, const half_t* qkv_bias16, 
     // more workgroups than four would
     hipLaunchKernelGGL(swin_window12_attn_kernel<2>, dim3((unsigned)((nwin + 1) / 2 * nheads)), dim3(576), 0, s, qkv, qkv_bias16, relbias, out,
                        H, W, C, nheads, shift, 1.0f / sqrtf(32.f), (int)nwin);
+    LAUNCH_CHECK();
+    return DVID_OK;
+}
+
+// =============================================================================================
+// DTYPE float32: the same three attentions on fp32 storage, on the VALU (one query per lane, or four lanes per query; exact fp32
+// products and softmax) -- other algorithms than the MFMA kernels above, not their templates.
+// =============================================================================================
+namespace {
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// attention, head dim 32: out[b][q][h*32 ..] = softmax_k(q . k / sqrt(32)) v.  One query per lane (its 32 q values and 32 output
+// accumulators in registers), keys and values in chunks of 64 through LDS (every lane reads the same key: broadcast reads), the
+// running maximum / sum of the streaming softmax updated once per 16 keys.
+// ---------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void f32_mha_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                     float* __restrict__ out, int lq, int lk, int q_ld, int kv_ld, int out_ld, long q_bs,
+                                                     long kv_bs, long out_bs, float scale) {
+    __shared__ float Ks[64 * 32];
+    __shared__ float Vs[64 * 32];
+    const int tid = threadIdx.x, head = blockIdx.y, b = blockIdx.z;
+    const int qi = blockIdx.x * 64 + tid;
+    const bool live = qi < lq;
+    float qv[32], acc[32];
+    {
+        const float* qp = q + b * q_bs + (long)(live ? qi : 0) * q_ld + head * 32;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float4v t = *reinterpret_cast<const float4v*>(qp + j * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) qv[j * 4 + e] = t[e] * scale;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 32; ++e) acc[e] = 0.f;
+    float mx = -INFINITY, den = 0.f;
+    const float* kb = k + b * kv_bs + head * 32;
+    const float* vb = v + b * kv_bs + head * 32;
+    for (int k0 = 0; k0 < lk; k0 += 64) {
+        const int nk = lk - k0 < 64 ? lk - k0 : 64;
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {          // 64 keys x 8 float4: lane -> (key = (i * 64 + tid) / 8, quarter = .. % 8)
+            const int idx = i * 64 + tid, kr = idx >> 3, c4 = (idx & 7) * 4;
+            float4v kk = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
+            if (kr < nk) {
+                kk = *reinterpret_cast<const float4v*>(kb + (long)(k0 + kr) * kv_ld + c4);
+                vv = *reinterpret_cast<const float4v*>(vb + (long)(k0 + kr) * kv_ld + c4);
+            }
+            *reinterpret_cast<float4v*>(&Ks[kr * 32 + c4]) = kk;
+            *reinterpret_cast<float4v*>(&Vs[kr * 32 + c4]) = vv;
+        }
+        __syncthreads();
+        // sub-chunks of 16 keys: scores into registers, one maximum / rescale per sub-chunk, then the weighted values
+#pragma unroll 1
+        for (int c0 = 0; c0 < nk; c0 += 16) {
+            float sc16[16];
+            float cmx = -INFINITY;
+#pragma unroll
+            for (int kk = 0; kk < 16; ++kk) {
+                float d = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float4v t = *reinterpret_cast<const float4v*>(&Ks[(c0 + kk) * 32 + j * 4]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) d = __builtin_fmaf(qv[j * 4 + e], t[e], d);
+                }
+                sc16[kk] = c0 + kk < nk ? d : -INFINITY;
+                cmx = fmaxf(cmx, sc16[kk]);
+            }
+            const float nmx = fmaxf(mx, cmx);
+            const float rescale = expf(mx - nmx);          // first sub-chunk: exp(-inf) = 0 on zero accumulators
+            den *= rescale;
+#pragma unroll
+            for (int e = 0; e < 32; ++e) acc[e] *= rescale;
+            mx = nmx;
+#pragma unroll
+            for (int kk = 0; kk < 16; ++kk) {
+                const float pr = expf(sc16[kk] - mx);          // masked keys: exp(-inf) = 0
+                den += pr;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float4v t = *reinterpret_cast<const float4v*>(&Vs[(c0 + kk) * 32 + j * 4]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[j * 4 + e] = __builtin_fmaf(pr, t[e], acc[j * 4 + e]);
+                }
+            }
+        }
+    }
+    if (live) {
+        const float inv = 1.f / den;
+        float* op = out + b * out_bs + (long)qi * out_ld + head * 32;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            *reinterpret_cast<float4v*>(op + j * 4) = (float4v){acc[j * 4] * inv, acc[j * 4 + 1] * inv, acc[j * 4 + 2] * inv, acc[j * 4 + 3] * inv};
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Swin window attention (swintransformer.py:68-176, :226-254), fp32: one workgroup (one wave) per (window, head), lane = query position of
+// the 7 x 7 window, keys and values through LDS.  A padded window position holds the qkv BIAS (the reference pads the normalised tokens
+// with zeros before the qkv Linear); the shifted map's region mask adds -100 between positions of different regions.
+// ---------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void f32_swin_window_attn_kernel(const float* __restrict__ qkv, const float* __restrict__ qkv_bias,
+                                                                  const float* __restrict__ relbias, float* __restrict__ out, int H, int W, int C,
+                                                                  int nheads, int shift, float scaling, int nwin) {
+    constexpr int WS = 7, NT = 49;
+    __shared__ float Ks[NT * 32];
+    __shared__ float Vs[NT * 32];
+    __shared__ int tok[64];
+    __shared__ int region[64];
+    const int tid = threadIdx.x;
+    const int lid = igemm_xcd_remap((int)blockIdx.x, nwin * nheads);
+    int wid = lid / nheads;
+    const int h = lid - wid * nheads;
+    const int Hp = (H + WS - 1) / WS * WS, Wp = (W + WS - 1) / WS * WS;
+    const int nwx = Wp / WS, nwy = Hp / WS;
+    const int wx = wid % nwx;
+    wid /= nwx;
+    const int wy = wid % nwy;
+    const int b = wid / nwy;
+    {
+        int t = -1, reg = 0;
+        if (tid < NT) {
+            const int py = tid / WS, px = tid - py * WS;
+            const int ys = wy * WS + py, xs = wx * WS + px;          // coordinates in the shifted, padded map
+            int y = ys + shift, x = xs + shift;                      // source coordinates before the roll
+            if (y >= Hp) y -= Hp;
+            if (x >= Wp) x -= Wp;
+            if (y < H && x < W) t = (b * H + y) * W + x;
+            if (shift > 0) {
+                const int hr = ys < Hp - WS ? 0 : (ys < Hp - shift ? 1 : 2);
+                const int wr = xs < Wp - WS ? 0 : (xs < Wp - shift ? 1 : 2);
+                reg = hr * 3 + wr;
+            }
+        }
+        tok[tid] = t;
+        region[tid] = reg;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < NT * 8; idx += 64) {
+        const int key = idx >> 3, c4 = (idx & 7) * 4;
+        const int t = tok[key];
+        const float* src = t >= 0 ? qkv + (long)t * 3 * C : qkv_bias;
+        *reinterpret_cast<float4v*>(&Ks[key * 32 + c4]) = *reinterpret_cast<const float4v*>(src + C + h * 32 + c4);
+        *reinterpret_cast<float4v*>(&Vs[key * 32 + c4]) = *reinterpret_cast<const float4v*>(src + 2 * C + h * 32 + c4);
+    }
+    const int qp = tid < NT ? tid : NT - 1;
+    const int tq = tok[qp], qreg = region[qp];
+    float qv[32];
+    {
+        const float* qsrc = (tq >= 0 ? qkv + (long)tq * 3 * C : qkv_bias) + h * 32;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float4v t = *reinterpret_cast<const float4v*>(qsrc + j * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) qv[j * 4 + e] = t[e] * scaling;
+        }
+    }
+    __syncthreads();
+    const float* brow = relbias + ((long)h * NT + qp) * SWIN_RELBIAS_PITCH;
+    float sc[NT];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int key = 0; key < NT; ++key) {
+        float d = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float4v t = *reinterpret_cast<const float4v*>(&Ks[key * 32 + j * 4]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) d = __builtin_fmaf(qv[j * 4 + e], t[e], d);
+        }
+        d += brow[key];
+        if (shift > 0 && region[key] != qreg) d += -100.0f;
+        sc[key] = d;
+        mx = fmaxf(mx, d);
+    }
+    float acc[32];
+#pragma unroll
+    for (int e = 0; e < 32; ++e) acc[e] = 0.f;
+    float den = 0.f;
+#pragma unroll
+    for (int key = 0; key < NT; ++key) {
+        const float pr = expf(sc[key] - mx);
+        den += pr;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float4v t = *reinterpret_cast<const float4v*>(&Vs[key * 32 + j * 4]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[j * 4 + e] = __builtin_fmaf(pr, t[e], acc[j * 4 + e]);
+        }
+    }
+    if (tid < NT && tq >= 0) {          // padded positions produce no output
+        const float inv = 1.f / den;
+        float* op = out + (long)tq * C + h * 32;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            *reinterpret_cast<float4v*>(op + j * 4) = (float4v){acc[j * 4] * inv, acc[j * 4 + 1] * inv, acc[j * 4 + 2] * inv, acc[j * 4 + 3] * inv};
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The same with 12 x 12 windows (144 tokens, shift 0 or 6).  One query per lane of one wave no longer covers a window, and 144 scores
+// per lane would not stay in registers: a workgroup is nine waves (576 threads) for one (window, head), FOUR lanes per query, lane
+// `part` of a query taking keys part, part + 4, ... (36 scores per lane).  The four partial maxima, sums and 32-float accumulators meet
+// in two xor-shuffles inside the quad; lane 0 of the quad writes the row.  K and V rows have a pitch of 36 floats (2 x 20.25 KB of
+// LDS): the four rows a quad reads in one ds_read_b128 start 36 banks apart, conflict-free.
+// ---------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(576) void f32_swin_window12_attn_kernel(const float* __restrict__ qkv, const float* __restrict__ qkv_bias,
+                                                                     const float* __restrict__ relbias, float* __restrict__ out, int H, int W, int C,
+                                                                     int nheads, int shift, float scaling, int nwin) {
+    constexpr int WS = 12, NT = 144, KP = 36, NPART = 4, NS = NT / NPART;
+    __shared__ __attribute__((aligned(16))) float Ks[NT * KP];
+    __shared__ __attribute__((aligned(16))) float Vs[NT * KP];
+    __shared__ int tok[NT];
+    __shared__ int region[NT];
+    const int tid = threadIdx.x;
+    const int lid = igemm_xcd_remap((int)blockIdx.x, nwin * nheads);
+    int wid = lid / nheads;
+    const int h = lid - wid * nheads;
+    const int Hp = (H + WS - 1) / WS * WS, Wp = (W + WS - 1) / WS * WS;
+    const int nwx = Wp / WS, nwy = Hp / WS;
+    const int wx = wid % nwx;
+    wid /= nwx;
+    const int wy = wid % nwy;
+    const int b = wid / nwy;
+    if (tid < NT) {
+        const int py = tid / WS, px = tid - py * WS;
+        const int ys = wy * WS + py, xs = wx * WS + px;          // coordinates in the shifted, padded map
+        int y = ys + shift, x = xs + shift;                      // source coordinates before the roll
+        if (y >= Hp) y -= Hp;
+        if (x >= Wp) x -= Wp;
+        int reg = 0;
+        if (shift > 0) {
+            const int hr = ys < Hp - WS ? 0 : (ys < Hp - shift ? 1 : 2);
+            const int wr = xs < Wp - WS ? 0 : (xs < Wp - shift ? 1 : 2);
+            reg = hr * 3 + wr;
+        }
+        tok[tid] = (y < H && x < W) ? (b * H + y) * W + x : -1;
+        region[tid] = reg;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < NT * 8; idx += 576) {
+        const int key = idx >> 3, c4 = (idx & 7) * 4;
+        const int t = tok[key];
+        const float* src = t >= 0 ? qkv + (long)t * 3 * C : qkv_bias;
+        *reinterpret_cast<float4v*>(&Ks[key * KP + c4]) = *reinterpret_cast<const float4v*>(src + C + h * 32 + c4);
+        *reinterpret_cast<float4v*>(&Vs[key * KP + c4]) = *reinterpret_cast<const float4v*>(src + 2 * C + h * 32 + c4);
+    }
+    const int qp = tid >> 2, part = tid & 3;                     // query position (< 144) and which quarter of its keys
+    const int tq = tok[qp], qreg = region[qp];
+    float qv[32];
+    {
+        const float* qsrc = (tq >= 0 ? qkv + (long)tq * 3 * C : qkv_bias) + h * 32;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float4v t = *reinterpret_cast<const float4v*>(qsrc + j * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) qv[j * 4 + e] = t[e] * scaling;
+        }
+    }
+    __syncthreads();
+    const float* brow = relbias + ((long)h * NT + qp) * SWIN12_RELBIAS_PITCH + part;
+    float sc[NS];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int key = i * NPART + part;
+        float d = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float4v t = *reinterpret_cast<const float4v*>(&Ks[key * KP + j * 4]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) d = __builtin_fmaf(qv[j * 4 + e], t[e], d);
+        }
+        d += brow[i * NPART];
+        if (shift > 0 && region[key] != qreg) d += -100.0f;
+        sc[i] = d;
+        mx = fmaxf(mx, d);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
+    float acc[32];
+#pragma unroll
+    for (int e = 0; e < 32; ++e) acc[e] = 0.f;
+    float den = 0.f;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int key = i * NPART + part;
+        const float pr = expf(sc[i] - mx);
+        den += pr;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float4v t = *reinterpret_cast<const float4v*>(&Vs[key * KP + j * 4]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[j * 4 + e] = __builtin_fmaf(pr, t[e], acc[j * 4 + e]);
+        }
+    }
+    den += __shfl_xor(den, 1, 64);
+    den += __shfl_xor(den, 2, 64);
+#pragma unroll
+    for (int e = 0; e < 32; ++e) {
+        acc[e] += __shfl_xor(acc[e], 1, 64);
+        acc[e] += __shfl_xor(acc[e], 2, 64);
+    }
+    if (part == 0 && tq >= 0) {         // padded positions produce no output
+        const float inv = 1.f / den;
+        float* op = out + (long)tq * C + h * 32;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            *reinterpret_cast<float4v*>(op + j * 4) = (float4v){acc[j * 4] * inv, acc[j * 4 + 1] * inv, acc[j * 4 + 2] * inv, acc[j * 4 + 3] * inv};
+    }
+}
+
+}  // namespace
+
+int dvid_f32_mha_launch(const float* q, const float* k, const float* v, float* out, int batch, int lq, int lk, int nheads, int q_ld, int kv_ld,
+                        int out_ld, long q_bs, long kv_bs, long out_bs, hipStream_t s) {
+    if (batch <= 0 || lq <= 0) return DVID_OK;
+    if (lk <= 0 || nheads <= 0 || (q_ld | kv_ld | out_ld) % 4) return DVID_ERR_ARG;
+    hipLaunchKernelGGL(f32_mha_kernel, dim3(ceil_div(lq, 64), nheads, batch), dim3(64), 0, s, q, k, v, out, lq, lk, q_ld, kv_ld, out_ld, q_bs, kv_bs,
+                       out_bs, 0.17677669529663688110f);          // 1 / sqrt(32)
+    LAUNCH_CHECK();
+    return DVID_OK;
+}
+
+int dvid_f32_swin_window_attn_launch(const float* qkv, const float* qkv_bias, const float* relbias, float* out, int batch, int H, int W, int C,
+                                     int nheads, int shift, hipStream_t s) {
+    if (C != nheads * 32) return DVID_ERR_UNSUPPORTED;
+    const long nwin = (long)batch * ((H + 6) / 7) * ((W + 6) / 7);
+    if (nwin * nheads > 0x7fffffffL) return DVID_ERR_UNSUPPORTED;
+    if (nwin == 0) return DVID_OK;
+    hipLaunchKernelGGL(f32_swin_window_attn_kernel, dim3((unsigned)(nwin * nheads)), dim3(64), 0, s, qkv, qkv_bias, relbias, out, H, W, C, nheads, shift,
+                       0.17677669529663688110f, (int)nwin);
+    LAUNCH_CHECK();
+    return DVID_OK;
+}
+
+int dvid_f32_swin_window12_attn_launch(const float* qkv, const float* qkv_bias, const float* relbias, float* out, int batch, int H, int W, int C,
+                                       int nheads, int shift, hipStream_t s) {
+    if (C != nheads * 32) return DVID_ERR_UNSUPPORTED;
+    const long nwin = (long)batch * ((H + 11) / 12) * ((W + 11) / 12);
+    if (nwin * nheads > 0x7fffffffL) return DVID_ERR_UNSUPPORTED;
+    if (nwin == 0) return DVID_OK;
+    hipLaunchKernelGGL(f32_swin_window12_attn_kernel, dim3((unsigned)(nwin * nheads)), dim3(576), 0, s, qkv, qkv_bias, relbias, out, H, W, C, nheads,
+                       shift, 0.17677669529663688110f, (int)nwin);
     LAUNCH_CHECK();
     return DVID_OK;
 }

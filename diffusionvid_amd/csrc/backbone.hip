@@ -128,7 +128,7 @@ struct ChainSlices {
 };
 
 // detectron2 build_resnet_fpn_backbone with DTYPE float32: normaliser -> NHWC4, BasicStem (7x7 / 2 + FrozenBN folded + ReLU + max pool),
-// the bottleneck stages layer by layer, FPN; every tensor fp32 (csrc/f32.hip)
+// the bottleneck stages layer by layer, FPN; every tensor fp32 (csrc/f32.hip; prep / max pool: csrc/elementwise.hip)
 int backbone_resnet_f32(dvid_model* m, const float* const* frames, int n, int height, int width, float* p3, float* p4, float* p5, hipStream_t s) {
     const PixelNorm px(m->cfg);
     return run_chains(m, n, s, [&](int f0, int nf, hipStream_t cs) -> int {

@@ -394,10 +394,7 @@ template <bool SC, int TN>
 int bn_launch(const BneckParams& p, hipStream_t s) {
     static_assert(kBytes <= 160 * 1024, "LDS");
     static std::atomic<unsigned long long> attr_set{0};          // one bit per device: the attribute belongs to (function, device)
-    if (first_on_device(attr_set)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bneck64_tail_kernel<SC, TN>), hipFuncAttributeMaxDynamicSharedMemorySize, kBytes));
-        mark_on_device(attr_set);
-    }
+    if (const int rc = allow_dynamic_lds(&bneck64_tail_kernel<SC, TN>, kBytes, attr_set); rc != DVID_OK) return rc;
     const int lds_opt = g_opt.bneck_lds;          // diagnostics: less than the whole LDS (>= kBias + 4096)
     hipLaunchKernelGGL((bneck64_tail_kernel<SC, TN>), dim3(p.ntiles), dim3(512), lds_opt >= kBias + 4096 && lds_opt <= kBytes ? lds_opt : kBytes, s, p);
     LAUNCH_CHECK();
@@ -717,10 +714,7 @@ template <bool CONV2, bool TAIL>
 int bn128_launch(const Bneck128Params& p, hipStream_t s) {
     static_assert(k8Bytes <= 160 * 1024, "LDS");
     static std::atomic<unsigned long long> attr_set{0};          // one bit per device: the attribute belongs to (function, device)
-    if (first_on_device(attr_set)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bneck128_tail_kernel<CONV2, TAIL>), hipFuncAttributeMaxDynamicSharedMemorySize, k8Bytes));
-        mark_on_device(attr_set);
-    }
+    if (const int rc = allow_dynamic_lds(&bneck128_tail_kernel<CONV2, TAIL>, k8Bytes, attr_set); rc != DVID_OK) return rc;
     const int lds_opt = g_opt.bneck_lds;          // diagnostics: less than the whole LDS (>= k8Bias + 3072)
     hipLaunchKernelGGL((bneck128_tail_kernel<CONV2, TAIL>), dim3(p.ntiles), dim3(512), lds_opt >= k8Bias + 3072 && lds_opt <= k8Bytes ? lds_opt : k8Bytes, s, p);
     LAUNCH_CHECK();

@@ -47,6 +47,16 @@ static inline unsigned long long device_bit() {
 }
 static inline bool first_on_device(const std::atomic<unsigned long long>& mask) { return (mask.load(std::memory_order_acquire) & device_bit()) == 0; }
 static inline void mark_on_device(std::atomic<unsigned long long>& mask) { mask.fetch_or(device_bit(), std::memory_order_release); }
+// The two together: let `kernel` take `bytes` of dynamic LDS on the current device, once per device.  `mask` is the caller's
+// `static std::atomic<unsigned long long>` for that kernel (one per template instance).  Returns a DVID_* code.
+template <typename Kernel>
+static inline int allow_dynamic_lds(Kernel* kernel, int bytes, std::atomic<unsigned long long>& mask) {
+    if (first_on_device(mask)) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        mark_on_device(mask);
+    }
+    return DVID_OK;
+}
 
 static inline long ceil_div(long a, long b) { return (a + b - 1) / b; }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
@@ -109,6 +119,8 @@ __device__ __forceinline__ float2v gelu_erf2(float2v x) {
     const float2v phi = {x[0] >= 0.f ? head[0] : tail[0], x[1] >= 0.f ? head[1] : tail[1]};
     return x * phi;
 }
+// v_mfma_f32_32x32x2_f32: f32 in, f32 accumulate (the exact-fp32 kernels of csrc/f32.hip and csrc/dynconv.hip)
+__device__ __forceinline__ float16v mfma_f32(float a, float b, float16v c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

@@ -403,10 +403,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(IgemmParams p, int 
 
 int launch_c64(IgemmParams p, hipStream_t s) {
     static std::atomic<unsigned long long> attr_done{0};          // one bit per device: the attribute belongs to (function, device)
-    if (first_on_device(attr_done)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_c64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, C64_BYTES));
-        mark_on_device(attr_done);
-    }
+    if (const int rc = allow_dynamic_lds(&conv3x3_c64_kernel, C64_BYTES, attr_done); rc != DVID_OK) return rc;
     const int tiles_x = ceil_div(p.W, TW);
     p.tiles_m = tiles_x * ceil_div((p.M / (p.H * p.W)) * p.H, TH);
     p.tiles_n = 1;
@@ -702,10 +699,8 @@ template <int PH>
 int launch_stem_pool_k(IgemmParams p, hipStream_t s) {
     using C = StemPool<PH>;
     static std::atomic<unsigned long long> attr_done{0};
-    if (C::kBytes > 64 * 1024 && first_on_device(attr_done)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_pool_kernel<PH>), hipFuncAttributeMaxDynamicSharedMemorySize, C::kBytes));
-        mark_on_device(attr_done);
-    }
+    if (C::kBytes > 64 * 1024)
+        if (const int rc = allow_dynamic_lds(&stem_pool_kernel<PH>, C::kBytes, attr_done); rc != DVID_OK) return rc;
     const int n = p.M / (p.H * p.W);
     const int hp = (p.H + 2 - 3) / 2 + 1, wp = (p.W + 2 - 3) / 2 + 1;
     const int tiles_x = (int)ceil_div(wp, SP_PW), tiles_y = (int)ceil_div(hp, PH);
@@ -723,10 +718,7 @@ template <int BN, int WN>
 int launch(IgemmParams p, hipStream_t s) {
     using C = Halo<BN, WN>;
     static std::atomic<unsigned long long> attr_done{0};          // one bit per device: the attribute belongs to (function, device)
-    if (first_on_device(attr_done)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_kernel<BN, WN>), hipFuncAttributeMaxDynamicSharedMemorySize, C::kBytes));
-        mark_on_device(attr_done);
-    }
+    if (const int rc = allow_dynamic_lds(&conv3x3_halo_kernel<BN, WN>, C::kBytes, attr_done); rc != DVID_OK) return rc;
     const int tiles_x = ceil_div(p.W, TW), tiles_y = ceil_div((p.M / (p.H * p.W)) * p.H, TH);
     p.tiles_m = tiles_x * tiles_y;
     p.tiles_n = p.Cout / BN;

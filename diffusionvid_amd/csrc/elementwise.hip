@@ -484,3 +484,119 @@ int dvid_patch_merge_ln_launch(const float* x, const float* g, const float* b, h
     LAUNCH_CHECK();
     return DVID_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// DTYPE float32: the same kernels on fp32 storage (four values per lane)
+// ---------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// fp32 NCHW frames in [0, 1] (a table of per-frame pointers, as csrc/elementwise.hip) -> normalised fp32 NHWC4 (channel 3 zero).
+// (x - mean) / std as the reference's normalizer divides (diffusion_det.py:301-303).
+__global__ void f32_prep_images_kernel(FrameTable in, float* __restrict__ out, long npix, long hw, float m0, float m1, float m2, float s0,
+                                       float s1, float s2) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const long img = i / hw, pix = i - img * hw;
+    const float* q = in.p[img] + pix;
+    *reinterpret_cast<float4v*>(out + i * 4) = (float4v){(q[0] - m0) / s0, (q[hw] - m1) / s1, (q[2 * hw] - m2) / s2, 0.f};
+}
+
+__global__ void f32_maxpool_kernel(const float* __restrict__ in, float* __restrict__ out, int n, int h, int w, int c, int ho, int wo) {
+    const int cv = c >> 2;
+    const long total = (long)n * ho * wo * cv;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int v = i % cv;
+    long t = i / cv;
+    const int ox = t % wo;
+    t /= wo;
+    const int oy = t % ho;
+    const int img = t / ho;
+    float4v best = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy) {
+        const int iy = oy * 2 - 1 + dy;
+        if ((unsigned)iy >= (unsigned)h) continue;
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+            const int ix = ox * 2 - 1 + dx;
+            if ((unsigned)ix >= (unsigned)w) continue;
+            const float4v x = *reinterpret_cast<const float4v*>(in + (((long)img * h + iy) * w + ix) * c + v * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) best[e] = fmaxf(best[e], x[e]);
+        }
+    }
+    *reinterpret_cast<float4v*>(out + i * 4) = best;
+}
+
+__global__ void f32_silu_kernel(const float* __restrict__ x, float* __restrict__ y, long n4) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    const float4v v = *reinterpret_cast<const float4v*>(x + i * 4);
+    float4v o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = v[e] / (1.f + expf(-v[e]));
+    *reinterpret_cast<float4v*>(y + i * 4) = o;
+}
+
+// box_head.py:533-536 / :643-647: fc = x * (scale + 1) + shift
+__global__ void f32_modulate_kernel(const float* __restrict__ x, const float* __restrict__ scale, int scale_ld, const float* __restrict__ shift,
+                                    int shift_per_row, int shift_ld, float* __restrict__ y, long n4, int rows_per_frame, int d) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    const int dv = d >> 2;
+    const long row = i / dv;
+    const int col = (int)(i - row * dv) * 4;
+    const long frame = row / rows_per_frame;
+    const float4v v = *reinterpret_cast<const float4v*>(x + i * 4);
+    const float4v sc = *reinterpret_cast<const float4v*>(scale + frame * scale_ld + col);
+    const float4v sh = *reinterpret_cast<const float4v*>(shift + (shift_per_row ? row : frame) * shift_ld + col);
+    float4v o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = v[e] * (sc[e] + 1.f) + sh[e];
+    *reinterpret_cast<float4v*>(y + i * 4) = o;
+}
+
+}  // namespace
+
+int dvid_f32_prep_images_launch(const float* const* frames, float* nhwc4, int n, int h, int w, const float* mean, const float* std_,
+                                hipStream_t s) {
+    const long hw = (long)h * w;
+    for (int f0 = 0; f0 < n; f0 += FrameTable::kMax) {
+        const int nf = n - f0 < FrameTable::kMax ? n - f0 : FrameTable::kMax;
+        FrameTable tab;
+        for (int i = 0; i < FrameTable::kMax; ++i) tab.p[i] = frames[f0 + (i < nf ? i : 0)];
+        const long npix = hw * nf;
+        hipLaunchKernelGGL(f32_prep_images_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, tab, nhwc4 + (long)f0 * hw * 4, npix, hw,
+                           mean[0], mean[1], mean[2], std_[0], std_[1], std_[2]);
+        LAUNCH_CHECK();
+    }
+    return DVID_OK;
+}
+
+int dvid_f32_maxpool3x3s2_launch(const float* in, float* out, int n, int h, int w, int c, hipStream_t s) {
+    if (c % 4) return DVID_ERR_ARG;
+    const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
+    const long total = (long)n * ho * wo * (c / 4);
+    hipLaunchKernelGGL(f32_maxpool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, out, n, h, w, c, ho, wo);
+    LAUNCH_CHECK();
+    return DVID_OK;
+}
+
+int dvid_f32_silu_launch(const float* x, float* y, long n, hipStream_t s) {
+    if (n % 4) return DVID_ERR_ARG;
+    hipLaunchKernelGGL(f32_silu_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, x, y, n / 4);
+    LAUNCH_CHECK();
+    return DVID_OK;
+}
+
+int dvid_f32_modulate_launch(const float* x, const float* scale, int scale_ld, const float* shift, int shift_per_row, int shift_ld, float* y,
+                             int rows, int rows_per_frame, int d, hipStream_t s) {
+    if (d % 4) return DVID_ERR_ARG;
+    const long n4 = (long)rows * d / 4;
+    hipLaunchKernelGGL(f32_modulate_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, x, scale, scale_ld, shift, shift_per_row, shift_ld,
+                       y, n4, rows_per_frame, d);
+    LAUNCH_CHECK();
+    return DVID_OK;
+}

@@ -1,29 +1,28 @@
-// The DTYPE float32 path: fp32 storage end to end and exact fp32 products.
+// The DTYPE float32 path's implicit GEMM: fp32 storage end to end and fp32-grade products for every convolution and linear layer.
 //
 // The reference runs fp32 unless `DTYPE float16` is given (mega_core/config/defaults.py:582; tools/test_net.py:97-98 switches apex amp
 // on for float16 only).  The fp16 path of this library (igemm2 / conv3x3 / wstat / bneck / headtail / dynconv / attention) rounds every
 // stored activation and every weight to fp16 -- the apex O1 policy -- which is where its distance from an fp32 evaluation comes from
-// (profiles/r05_logit_error_stages.txt).  The kernels here keep every tensor in fp32 and multiply on v_mfma_f32_32x32x2_f32: f32 in,
-// f32 accumulate, bit-for-bit a k-ordered fmaf chain (MI355X_MICROARCH.md), 157 TFLOP/s dense peak = 1/16 of the fp16 MFMA rate.
-// They are deliberately plain -- one implicit-GEMM kernel for every convolution and linear layer, VALU kernels for the reductions --
-// because the mode exists for conformance (the fp32 CPU oracle's results to ~1e-5), not for the headline rate.
+// (profiles/r05_logit_error_stages.txt).  The float32 kernels keep every tensor in fp32.  The mode exists for conformance (the fp32 CPU
+// oracle's results to ~1e-5), not for the headline rate.
 //
 //   f32_igemm_kernel      conv / linear: NHWC fp32 in, [Cout][Kpad] fp32 weights, + bias, + residual (same shape or FPN nearest-x2
-//                         top-down), ReLU / exact GELU, fp32 out; 128 x BN x 16 tiles through LDS, 2 x 2 waves
-//   f32_roialign_kernel   detectron2 ROIPooler(ROIAlignV2) as called at box_head.py:507/:617 on fp32 pyramids (csrc/roialign.hip's walk)
-//   f32_mha_kernel        nn.MultiheadAttention's softmax(q k^T / sqrt(32)) v per head, one query per lane, keys through LDS
-//   f32_dynconv_kernel    DynamicConv.forward (box_head.py:687-711): two per-box products + LayerNorm + ReLU, one workgroup per box
-//   elementwise           image normaliser -> NHWC4, 3x3/2 max pool, SiLU, scale / shift modulation
+//                         top-down), ReLU / exact GELU, fp32 out; 128 x BN x 16 tiles through LDS, 2 x 2 waves, v_mfma_f32_32x32x2_f32:
+//                         f32 in, f32 accumulate, bit-for-bit a k-ordered fmaf chain (MI355X_MICROARCH.md), 1/16 of the fp16 MFMA rate
+//   f32x3_igemm_kernel    the same tiles on split (hi, lo) fp16 operands (csrc/f32_split.h), library option f32_split = 1 (the default)
+//   dvid_f32_igemm_launch picks between them and hands the shapes they take to csrc/f32_wstat.hip and csrc/f32_conv3x3.hip
+//
+// The float32 forms of the other kernels stand beside their fp16 siblings: csrc/elementwise.hip (image normaliser, max pool, SiLU,
+// modulation), csrc/roialign.hip, csrc/attention.hip (MHA, Swin window attention), csrc/dynconv.hip, csrc/localattn.hip.
 #include <stdlib.h>
 
 #include "common.h"
+#include "f32_split.h"
 #include "igemm_epilogue.h"
 #include "kernels.h"
 #include "options.h"
 
 namespace {
-
-__device__ __forceinline__ float16v mfma_f32(float a, float b, float16v c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // implicit GEMM.  D[m][n] = sum_k A[m][k] W[n][k]; A is the im2col view of the NHWC input (k = (ky * KW + kx) * Cin + c, Cin % 4 == 0),
@@ -324,12 +323,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BN == 128 ?
     auto split_store = [&](float4v v, bool ok, half_t* hi_row, half_t* lo_row) {
         if (!ok) v = (float4v){0.f, 0.f, 0.f, 0.f};
         // an activation beyond the fp16 range would become inf here where fp32 arithmetic would not: reported, never silent (the model
-        // checks the flag at the batch's host synchronisation and raises; f32_split = 0 has no such limit)
-        if (p.range_flag && fmaxf(fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])), fmaxf(__builtin_fabsf(v[2]), __builtin_fabsf(v[3]))) > 65504.f)
+        // checks the flag at the batch's host synchronisation and raises; f32_split = 0 has no such limit).  One test per chunk here.
+        if (p.range_flag && fmaxf(fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])), fmaxf(__builtin_fabsf(v[2]), __builtin_fabsf(v[3]))) > f32_split::kFp16Max)
             atomicOr(p.range_flag, 1);
-        const half4 h = __builtin_convertvector(v, half4);                     // round to nearest even
-        const float4v back = __builtin_convertvector(h, float4v);
-        const half4 l = __builtin_convertvector(v - back, half4);              // v - back is exact in fp32
+        half4 h, l;
+        f32_split::split4(v, h, l);
         *reinterpret_cast<half4*>(hi_row) = h;
         *reinterpret_cast<half4*>(lo_row) = l;
     };
@@ -374,19 +372,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BN == 128 ?
                 bh[nb] = *reinterpret_cast<const half8*>(Bhi + off);
                 bl[nb] = *reinterpret_cast<const half8*>(Blo + off);
             }
-            // the two small terms first, then the leading one (the accumulator is fp32 either way; the order is fixed)
+            // one pass over every tile, then the next (csrc/f32_split.h: the two small terms first, then the leading one)
 #pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
+            for (int pass = 0; pass < 3; ++pass)
 #pragma unroll
-                for (int nb = 0; nb < NB; ++nb) acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mb], bh[nb], acc[mb][nb], 0, 0, 0);
+                for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mb], bl[nb], acc[mb][nb], 0, 0, 0);
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mb], bh[nb], acc[mb][nb], 0, 0, 0);
+                    for (int nb = 0; nb < NB; ++nb) acc[mb][nb] = f32_split::mfma_pass<false>(pass, ah[mb], al[mb], bh[nb], bl[nb], acc[mb][nb]);
         }
         __syncthreads();                       // every wave has read this step's fragments
         if (kt + 1 < nk) {
@@ -395,829 +387,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BN == 128 ?
         }
     }
     f32_epilogue<BN>(p, acc, reinterpret_cast<float*>(Sm), m0, n0, wm, wn, lane, tid);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// elementwise
-// ---------------------------------------------------------------------------------------------------------------------------------
-// fp32 NCHW frames in [0, 1] (a table of per-frame pointers, as csrc/elementwise.hip) -> normalised fp32 NHWC4 (channel 3 zero).
-// (x - mean) / std as the reference's normalizer divides (diffusion_det.py:301-303).
-__global__ void f32_prep_images_kernel(FrameTable in, float* __restrict__ out, long npix, long hw, float m0, float m1, float m2, float s0,
-                                       float s1, float s2) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npix) return;
-    const long img = i / hw, pix = i - img * hw;
-    const float* q = in.p[img] + pix;
-    *reinterpret_cast<float4v*>(out + i * 4) = (float4v){(q[0] - m0) / s0, (q[hw] - m1) / s1, (q[2 * hw] - m2) / s2, 0.f};
-}
-
-__global__ void f32_maxpool_kernel(const float* __restrict__ in, float* __restrict__ out, int n, int h, int w, int c, int ho, int wo) {
-    const int cv = c >> 2;
-    const long total = (long)n * ho * wo * cv;
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int v = i % cv;
-    long t = i / cv;
-    const int ox = t % wo;
-    t /= wo;
-    const int oy = t % ho;
-    const int img = t / ho;
-    float4v best = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy) {
-        const int iy = oy * 2 - 1 + dy;
-        if ((unsigned)iy >= (unsigned)h) continue;
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-            const int ix = ox * 2 - 1 + dx;
-            if ((unsigned)ix >= (unsigned)w) continue;
-            const float4v x = *reinterpret_cast<const float4v*>(in + (((long)img * h + iy) * w + ix) * c + v * 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) best[e] = fmaxf(best[e], x[e]);
-        }
-    }
-    *reinterpret_cast<float4v*>(out + i * 4) = best;
-}
-
-__global__ void f32_silu_kernel(const float* __restrict__ x, float* __restrict__ y, long n4) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    const float4v v = *reinterpret_cast<const float4v*>(x + i * 4);
-    float4v o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = v[e] / (1.f + expf(-v[e]));
-    *reinterpret_cast<float4v*>(y + i * 4) = o;
-}
-
-// box_head.py:533-536 / :643-647: fc = x * (scale + 1) + shift
-__global__ void f32_modulate_kernel(const float* __restrict__ x, const float* __restrict__ scale, int scale_ld, const float* __restrict__ shift,
-                                    int shift_per_row, int shift_ld, float* __restrict__ y, long n4, int rows_per_frame, int d) {
-#pragma clang fp contract(off)
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    const int dv = d >> 2;
-    const long row = i / dv;
-    const int col = (int)(i - row * dv) * 4;
-    const long frame = row / rows_per_frame;
-    const float4v v = *reinterpret_cast<const float4v*>(x + i * 4);
-    const float4v sc = *reinterpret_cast<const float4v*>(scale + frame * scale_ld + col);
-    const float4v sh = *reinterpret_cast<const float4v*>(shift + (shift_per_row ? row : frame) * shift_ld + col);
-    float4v o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = v[e] * (sc[e] + 1.f) + sh[e];
-    *reinterpret_cast<float4v*>(y + i * 4) = o;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// RoIAlignV2 (aligned, 7 x 7 bins, 2 x 2 samples), fp32 pyramids: csrc/roialign.hip's kernel with fp32 taps -- one workgroup per box,
-// 32 lanes x 8 channels cover a tap's 256 channels, the 8 lane groups walk the 49 bins
-// ---------------------------------------------------------------------------------------------------------------------------------
-constexpr int RP = 7, RG = 2;
-
-struct Tap32 {
-    int lo, hi;
-    float wl, wh;
-    bool ok;
-};
-__device__ __forceinline__ Tap32 axis_tap32(float y, int limit) {          // torchvision bilinear_interpolate, one axis
-    Tap32 t;
-    t.ok = !(y < -1.0f || y > (float)limit);
-    if (y <= 0.f) y = 0.f;
-    int lo = (int)y;
-    int hi;
-    if (lo >= limit - 1) {
-        hi = lo = limit - 1;
-        y = (float)lo;
-    } else {
-        hi = lo + 1;
-    }
-    const float l = y - (float)lo;
-    t.lo = lo;
-    t.hi = hi;
-    t.wl = 1.f - l;
-    t.wh = l;
-    return t;
-}
-
-__global__ __launch_bounds__(256) void f32_roialign_kernel(RoiLevels32 lv, const float* __restrict__ boxes, int boxes_per_img,
-                                                            float* __restrict__ roi_out, float* __restrict__ mean_out, int nbox) {
-#pragma clang fp contract(off)
-    __shared__ float red[8][256];
-    const int box = igemm_xcd_remap((int)blockIdx.x, nbox);
-    const int img = box / boxes_per_img;
-    const int tid = threadIdx.x;
-    const int grp = tid >> 5, ln = tid & 31;
-    const float bx1 = boxes[box * 4 + 0], by1 = boxes[box * 4 + 1], bx2 = boxes[box * 4 + 2], by2 = boxes[box * 4 + 3];
-    const float area = (bx2 - bx1) * (by2 - by1);          // detectron2 assign_boxes_to_levels (canonical 224 / level 4, levels 3..5)
-    const bool valid_box = area >= 0.f;
-    float lvf = floorf(4.f + log2f(sqrtf(area) / 224.f + 1e-8f));
-    lvf = fminf(fmaxf(lvf, 3.f), 5.f);
-    const int level = valid_box ? (int)lvf - 3 : 0;
-    const int H = lv.h[level], W = lv.w[level];
-    const float sc = lv.scale[level];
-    const float* feat = lv.feat[level] + (long)img * H * W * 256;
-    const float x1 = bx1 * sc - 0.5f, y1 = by1 * sc - 0.5f;
-    const float x2 = bx2 * sc - 0.5f, y2 = by2 * sc - 0.5f;
-    const float bin_w = (x2 - x1) / RP, bin_h = (y2 - y1) / RP;
-    float macc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) macc[e] = 0.f;
-    for (int pb = grp; pb < RP * RP; pb += 8) {
-        const int ph = pb / RP, pw = pb - ph * RP;
-        float acc[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-        if (valid_box) {
-#pragma unroll
-            for (int iy = 0; iy < RG; ++iy) {
-                const float y = y1 + ph * bin_h + (iy + 0.5f) * bin_h / RG;
-                const Tap32 ty = axis_tap32(y, H);
-#pragma unroll
-                for (int ix = 0; ix < RG; ++ix) {
-                    const float x = x1 + pw * bin_w + (ix + 0.5f) * bin_w / RG;
-                    const Tap32 tx = axis_tap32(x, W);
-                    if (!(ty.ok && tx.ok)) continue;
-                    const float w4[4] = {ty.wl * tx.wl, ty.wl * tx.wh, ty.wh * tx.wl, ty.wh * tx.wh};
-                    const long o4[4] = {(long)ty.lo * W + tx.lo, (long)ty.lo * W + tx.hi, (long)ty.hi * W + tx.lo, (long)ty.hi * W + tx.hi};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float4v a = *reinterpret_cast<const float4v*>(feat + o4[q] * 256 + ln * 8);
-                        const float4v b = *reinterpret_cast<const float4v*>(feat + o4[q] * 256 + ln * 8 + 4);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            acc[e] += w4[q] * a[e];
-                            acc[4 + e] += w4[q] * b[e];
-                        }
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            acc[e] *= 1.f / (RG * RG);
-            macc[e] += acc[e];
-        }
-        float* o = roi_out + ((long)box * (RP * RP) + pb) * 256 + ln * 8;
-        *reinterpret_cast<float4v*>(o) = (float4v){acc[0], acc[1], acc[2], acc[3]};
-        *reinterpret_cast<float4v*>(o + 4) = (float4v){acc[4], acc[5], acc[6], acc[7]};
-    }
-    if (mean_out) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[grp][ln * 8 + e] = macc[e];
-        __syncthreads();
-        float s = 0.f;
-#pragma unroll
-        for (int g = 0; g < 8; ++g) s += red[g][tid];
-        mean_out[(long)box * 256 + tid] = s / (RP * RP);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// attention, head dim 32: out[b][q][h*32 ..] = softmax_k(q . k / sqrt(32)) v.  One query per lane (its 32 q values and 32 output
-// accumulators in registers), keys and values in chunks of 64 through LDS (every lane reads the same key: broadcast reads), the
-// running maximum / sum of the streaming softmax updated once per 16 keys.
-// ---------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void f32_mha_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                                                     float* __restrict__ out, int lq, int lk, int q_ld, int kv_ld, int out_ld, long q_bs,
-                                                     long kv_bs, long out_bs, float scale) {
-    __shared__ float Ks[64 * 32];
-    __shared__ float Vs[64 * 32];
-    const int tid = threadIdx.x, head = blockIdx.y, b = blockIdx.z;
-    const int qi = blockIdx.x * 64 + tid;
-    const bool live = qi < lq;
-    float qv[32], acc[32];
-    {
-        const float* qp = q + b * q_bs + (long)(live ? qi : 0) * q_ld + head * 32;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4v t = *reinterpret_cast<const float4v*>(qp + j * 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) qv[j * 4 + e] = t[e] * scale;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 32; ++e) acc[e] = 0.f;
-    float mx = -INFINITY, den = 0.f;
-    const float* kb = k + b * kv_bs + head * 32;
-    const float* vb = v + b * kv_bs + head * 32;
-    for (int k0 = 0; k0 < lk; k0 += 64) {
-        const int nk = lk - k0 < 64 ? lk - k0 : 64;
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {          // 64 keys x 8 float4: lane -> (key = (i * 64 + tid) / 8, quarter = .. % 8)
-            const int idx = i * 64 + tid, kr = idx >> 3, c4 = (idx & 7) * 4;
-            float4v kk = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-            if (kr < nk) {
-                kk = *reinterpret_cast<const float4v*>(kb + (long)(k0 + kr) * kv_ld + c4);
-                vv = *reinterpret_cast<const float4v*>(vb + (long)(k0 + kr) * kv_ld + c4);
-            }
-            *reinterpret_cast<float4v*>(&Ks[kr * 32 + c4]) = kk;
-            *reinterpret_cast<float4v*>(&Vs[kr * 32 + c4]) = vv;
-        }
-        __syncthreads();
-        // sub-chunks of 16 keys: scores into registers, one maximum / rescale per sub-chunk, then the weighted values
-#pragma unroll 1
-        for (int c0 = 0; c0 < nk; c0 += 16) {
-            float sc16[16];
-            float cmx = -INFINITY;
-#pragma unroll
-            for (int kk = 0; kk < 16; ++kk) {
-                float d = 0.f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float4v t = *reinterpret_cast<const float4v*>(&Ks[(c0 + kk) * 32 + j * 4]);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) d = __builtin_fmaf(qv[j * 4 + e], t[e], d);
-                }
-                sc16[kk] = c0 + kk < nk ? d : -INFINITY;
-                cmx = fmaxf(cmx, sc16[kk]);
-            }
-            const float nmx = fmaxf(mx, cmx);
-            const float rescale = expf(mx - nmx);          // first sub-chunk: exp(-inf) = 0 on zero accumulators
-            den *= rescale;
-#pragma unroll
-            for (int e = 0; e < 32; ++e) acc[e] *= rescale;
-            mx = nmx;
-#pragma unroll
-            for (int kk = 0; kk < 16; ++kk) {
-                const float pr = expf(sc16[kk] - mx);          // masked keys: exp(-inf) = 0
-                den += pr;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float4v t = *reinterpret_cast<const float4v*>(&Vs[(c0 + kk) * 32 + j * 4]);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[j * 4 + e] = __builtin_fmaf(pr, t[e], acc[j * 4 + e]);
-                }
-            }
-        }
-    }
-    if (live) {
-        const float inv = 1.f / den;
-        float* op = out + b * out_bs + (long)qi * out_ld + head * 32;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            *reinterpret_cast<float4v*>(op + j * 4) = (float4v){acc[j * 4] * inv, acc[j * 4 + 1] * inv, acc[j * 4 + 2] * inv, acc[j * 4 + 3] * inv};
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Swin window attention (swintransformer.py:68-176, :226-254), fp32: one workgroup (one wave) per (window, head), lane = query position of
-// the 7 x 7 window, keys and values through LDS.  A padded window position holds the qkv BIAS (the reference pads the normalised tokens
-// with zeros before the qkv Linear); the shifted map's region mask adds -100 between positions of different regions.
-// ---------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void f32_swin_window_attn_kernel(const float* __restrict__ qkv, const float* __restrict__ qkv_bias,
-                                                                  const float* __restrict__ relbias, float* __restrict__ out, int H, int W, int C,
-                                                                  int nheads, int shift, float scaling, int nwin) {
-    constexpr int WS = 7, NT = 49;
-    __shared__ float Ks[NT * 32];
-    __shared__ float Vs[NT * 32];
-    __shared__ int tok[64];
-    __shared__ int region[64];
-    const int tid = threadIdx.x;
-    const int lid = igemm_xcd_remap((int)blockIdx.x, nwin * nheads);
-    int wid = lid / nheads;
-    const int h = lid - wid * nheads;
-    const int Hp = (H + WS - 1) / WS * WS, Wp = (W + WS - 1) / WS * WS;
-    const int nwx = Wp / WS, nwy = Hp / WS;
-    const int wx = wid % nwx;
-    wid /= nwx;
-    const int wy = wid % nwy;
-    const int b = wid / nwy;
-    {
-        int t = -1, reg = 0;
-        if (tid < NT) {
-            const int py = tid / WS, px = tid - py * WS;
-            const int ys = wy * WS + py, xs = wx * WS + px;          // coordinates in the shifted, padded map
-            int y = ys + shift, x = xs + shift;                      // source coordinates before the roll
-            if (y >= Hp) y -= Hp;
-            if (x >= Wp) x -= Wp;
-            if (y < H && x < W) t = (b * H + y) * W + x;
-            if (shift > 0) {
-                const int hr = ys < Hp - WS ? 0 : (ys < Hp - shift ? 1 : 2);
-                const int wr = xs < Wp - WS ? 0 : (xs < Wp - shift ? 1 : 2);
-                reg = hr * 3 + wr;
-            }
-        }
-        tok[tid] = t;
-        region[tid] = reg;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < NT * 8; idx += 64) {
-        const int key = idx >> 3, c4 = (idx & 7) * 4;
-        const int t = tok[key];
-        const float* src = t >= 0 ? qkv + (long)t * 3 * C : qkv_bias;
-        *reinterpret_cast<float4v*>(&Ks[key * 32 + c4]) = *reinterpret_cast<const float4v*>(src + C + h * 32 + c4);
-        *reinterpret_cast<float4v*>(&Vs[key * 32 + c4]) = *reinterpret_cast<const float4v*>(src + 2 * C + h * 32 + c4);
-    }
-    const int qp = tid < NT ? tid : NT - 1;
-    const int tq = tok[qp], qreg = region[qp];
-    float qv[32];
-    {
-        const float* qsrc = (tq >= 0 ? qkv + (long)tq * 3 * C : qkv_bias) + h * 32;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4v t = *reinterpret_cast<const float4v*>(qsrc + j * 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) qv[j * 4 + e] = t[e] * scaling;
-        }
-    }
-    __syncthreads();
-    const float* brow = relbias + ((long)h * NT + qp) * SWIN_RELBIAS_PITCH;
-    float sc[NT];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int key = 0; key < NT; ++key) {
-        float d = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4v t = *reinterpret_cast<const float4v*>(&Ks[key * 32 + j * 4]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) d = __builtin_fmaf(qv[j * 4 + e], t[e], d);
-        }
-        d += brow[key];
-        if (shift > 0 && region[key] != qreg) d += -100.0f;
-        sc[key] = d;
-        mx = fmaxf(mx, d);
-    }
-    float acc[32];
-#pragma unroll
-    for (int e = 0; e < 32; ++e) acc[e] = 0.f;
-    float den = 0.f;
-#pragma unroll
-    for (int key = 0; key < NT; ++key) {
-        const float pr = expf(sc[key] - mx);
-        den += pr;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4v t = *reinterpret_cast<const float4v*>(&Vs[key * 32 + j * 4]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[j * 4 + e] = __builtin_fmaf(pr, t[e], acc[j * 4 + e]);
-        }
-    }
-    if (tid < NT && tq >= 0) {          // padded positions produce no output
-        const float inv = 1.f / den;
-        float* op = out + (long)tq * C + h * 32;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            *reinterpret_cast<float4v*>(op + j * 4) = (float4v){acc[j * 4] * inv, acc[j * 4 + 1] * inv, acc[j * 4 + 2] * inv, acc[j * 4 + 3] * inv};
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// The same with 12 x 12 windows (144 tokens, shift 0 or 6).  One query per lane of one wave no longer covers a window, and 144 scores
-// per lane would not stay in registers: a workgroup is nine waves (576 threads) for one (window, head), FOUR lanes per query, lane
-// `part` of a query taking keys part, part + 4, ... (36 scores per lane).  The four partial maxima, sums and 32-float accumulators meet
-// in two xor-shuffles inside the quad; lane 0 of the quad writes the row.  K and V rows have a pitch of 36 floats (2 x 20.25 KB of
-// LDS): the four rows a quad reads in one ds_read_b128 start 36 banks apart, conflict-free.
-// ---------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(576) void f32_swin_window12_attn_kernel(const float* __restrict__ qkv, const float* __restrict__ qkv_bias,
-                                                                     const float* __restrict__ relbias, float* __restrict__ out, int H, int W, int C,
-                                                                     int nheads, int shift, float scaling, int nwin) {
-    constexpr int WS = 12, NT = 144, KP = 36, NPART = 4, NS = NT / NPART;
-    __shared__ __attribute__((aligned(16))) float Ks[NT * KP];
-    __shared__ __attribute__((aligned(16))) float Vs[NT * KP];
-    __shared__ int tok[NT];
-    __shared__ int region[NT];
-    const int tid = threadIdx.x;
-    const int lid = igemm_xcd_remap((int)blockIdx.x, nwin * nheads);
-    int wid = lid / nheads;
-    const int h = lid - wid * nheads;
-    const int Hp = (H + WS - 1) / WS * WS, Wp = (W + WS - 1) / WS * WS;
-    const int nwx = Wp / WS, nwy = Hp / WS;
-    const int wx = wid % nwx;
-    wid /= nwx;
-    const int wy = wid % nwy;
-    const int b = wid / nwy;
-    if (tid < NT) {
-        const int py = tid / WS, px = tid - py * WS;
-        const int ys = wy * WS + py, xs = wx * WS + px;          // coordinates in the shifted, padded map
-        int y = ys + shift, x = xs + shift;                      // source coordinates before the roll
-        if (y >= Hp) y -= Hp;
-        if (x >= Wp) x -= Wp;
-        int reg = 0;
-        if (shift > 0) {
-            const int hr = ys < Hp - WS ? 0 : (ys < Hp - shift ? 1 : 2);
-            const int wr = xs < Wp - WS ? 0 : (xs < Wp - shift ? 1 : 2);
-            reg = hr * 3 + wr;
-        }
-        tok[tid] = (y < H && x < W) ? (b * H + y) * W + x : -1;
-        region[tid] = reg;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < NT * 8; idx += 576) {
-        const int key = idx >> 3, c4 = (idx & 7) * 4;
-        const int t = tok[key];
-        const float* src = t >= 0 ? qkv + (long)t * 3 * C : qkv_bias;
-        *reinterpret_cast<float4v*>(&Ks[key * KP + c4]) = *reinterpret_cast<const float4v*>(src + C + h * 32 + c4);
-        *reinterpret_cast<float4v*>(&Vs[key * KP + c4]) = *reinterpret_cast<const float4v*>(src + 2 * C + h * 32 + c4);
-    }
-    const int qp = tid >> 2, part = tid & 3;                     // query position (< 144) and which quarter of its keys
-    const int tq = tok[qp], qreg = region[qp];
-    float qv[32];
-    {
-        const float* qsrc = (tq >= 0 ? qkv + (long)tq * 3 * C : qkv_bias) + h * 32;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4v t = *reinterpret_cast<const float4v*>(qsrc + j * 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) qv[j * 4 + e] = t[e] * scaling;
-        }
-    }
-    __syncthreads();
-    const float* brow = relbias + ((long)h * NT + qp) * SWIN12_RELBIAS_PITCH + part;
-    float sc[NS];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        const int key = i * NPART + part;
-        float d = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4v t = *reinterpret_cast<const float4v*>(&Ks[key * KP + j * 4]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) d = __builtin_fmaf(qv[j * 4 + e], t[e], d);
-        }
-        d += brow[i * NPART];
-        if (shift > 0 && region[key] != qreg) d += -100.0f;
-        sc[i] = d;
-        mx = fmaxf(mx, d);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
-    float acc[32];
-#pragma unroll
-    for (int e = 0; e < 32; ++e) acc[e] = 0.f;
-    float den = 0.f;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        const int key = i * NPART + part;
-        const float pr = expf(sc[i] - mx);
-        den += pr;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4v t = *reinterpret_cast<const float4v*>(&Vs[key * KP + j * 4]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[j * 4 + e] = __builtin_fmaf(pr, t[e], acc[j * 4 + e]);
-        }
-    }
-    den += __shfl_xor(den, 1, 64);
-    den += __shfl_xor(den, 2, 64);
-#pragma unroll
-    for (int e = 0; e < 32; ++e) {
-        acc[e] += __shfl_xor(acc[e], 1, 64);
-        acc[e] += __shfl_xor(acc[e], 2, 64);
-    }
-    if (part == 0 && tq >= 0) {         // padded positions produce no output
-        const float inv = 1.f / den;
-        float* op = out + (long)tq * C + h * 32;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            *reinterpret_cast<float4v*>(op + j * 4) = (float4v){acc[j * 4] * inv, acc[j * 4 + 1] * inv, acc[j * 4 + 2] * inv, acc[j * 4 + 3] * inv};
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// DynamicConv (box_head.py:687-711), one workgroup per box: F1 = roi[49 x 256] . param1[256 x 64] -> LayerNorm(64) + ReLU ->
-// F2 = F1 . param2[64 x 256] -> LayerNorm(256) + ReLU -> out[49 x 256].  The per-box parameters arrive as P1T[64][256] | P2T[256][64]
-// ([N][K] rows, the row order csrc/weights.hip gives dynamic_layer), so both MFMA operands are K-contiguous rows read straight from
-// global as float4 fragments; F1 / F2 cross LDS for the row statistics.
-// ---------------------------------------------------------------------------------------------------------------------------------
-constexpr int DC_P1 = 68, DC_P2 = 260;
-// (two workgroups per CU: left to itself the compiler takes 200 VGPRs + 64 AGPRs, over the 256 a wave may have at two waves per SIMD, and
-// a box's loads, products and LayerNorms then run strictly one after the other on the CU)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void f32_dynconv_kernel(const float* __restrict__ roi, const float* __restrict__ params,
-                                                           const float* __restrict__ g1, const float* __restrict__ b1,
-                                                           const float* __restrict__ g2, const float* __restrict__ b2, float* __restrict__ out,
-                                                           int nbox) {
-#pragma clang fp contract(off)
-    __shared__ float F1[64 * DC_P1];
-    __shared__ float F2[49 * DC_P2];
-    const int box = igemm_xcd_remap((int)blockIdx.x, nbox);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int fr = lane & 31, fk = (lane >> 5) * 4;
-    const float* x = roi + (long)box * 49 * 256;
-    const float* p1 = params + (long)box * 32768;
-    const float* p2 = p1 + 64 * 256;
-
-    // the second product's parameter fragments are requested first: they land under the first product
-    float4v w2[2][8];
-#pragma unroll
-    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) w2[nb][j] = *reinterpret_cast<const float4v*>(p2 + (long)((wave * 2 + nb) * 32 + fr) * 64 + j * 8 + fk);
-
-    // ---- product 1: wave = (row block mb, column block nb) of the 64 x 64 result, K = 256 in four chunks of 64
-    {
-        const int mb = wave >> 1, nb = wave & 1;
-        const int prow = mb * 32 + fr;
-        const bool pok = prow < 49;
-        const float* ap = x + (long)(pok ? prow : 0) * 256 + fk;
-        const float* bp = p1 + (long)(nb * 32 + fr) * 256 + fk;
-        float16v acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        float4v a[2][8], b[2][8];
-        auto fetch = [&](int c, int buf) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                a[buf][j] = pok ? *reinterpret_cast<const float4v*>(ap + c * 64 + j * 8) : (float4v){0.f, 0.f, 0.f, 0.f};
-                b[buf][j] = *reinterpret_cast<const float4v*>(bp + c * 64 + j * 8);
-            }
-        };
-        fetch(0, 0);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if (c + 1 < 4) fetch(c + 1, (c + 1) & 1);
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = mfma_f32(a[c & 1][j][e], b[c & 1][j][e], acc);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) F1[(mb * 32 + (r >> 2) * 8 + (lane >> 5) * 4 + (r & 3)) * DC_P1 + nb * 32 + fr] = acc[r];
-    }
-    __syncthreads();
-    // ---- LayerNorm(64) + ReLU on rows 0..48: four lanes per row, 16 values each
-    if (tid < 49 * 4) {
-        const int row = tid >> 2, part = tid & 3;
-        float* rp = &F1[row * DC_P1 + part * 16];
-        float vals[16], sum = 0.f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            vals[e] = rp[e];
-            sum += vals[e];
-        }
-        sum += __shfl_xor(sum, 1, 64);
-        sum += __shfl_xor(sum, 2, 64);
-        const float mean = sum / 64.f;
-        float sq = 0.f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const float t = vals[e] - mean;
-            sq += t * t;
-        }
-        sq += __shfl_xor(sq, 1, 64);
-        sq += __shfl_xor(sq, 2, 64);
-        const float rstd = rsqrtf(sq / 64.f + 1e-5f);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) rp[e] = fmaxf((vals[e] - mean) * rstd * g1[part * 16 + e] + b1[part * 16 + e], 0.f);
-    }
-    __syncthreads();
-    // ---- product 2: wave w owns columns [64 w, 64 w + 64) of the 64 x 256 result, K = 64
-    {
-        float16v acc[2][2];
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mb][nb][r] = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float4v a[2];
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb) a[mb] = *reinterpret_cast<const float4v*>(&F1[(mb * 32 + fr) * DC_P1 + j * 8 + fk]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb) acc[mb][nb] = mfma_f32(a[mb][e], w2[nb][j][e], acc[mb][nb]);
-        }
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = mb * 32 + (r >> 2) * 8 + (lane >> 5) * 4 + (r & 3);
-                    if (row < 49) F2[row * DC_P2 + (wave * 2 + nb) * 32 + fr] = acc[mb][nb][r];
-                }
-    }
-    __syncthreads();
-    // ---- LayerNorm(256) + ReLU, one wave per row, 4 values per lane; rows go straight to global
-    const float4v gg = *reinterpret_cast<const float4v*>(g2 + lane * 4);
-    const float4v bb = *reinterpret_cast<const float4v*>(b2 + lane * 4);
-    for (int row = wave; row < 49; row += 4) {
-        const float4v t = *reinterpret_cast<const float4v*>(&F2[row * DC_P2 + lane * 4]);
-        const float mean = wave_sum(t[0] + t[1] + t[2] + t[3]) / 256.f;
-        float sq = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float u = t[e] - mean;
-            sq += u * u;
-        }
-        const float rstd = rsqrtf(wave_sum(sq) / 256.f + 1e-5f);
-        float4v o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = fmaxf((t[e] - mean) * rstd * gg[e] + bb[e], 0.f);
-        *reinterpret_cast<float4v*>(out + ((long)box * 49 + row) * 256 + lane * 4) = o;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// The same per-box pipeline with SPLIT operands (library option f32_split = 1, the default): both products run as three passes of the
-// fp16 MFMA on (hi, lo) halves of the fp32 values -- the arithmetic of f32x3_igemm_kernel: lo_a hi_b + hi_a lo_b + hi_a hi_b, fp32
-// accumulation -- instead of 256 fp32-MFMA instructions of 64 cycles per wave and box.  Each wave splits the fragments it multiplies, in
-// registers, straight from the global loads; product 1 is split over K across the four waves (see the kernel), its partial sums and
-// F1 cross LDS as fp32 for the LayerNorm statistics, and F1 comes back as two fp16 planes (rows of 64 halves at a pitch of 72:
-// conflict-free ds_read_b128 fragments) over the same bytes.
-// LayerNorm / ReLU arithmetic is the fp32 kernel's.  |value| > 65504 in the RoI tile or the parameters sets `range_flag`.
-// ---------------------------------------------------------------------------------------------------------------------------------
-constexpr int DX_PH = 72;          // halves per F1 plane row
-__device__ __forceinline__ void split8(const float4v v0, const float4v v1, half8& h, half8& l, float& mx) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) mx = fmaxf(mx, fmaxf(__builtin_fabsf(v0[e]), __builtin_fabsf(v1[e])));
-    const half4 h0 = __builtin_convertvector(v0, half4), h1 = __builtin_convertvector(v1, half4);          // round to nearest even
-    const half4 l0 = __builtin_convertvector(v0 - __builtin_convertvector(h0, float4v), half4);            // v - hi is exact in fp32
-    const half4 l1 = __builtin_convertvector(v1 - __builtin_convertvector(h1, float4v), half4);
-    h = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-    l = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-__device__ __forceinline__ float16v mfma_x3(const half8 ah, const half8 al, const half8 bh, const half8 bl, float16v acc) {
-    // the two small terms first, then the leading one: f32x3_igemm_kernel's order
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
-}
-
-__global__ __launch_bounds__(256) void f32x3_dynconv_kernel(const float* __restrict__ roi, const float* __restrict__ params,
-                                                             const float* __restrict__ g1, const float* __restrict__ b1,
-                                                             const float* __restrict__ g2, const float* __restrict__ b2, float* __restrict__ out,
-                                                             int nbox, int* __restrict__ range_flag) {
-#pragma clang fp contract(off)
-    // LDS: product 1's four K-quarter partial sums [4][64][68] fp32 (69632 bytes); afterwards the same bytes hold F1 as two fp16 planes
-    // (18432) and, behind them, F2 [49][260] fp32
-    constexpr int PART = 64 * DC_P1;                      // floats per partial
-    constexpr int F1_BYTES = 2 * 64 * DX_PH * 2;
-    constexpr int LDS_BYTES = 4 * PART * 4 > F1_BYTES + 49 * DC_P2 * 4 ? 4 * PART * 4 : F1_BYTES + 49 * DC_P2 * 4;
-    __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
-    float* const P = reinterpret_cast<float*>(lds);
-    half_t* const F1h = reinterpret_cast<half_t*>(lds);
-    half_t* const F1l = F1h + 64 * DX_PH;
-    float* const F2 = reinterpret_cast<float*>(lds + F1_BYTES);
-    const int box = igemm_xcd_remap((int)blockIdx.x, nbox);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int fr = lane & 31, fk = (lane >> 5) * 8;          // fp16 MFMA operand map: lane l = row l & 31, k = 8 (l >> 5) .. + 8 of a 16-deep step
-    const float* x = roi + (long)box * 49 * 256;
-    const float* p1 = params + (long)box * 32768;
-    const float* p2 = p1 + 64 * 256;
-    float mx = 0.f;
-
-    // ---- product 1, split over K: wave w multiplies k in [64 w, 64 w + 64) for the whole 64 x 64 result.  Every RoI / parameter value is
-    // loaded by exactly one lane, and ALL of a box's 114 KB of first-product operands are requested before the first one is used (the
-    // (row block, column block) split of the fp32 kernel double-buffers 64-deep chunks: ~32 KB in flight per workgroup, which is what
-    // paced it -- 2.4-2.6 TB/s with either MFMA).
-    float16v acc[2][2];
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mb][nb][r] = 0.f;
-    {
-        float4v a[2][4][2], b[2][4][2];
-        const bool pok = 32 + fr < 49;          // row block 1 holds rows 32..48
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int k = 64 * wave + 16 * ks + fk + 4 * h;
-                a[0][ks][h] = *reinterpret_cast<const float4v*>(x + (long)fr * 256 + k);
-                a[1][ks][h] = pok ? *reinterpret_cast<const float4v*>(x + (long)(32 + fr) * 256 + k) : (float4v){0.f, 0.f, 0.f, 0.f};
-                b[0][ks][h] = *reinterpret_cast<const float4v*>(p1 + (long)fr * 256 + k);
-                b[1][ks][h] = *reinterpret_cast<const float4v*>(p1 + (long)(32 + fr) * 256 + k);
-            }
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            half8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                split8(a[i][ks][0], a[i][ks][1], ah[i], al[i], mx);
-                split8(b[i][ks][0], b[i][ks][1], bh[i], bl[i], mx);
-            }
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb) acc[mb][nb] = mfma_x3(ah[mb], al[mb], bh[nb], bl[nb], acc[mb][nb]);
-        }
-    }
-    // the second product's parameter fragments (raw fp32; wave w owns columns [64 w, 64 w + 64)): requested now, they land under the
-    // reduction and the LayerNorm below
-    float4v w2[2][4][2];
-#pragma unroll
-    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const float* q = p2 + (long)((wave * 2 + nb) * 32 + fr) * 64 + ks * 16 + fk;
-            w2[nb][ks][0] = *reinterpret_cast<const float4v*>(q);
-            w2[nb][ks][1] = *reinterpret_cast<const float4v*>(q + 4);
-        }
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                P[wave * PART + (mb * 32 + (r >> 2) * 8 + (lane >> 5) * 4 + (r & 3)) * DC_P1 + nb * 32 + fr] = acc[mb][nb][r];
-    __syncthreads();
-    // ---- the four partial sums in a fixed order, LayerNorm(64) + ReLU on rows 0..48: four lanes per row, 16 values each; the result goes
-    // back as (hi, lo) planes, rows 49..63 zero
-    {
-        const int row = tid >> 2, part = tid & 3;
-        float vals[16];
-        if (row < 49) {
-            const float* rp = &P[row * DC_P1 + part * 16];
-            float sum = 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                vals[e] = (rp[e] + rp[PART + e]) + (rp[2 * PART + e] + rp[3 * PART + e]);
-                sum += vals[e];
-            }
-            sum += __shfl_xor(sum, 1, 64);
-            sum += __shfl_xor(sum, 2, 64);
-            const float mean = sum / 64.f;
-            float sq = 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const float t = vals[e] - mean;
-                sq += t * t;
-            }
-            sq += __shfl_xor(sq, 1, 64);
-            sq += __shfl_xor(sq, 2, 64);
-            const float rstd = rsqrtf(sq / 64.f + 1e-5f);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) vals[e] = fmaxf((vals[e] - mean) * rstd * g1[part * 16 + e] + b1[part * 16 + e], 0.f);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) vals[e] = 0.f;
-        }
-        __syncthreads();          // every partial sum has been read
-        float unused = 0.f;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            half8 vh, vl;
-            split8((float4v){vals[8 * h], vals[8 * h + 1], vals[8 * h + 2], vals[8 * h + 3]},
-                   (float4v){vals[8 * h + 4], vals[8 * h + 5], vals[8 * h + 6], vals[8 * h + 7]}, vh, vl, unused);
-            *reinterpret_cast<half8*>(F1h + row * DX_PH + part * 16 + 8 * h) = vh;
-            *reinterpret_cast<half8*>(F1l + row * DX_PH + part * 16 + 8 * h) = vl;
-        }
-    }
-    __syncthreads();
-    // ---- product 2: wave w owns columns [64 w, 64 w + 64) of the 64 x 256 result, K = 64
-    {
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mb][nb][r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            half8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb) {
-                ah[mb] = *reinterpret_cast<const half8*>(F1h + (mb * 32 + fr) * DX_PH + ks * 16 + fk);
-                al[mb] = *reinterpret_cast<const half8*>(F1l + (mb * 32 + fr) * DX_PH + ks * 16 + fk);
-            }
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb) split8(w2[nb][ks][0], w2[nb][ks][1], bh[nb], bl[nb], mx);
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb) acc[mb][nb] = mfma_x3(ah[mb], al[mb], bh[nb], bl[nb], acc[mb][nb]);
-        }
-        // (F2 lies behind the planes: no wave's fragment reads are disturbed by another wave's results)
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = mb * 32 + (r >> 2) * 8 + (lane >> 5) * 4 + (r & 3);
-                    if (row < 49) F2[row * DC_P2 + (wave * 2 + nb) * 32 + fr] = acc[mb][nb][r];
-                }
-    }
-    if (range_flag && mx > 65504.f) atomicOr(range_flag, 1);          // reported, never a silent inf (f32_split = 0 has no such limit)
-    __syncthreads();
-    // ---- LayerNorm(256) + ReLU, one wave per row, 4 values per lane; rows go straight to global
-    const float4v gg = *reinterpret_cast<const float4v*>(g2 + lane * 4);
-    const float4v bb = *reinterpret_cast<const float4v*>(b2 + lane * 4);
-    for (int row = wave; row < 49; row += 4) {
-        const float4v t = *reinterpret_cast<const float4v*>(&F2[row * DC_P2 + lane * 4]);
-        const float mean = wave_sum(t[0] + t[1] + t[2] + t[3]) / 256.f;
-        float sq = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float u = t[e] - mean;
-            sq += u * u;
-        }
-        const float rstd = rsqrtf(wave_sum(sq) / 256.f + 1e-5f);
-        float4v o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = fmaxf((t[e] - mean) * rstd * gg[e] + bb[e], 0.f);
-        *reinterpret_cast<float4v*>(out + ((long)box * 49 + row) * 256 + lane * 4) = o;
-    }
 }
 
 }  // namespace
@@ -1263,100 +432,6 @@ int dvid_f32_igemm_launch(const F32GemmParams& p0, hipStream_t s) {
         if (split) hipLaunchKernelGGL(f32x3_igemm_kernel<128>, dim3(p.tiles_m * p.tiles_n), dim3(256), 0, s, p);
         else hipLaunchKernelGGL(f32_igemm_kernel<128>, dim3(p.tiles_m * p.tiles_n), dim3(256), 0, s, p);
     }
-    LAUNCH_CHECK();
-    return DVID_OK;
-}
-
-int dvid_f32_prep_images_launch(const float* const* frames, float* nhwc4, int n, int h, int w, const float* mean, const float* std_,
-                                hipStream_t s) {
-    const long hw = (long)h * w;
-    for (int f0 = 0; f0 < n; f0 += FrameTable::kMax) {
-        const int nf = n - f0 < FrameTable::kMax ? n - f0 : FrameTable::kMax;
-        FrameTable tab;
-        for (int i = 0; i < FrameTable::kMax; ++i) tab.p[i] = frames[f0 + (i < nf ? i : 0)];
-        const long npix = hw * nf;
-        hipLaunchKernelGGL(f32_prep_images_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, tab, nhwc4 + (long)f0 * hw * 4, npix, hw,
-                           mean[0], mean[1], mean[2], std_[0], std_[1], std_[2]);
-        LAUNCH_CHECK();
-    }
-    return DVID_OK;
-}
-
-int dvid_f32_maxpool3x3s2_launch(const float* in, float* out, int n, int h, int w, int c, hipStream_t s) {
-    if (c % 4) return DVID_ERR_ARG;
-    const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
-    const long total = (long)n * ho * wo * (c / 4);
-    hipLaunchKernelGGL(f32_maxpool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, out, n, h, w, c, ho, wo);
-    LAUNCH_CHECK();
-    return DVID_OK;
-}
-
-int dvid_f32_silu_launch(const float* x, float* y, long n, hipStream_t s) {
-    if (n % 4) return DVID_ERR_ARG;
-    hipLaunchKernelGGL(f32_silu_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, x, y, n / 4);
-    LAUNCH_CHECK();
-    return DVID_OK;
-}
-
-int dvid_f32_modulate_launch(const float* x, const float* scale, int scale_ld, const float* shift, int shift_per_row, int shift_ld, float* y,
-                             int rows, int rows_per_frame, int d, hipStream_t s) {
-    if (d % 4) return DVID_ERR_ARG;
-    const long n4 = (long)rows * d / 4;
-    hipLaunchKernelGGL(f32_modulate_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, x, scale, scale_ld, shift, shift_per_row, shift_ld,
-                       y, n4, rows_per_frame, d);
-    LAUNCH_CHECK();
-    return DVID_OK;
-}
-
-int dvid_f32_roialign_launch(const RoiLevels32& lv, int channels, const float* boxes, int n_img, int boxes_per_img, float* roi_out,
-                             float* mean_out, hipStream_t s) {
-    if (channels != 256) return DVID_ERR_UNSUPPORTED;
-    const int nbox = n_img * boxes_per_img;
-    if (nbox == 0) return DVID_OK;
-    hipLaunchKernelGGL(f32_roialign_kernel, dim3(nbox), dim3(256), 0, s, lv, boxes, boxes_per_img, roi_out, mean_out, nbox);
-    LAUNCH_CHECK();
-    return DVID_OK;
-}
-
-int dvid_f32_mha_launch(const float* q, const float* k, const float* v, float* out, int batch, int lq, int lk, int nheads, int q_ld, int kv_ld,
-                        int out_ld, long q_bs, long kv_bs, long out_bs, hipStream_t s) {
-    if (batch <= 0 || lq <= 0) return DVID_OK;
-    if (lk <= 0 || nheads <= 0 || (q_ld | kv_ld | out_ld) % 4) return DVID_ERR_ARG;
-    hipLaunchKernelGGL(f32_mha_kernel, dim3(ceil_div(lq, 64), nheads, batch), dim3(64), 0, s, q, k, v, out, lq, lk, q_ld, kv_ld, out_ld, q_bs, kv_bs,
-                       out_bs, 0.17677669529663688110f);          // 1 / sqrt(32)
-    LAUNCH_CHECK();
-    return DVID_OK;
-}
-
-int dvid_f32_swin_window_attn_launch(const float* qkv, const float* qkv_bias, const float* relbias, float* out, int batch, int H, int W, int C,
-                                     int nheads, int shift, hipStream_t s) {
-    if (C != nheads * 32) return DVID_ERR_UNSUPPORTED;
-    const long nwin = (long)batch * ((H + 6) / 7) * ((W + 6) / 7);
-    if (nwin * nheads > 0x7fffffffL) return DVID_ERR_UNSUPPORTED;
-    if (nwin == 0) return DVID_OK;
-    hipLaunchKernelGGL(f32_swin_window_attn_kernel, dim3((unsigned)(nwin * nheads)), dim3(64), 0, s, qkv, qkv_bias, relbias, out, H, W, C, nheads, shift,
-                       0.17677669529663688110f, (int)nwin);
-    LAUNCH_CHECK();
-    return DVID_OK;
-}
-
-int dvid_f32_swin_window12_attn_launch(const float* qkv, const float* qkv_bias, const float* relbias, float* out, int batch, int H, int W, int C,
-                                       int nheads, int shift, hipStream_t s) {
-    if (C != nheads * 32) return DVID_ERR_UNSUPPORTED;
-    const long nwin = (long)batch * ((H + 11) / 12) * ((W + 11) / 12);
-    if (nwin * nheads > 0x7fffffffL) return DVID_ERR_UNSUPPORTED;
-    if (nwin == 0) return DVID_OK;
-    hipLaunchKernelGGL(f32_swin_window12_attn_kernel, dim3((unsigned)(nwin * nheads)), dim3(576), 0, s, qkv, qkv_bias, relbias, out, H, W, C, nheads,
-                       shift, 0.17677669529663688110f, (int)nwin);
-    LAUNCH_CHECK();
-    return DVID_OK;
-}
-
-int dvid_f32_dynconv_launch(const float* roi, const float* params, const float* g1, const float* b1, const float* g2, const float* b2,
-                            float* out, int rows, int* range_flag, hipStream_t s) {
-    if (rows <= 0) return DVID_OK;
-    if (g_opt.f32_split != 0) hipLaunchKernelGGL(f32x3_dynconv_kernel, dim3(rows), dim3(256), 0, s, roi, params, g1, b1, g2, b2, out, rows, range_flag);
-    else hipLaunchKernelGGL(f32_dynconv_kernel, dim3(rows), dim3(256), 0, s, roi, params, g1, b1, g2, b2, out, rows);
     LAUNCH_CHECK();
     return DVID_OK;
 }

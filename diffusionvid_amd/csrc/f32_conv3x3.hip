@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "f32_split.h"
 #include "igemm_epilogue.h"
 #include "kernels.h"
 #include "options.h"
@@ -95,8 +96,8 @@ __global__ __launch_bounds__(512) void f32x3_conv3x3_kernel(F32GemmParams p, int
             if (!hok[i]) v = (float4v){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int e = 0; e < 4; ++e) range_max = fmaxf(range_max, __builtin_fabsf(v[e]));
-            const half4 h = __builtin_convertvector(v, half4);                                        // round to nearest even
-            const half4 l = __builtin_convertvector(v - __builtin_convertvector(h, float4v), half4);   // v - hi is exact in fp32
+            half4 h, l;
+            f32_split::split4(v, h, l);
             if (hin[i]) {
                 *reinterpret_cast<half4*>(Hhi + hdst[i]) = h;
                 *reinterpret_cast<half4*>(Hlo + hdst[i]) = l;
@@ -195,19 +196,13 @@ __global__ __launch_bounds__(512) void f32x3_conv3x3_kernel(F32GemmParams p, int
                         wh[nb] = *reinterpret_cast<const half8*>(bh + off);
                         wl[nb] = *reinterpret_cast<const half8*>(bl + off);
                     }
-                    // the two small terms first, then the leading one (f32x3_igemm_kernel's order)
+                    // one pass over every tile, then the next (f32x3_igemm_kernel's order)
 #pragma unroll
-                    for (int mb = 0; mb < 2; ++mb)
+                    for (int pass = 0; pass < 3; ++pass)
 #pragma unroll
-                        for (int nb = 0; nb < NB; ++nb) acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mb], wh[nb], acc[mb][nb], 0, 0, 0);
+                        for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
-                    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                        for (int nb = 0; nb < NB; ++nb) acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mb], wl[nb], acc[mb][nb], 0, 0, 0);
-#pragma unroll
-                    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                        for (int nb = 0; nb < NB; ++nb) acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mb], wh[nb], acc[mb][nb], 0, 0, 0);
+                            for (int nb = 0; nb < NB; ++nb) acc[mb][nb] = f32_split::mfma_pass<false>(pass, ah[mb], al[mb], wh[nb], wl[nb], acc[mb][nb]);
                 }
             }
         }
@@ -220,7 +215,7 @@ __global__ __launch_bounds__(512) void f32x3_conv3x3_kernel(F32GemmParams p, int
         tg = ntg;
         chunk = nchunk;
     }
-    if (p.range_flag && range_max > 65504.f) atomicOr(p.range_flag, 1);          // as f32x3_igemm_kernel: reported, never a silent inf
+    f32_split::report_range(p.range_flag, range_max);
 
     // ---- epilogue straight from the accumulator layout: register r of block (mb, nb) = pixel column (r >> 2) * 8 + (lane >> 5) * 4 + (r & 3)
     // of patch row 2 wm + mb, channel lane & 31 of the block -- 32 lanes cover 128 contiguous bytes of one pixel
@@ -253,10 +248,7 @@ int c3_launch(const F32GemmParams& p, hipStream_t s) {
     constexpr int smem = C3Smem<BN, TAPS>::kBytes;
     static_assert(smem <= 160 * 1024, "LDS");
     static std::atomic<unsigned long long> attr_set{0};          // one bit per device: the attribute belongs to (function, device)
-    if (first_on_device(attr_set)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&f32x3_conv3x3_kernel<BN, TAPS>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        mark_on_device(attr_set);
-    }
+    if (const int rc = allow_dynamic_lds(&f32x3_conv3x3_kernel<BN, TAPS>, smem, attr_set); rc != DVID_OK) return rc;
     const int tiles_x = ceil_div(p.W, C3_TW), tiles_y = ceil_div(p.H, C3_TH), tiles_n = ceil_div(p.Cout, BN);
     const long n_img = p.M / ((long)p.Ho * p.Wo);
     const long grid = n_img * tiles_y * tiles_x * tiles_n;

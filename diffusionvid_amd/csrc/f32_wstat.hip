@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "f32_split.h"
 #include "igemm_epilogue.h"
 #include "kernels.h"
 #include "options.h"
@@ -102,14 +103,10 @@ __global__ __launch_bounds__(512) void f32x3_wstat_kernel(F32GemmParams p, int n
         char* const stg = smem + stage * STAGE;
 #pragma unroll
         for (int i = 0; i < CPT; ++i) {
-            const float4v v0 = ra[i][0], v1 = ra[i][1];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) range_max = fmaxf(range_max, fmaxf(__builtin_fabsf(v0[e]), __builtin_fabsf(v1[e])));
-            const half4 h0 = __builtin_convertvector(v0, half4), h1 = __builtin_convertvector(v1, half4);          // round to nearest even
-            const half4 l0 = __builtin_convertvector(v0 - __builtin_convertvector(h0, float4v), half4);            // v - hi is exact in fp32
-            const half4 l1 = __builtin_convertvector(v1 - __builtin_convertvector(h1, float4v), half4);
-            *reinterpret_cast<half8*>(stg + lds_off[i]) = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-            *reinterpret_cast<half8*>(stg + PLANE + lds_off[i]) = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
+            half8 h, l;
+            f32_split::split8(ra[i][0], ra[i][1], h, l, range_max);
+            *reinterpret_cast<half8*>(stg + lds_off[i]) = h;
+            *reinterpret_cast<half8*>(stg + PLANE + lds_off[i]) = l;
         }
     };
 
@@ -176,13 +173,11 @@ __global__ __launch_bounds__(512) void f32x3_wstat_kernel(F32GemmParams p, int n
             for (int ks = 0; ks < KS; ++ks) {
                 if (ks + 1 < KS) frag(ks + 1);
                 __builtin_amdgcn_sched_barrier(0);
-                // the two small terms first, then the leading one: f32x3_igemm_kernel's order
+                // one pass over every row block, then the next, in f32x3_igemm_kernel's order; the weights are the MFMA's first operand
 #pragma unroll
-                for (int rb = 0; rb < RB; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[ks], al[ks & 1][rb], acc[rb], 0, 0, 0);
+                for (int pass = 0; pass < 3; ++pass)
 #pragma unroll
-                for (int rb = 0; rb < RB; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[ks], ah[ks & 1][rb], acc[rb], 0, 0, 0);
-#pragma unroll
-                for (int rb = 0; rb < RB; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[ks], ah[ks & 1][rb], acc[rb], 0, 0, 0);
+                    for (int rb = 0; rb < RB; ++rb) acc[rb] = f32_split::mfma_pass<true>(pass, ah[ks & 1][rb], al[ks & 1][rb], wh[ks], wl[ks], acc[rb]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
@@ -244,9 +239,7 @@ __global__ __launch_bounds__(512) void f32x3_wstat_kernel(F32GemmParams p, int n
             __syncthreads();                      // tile t + 1 visible; nobody reads tile t any more
         }
     }
-    // an activation beyond the fp16 range became inf in its hi part where fp32 arithmetic would not: reported, never silent (as
-    // f32x3_igemm_kernel; one test per thread and launch instead of one per chunk)
-    if (p.range_flag && range_max > 65504.f) atomicOr(p.range_flag, 1);
+    f32_split::report_range(p.range_flag, range_max);          // (one test per thread and launch instead of f32x3_igemm_kernel's one per chunk)
 }
 
 template <int K, int RB, bool HAS_RES, int ACT>
@@ -254,10 +247,7 @@ int f32ws_launch_k(const F32GemmParams& p, hipStream_t s) {
     constexpr int smem = F32WsSmem<K, RB>::kBytes;
     static_assert(smem <= 160 * 1024, "LDS");
     static std::atomic<unsigned long long> attr_set{0};          // one bit per device: the attribute belongs to (function, device)
-    if (first_on_device(attr_set)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&f32x3_wstat_kernel<K, RB, HAS_RES, ACT>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        mark_on_device(attr_set);
-    }
+    if (const int rc = allow_dynamic_lds(&f32x3_wstat_kernel<K, RB, HAS_RES, ACT>, smem, attr_set); rc != DVID_OK) return rc;
     hipLaunchKernelGGL((f32x3_wstat_kernel<K, RB, HAS_RES, ACT>), dim3(256), dim3(512), smem, s, p, p.Cout / 256);
     LAUNCH_CHECK();
     return DVID_OK;

@@ -167,7 +167,7 @@ int rcnn_head_chain(dvid_model* m, const HeadW& hw, int is_cond, const void* p3,
     return DVID_OK;
 }
 
-// The same pass with DTYPE float32 (csrc/f32.hip): fp32 RoI tiles, q / k / v, dynamic parameters, hidden layers; layer by layer.
+// The same pass with DTYPE float32 (the f32_* kernels of csrc/roialign.hip, attention.hip, dynconv.hip, elementwise.hip; csrc/f32.hip for the layers): fp32 RoI tiles, q / k / v, dynamic parameters, hidden layers; layer by layer.
 int rcnn_head_chain_f32(dvid_model* m, const HeadW& hw, int is_cond, const void* p3, const void* p4, const void* p5, int nf, int height, int width,
                         int M, const float* boxes, const float* pro_features, const float* cond, float* logits, float* boxes_out,
                         float* obj_features, int* bad_box_flag, const float* ss_dev, int ss_stride, hipStream_t s) {

@@ -381,10 +381,8 @@ int launch(const HeadTailParams& p, hipStream_t s) {
     constexpr int BM = 32 * MT;
     constexpr int smem = 2 * BM * APITCH + BM * CPITCH * 4;
     static std::atomic<unsigned long long> attr_set{0};          // one bit per device: the attribute belongs to (function, device)
-    if (first_on_device(attr_set) && smem > 64 * 1024) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&head_tail_kernel<MT>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        mark_on_device(attr_set);
-    }
+    if (smem > 64 * 1024)
+        if (const int rc = allow_dynamic_lds(&head_tail_kernel<MT>, smem, attr_set); rc != DVID_OK) return rc;
     hipLaunchKernelGGL(head_tail_kernel<MT>, dim3((unsigned)((p.R + BM - 1) / BM)), dim3(512), smem, s, p);
     LAUNCH_CHECK();
     return DVID_OK;

@@ -478,11 +478,7 @@ int launch2k(const IgemmParams& p, hipStream_t s) {
     constexpr int smem = Smem2<BM, BN, BKT, NSTAGE>::kBytes;
     if (smem > 64 * 1024) {
         static std::atomic<unsigned long long> attr_set{0};          // one bit per device: the attribute belongs to (function, device)
-        if (first_on_device(attr_set)) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm2_kernel<BM, BN, BKT, NSTAGE, WN, AK, EPI>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            mark_on_device(attr_set);
-        }
+        if (const int rc = allow_dynamic_lds(&igemm2_kernel<BM, BN, BKT, NSTAGE, WN, AK, EPI>, smem, attr_set); rc != DVID_OK) return rc;
     }
     const int nsplit = p.splitk > 1 ? p.splitk : 1;
     hipLaunchKernelGGL((igemm2_kernel<BM, BN, BKT, NSTAGE, WN, AK, EPI>), dim3(p.tiles_m * p.tiles_n * nsplit), dim3(128 * WN), smem, s, p);

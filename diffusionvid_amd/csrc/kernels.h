@@ -73,7 +73,7 @@ int dvid_modulate_launch(const float* x, const float* scale, int scale_ld, const
 int dvid_silu_f16_launch(const float* x, half_t* y, long n, hipStream_t s);
 
 // roialign.hip
-template <typename T>          // the three FPN levels' maps: fp16 (RoiLevels) or fp32 (RoiLevels32, f32.hip)
+template <typename T>          // the three FPN levels' maps: fp16 (RoiLevels) or fp32 (RoiLevels32)
 struct RoiLevelsT {
     const T* feat[3];
     int h[3], w[3];
@@ -200,7 +200,8 @@ int dvid_cdist_launch(const float* x, int n, int d, float* dist, hipStream_t s);
 int dvid_fps_launch(const float* dist, int n, int m, int bs_emul, int* idx, hipStream_t s);
 int dvid_gather_rows_launch(const float* x, const int* idx, float* y, int m, int d, hipStream_t s);
 
-// f32.hip: the DTYPE float32 path (fp32 storage, v_mfma_f32_32x32x2_f32 products)
+// DTYPE float32 (fp32 storage, fp32-grade products).  f32.hip: the implicit GEMM of every convolution and linear layer -- exact fp32 products
+// on v_mfma_f32_32x32x2_f32, or split (hi, lo) fp16 operands on three passes of the fp16 MFMA (f32_split.h)
 struct F32GemmParams {
     const float* in;     // NHWC fp32 [N,H,W,Cin], Cin % 4 == 0  (Linear: [M,K] as N = M, H = W = 1, Cin = K)
     const float* w;      // [Cout][Kpad], k = (ky*KW + kx)*Cin + c, zero beyond K; Kpad % 16 == 0
@@ -225,14 +226,16 @@ int dvid_f32_wstat_launch_tiles(const F32GemmParams& p, hipStream_t s);
 // csrc/f32_conv3x3.hip: 3x3 / stride-1 layers with the halo staged and split once per channel chunk (another summation order than the tiled kernel)
 bool dvid_f32_conv3x3_supported(const F32GemmParams& p);
 int dvid_f32_conv3x3_launch(const F32GemmParams& p, hipStream_t s);
+// the other float32 kernels stand beside their fp16 siblings.  elementwise.hip:
 int dvid_f32_prep_images_launch(const float* const* frames, float* nhwc4, int n, int h, int w, const float* mean, const float* std_, hipStream_t s);
 int dvid_f32_maxpool3x3s2_launch(const float* in, float* out, int n, int h, int w, int c, hipStream_t s);
 int dvid_f32_silu_launch(const float* x, float* y, long n, hipStream_t s);
 int dvid_f32_modulate_launch(const float* x, const float* scale, int scale_ld, const float* shift, int shift_per_row, int shift_ld, float* y,
                              int rows, int rows_per_frame, int d, hipStream_t s);
+// roialign.hip
 int dvid_f32_roialign_launch(const RoiLevels32& lv, int channels, const float* boxes, int n_img, int boxes_per_img, float* roi_out,
                              float* mean_out, hipStream_t s);
-// q / k / v fp32 with head h at columns [32 h, 32 h + 32) of a row (head dim 32)
+// attention.hip: q / k / v fp32 with head h at columns [32 h, 32 h + 32) of a row (head dim 32)
 int dvid_f32_mha_launch(const float* q, const float* k, const float* v, float* out, int batch, int lq, int lk, int nheads, int q_ld, int kv_ld,
                         int out_ld, long q_bs, long kv_bs, long out_bs, hipStream_t s);
 // Swin window attention (shift + 7 x 7 windows + relative-position bias + region mask), fp32: qkv [B*H*W][3C], qkv_bias [3C] (q / k / v of a
@@ -242,7 +245,7 @@ int dvid_f32_swin_window_attn_launch(const float* qkv, const float* qkv_bias, co
 // the same with 12 x 12 windows: relbias [nheads][144][SWIN12_RELBIAS_PITCH]
 int dvid_f32_swin_window12_attn_launch(const float* qkv, const float* qkv_bias, const float* relbias, float* out, int batch, int H, int W, int C,
                                        int nheads, int shift, hipStream_t s);
-// roi [R][49][256], params [R][32768] as P1T[64][256] | P2T[256][64], out [R][49][256]; range_flag (device int or null): the split-operand
+// dynconv.hip: roi [R][49][256], params [R][32768] as P1T[64][256] | P2T[256][64], out [R][49][256]; range_flag (device int or null): the split-operand
 // form ORs 1 into it when a RoI / parameter magnitude exceeds the fp16 range
 int dvid_f32_dynconv_launch(const float* roi, const float* params, const float* g1, const float* b1, const float* g2, const float* b2,
                             float* out, int rows, int* range_flag, hipStream_t s);

@@ -9,10 +9,11 @@
 //
 // MODE 0 (DTYPE float16): fp16 rows, fp16 weights in fragment order (weights.hip: make_frags), v_mfma_f32_32x32x16_f16, fp32 sums.
 // MODE 1 (DTYPE float32, option f32_split = 1): fp32 rows split in the kernel into (hi, lo) fp16 parts, the scaled weight rows as
-//         (hi, lo) fragment planes, three MFMA passes lo*hi + hi*lo + hi*hi as in csrc/f32.hip; a row value beyond the fp16 range
+//         (hi, lo) fragment planes, the three MFMA passes of csrc/f32_split.h with the weights as the first operand, the two small ones in the opposite order; a row value beyond the fp16 range
 //         sets `range_flag`.
 // MODE 2 (DTYPE float32, f32_split = 0): exact fp32 products on v_mfma_f32_32x32x2f32, the scaled fp32 rows [256][256] read in place.
 // MODE 1 / 2 multiply channel n's sum by wscale[n] (the power of two the packed row was divided by, weights.hip: make_conv).
+#include "f32_split.h"
 #include "kernels.h"
 
 namespace {
@@ -56,25 +57,20 @@ __global__ __launch_bounds__(256) void outproj_ln_kernel(const void* __restrict_
             const float4v a = *reinterpret_cast<const float4v*>(x + ks * 16);
             const float4v b = *reinterpret_cast<const float4v*>(x + ks * 16 + 4);
             half8 xh, xl;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                mx = fmaxf(mx, fmaxf(__builtin_fabsf(a[e]), __builtin_fabsf(b[e])));
-                xh[e] = (half_t)a[e];
-                xl[e] = (half_t)(a[e] - (float)xh[e]);
-                xh[4 + e] = (half_t)b[e];
-                xl[4 + e] = (half_t)(b[e] - (float)xh[4 + e]);
-            }
+            f32_split::split8(a, b, xh, xl, mx);
 #pragma unroll
             for (int nt = 0; nt < 8; ++nt) {
                 const long o = (((long)nt * (LD / 16) + ks) * 64 + lane) * 8;
                 const half8 wh = *reinterpret_cast<const half8*>(wf_hi + o);
                 const half8 wl = *reinterpret_cast<const half8*>(wf_lo + o);
-                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh, acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl, acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh, acc[nt], 0, 0, 0);
+                // (this kernel has run the two small terms the other way round since it was written -- weight lo x row hi first; kept, so
+                // that its results stay what they were bit for bit)
+                acc[nt] = f32_split::mfma_pass<true>(1, xh, xl, wh, wl, acc[nt]);
+                acc[nt] = f32_split::mfma_pass<true>(0, xh, xl, wh, wl, acc[nt]);
+                acc[nt] = f32_split::mfma_pass<true>(2, xh, xl, wh, wl, acc[nt]);
             }
         }
-        if (range_flag && mx > 65504.f) atomicOr(range_flag, 1);          // reported, never a silent inf (f32_split = 0 has no such limit)
+        f32_split::report_range(range_flag, mx);
     } else {
         // eight k per step: half h of the wave takes k = 8 kc + 4 h .. + 4 of both operands, MFMA e multiplies element e of each
         // (any pairing of k between the operands gives the same sum of products)

@@ -64,7 +64,7 @@ int linear_run(const ConvW& w, const half_t* in, int rows, void* out, int relu, 
     return conv_run(w, in, rows, 1, 1, out, s, {.relu = relu, .out_f32 = out_f32});
 }
 
-// ---- DTYPE float32: the same layers on csrc/f32.hip (fp32 NHWC activations, un-rounded weights) ---------------------------------
+// ---- DTYPE float32: the same layers on the fp32 kernels (fp32 NHWC activations, un-rounded weights) ---------------------------------
 int conv_run32(const ConvW& w, const float* in, int n, int h, int wd, float* out, hipStream_t s, const ConvOpts32& o) {
     if (!w.w32) return DVID_ERR_STATE;
     F32GemmParams p;

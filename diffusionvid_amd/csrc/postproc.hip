@@ -634,11 +634,7 @@ int dvid_topk_candidates_launch(const float* logits, const float* boxes, int n_i
         const size_t smem2 = (size_t)mpad * 8 + (size_t)m * c * 4 + 2048 * 4;
         if (m * c > m && smem2 <= 150 * 1024) {
             static std::atomic<unsigned long long> attr2{0};          // one bit per device: the attribute belongs to (function, device)
-            if (first_on_device(attr2)) {
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&topk_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            150 * 1024));
-                mark_on_device(attr2);
-            }
+            if (const int rc = allow_dynamic_lds(&topk_select_kernel, 150 * 1024, attr2); rc != DVID_OK) return rc;
             hipLaunchKernelGGL(topk_select_kernel, dim3(n_img, nsets), dim3(1024), smem2, s, logits, boxes, n_img, m, c, mpad, cand_boxes,
                                cand_scores, cand_labels);
             LAUNCH_CHECK();
@@ -649,11 +645,7 @@ int dvid_topk_candidates_launch(const float* logits, const float* boxes, int n_i
     const size_t smem = (size_t)npad * 8;
     if (smem > 160 * 1024) return dvid_topk_stream_launch(logits, boxes, n_img, nsets, m, c, cand_boxes, cand_scores, cand_labels, s);
     static std::atomic<unsigned long long> attr{0};          // one bit per device: the attribute belongs to (function, device)
-    if (first_on_device(attr)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&topk_candidates_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        mark_on_device(attr);
-    }
+    if (const int rc = allow_dynamic_lds(&topk_candidates_kernel, 160 * 1024, attr); rc != DVID_OK) return rc;
     hipLaunchKernelGGL(topk_candidates_kernel, dim3(n_img, nsets), dim3(1024), smem, s, logits, boxes, n_img, m, c, npad, cand_boxes,
                        cand_scores, cand_labels);
     LAUNCH_CHECK();
@@ -677,11 +669,7 @@ int dvid_nms_frames_launch(const float* cand_boxes, const float* cand_scores, co
     const int npad = next_pow2(n);
     const size_t smem = nms_frame_lds_bytes(n);
     static std::atomic<unsigned long long> attr{0};          // one bit per device: the attribute belongs to (function, device)
-    if (first_on_device(attr)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&nms_frame_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024));
-        mark_on_device(attr);
-    }
+    if (const int rc = allow_dynamic_lds(&nms_frame_kernel, 160 * 1024, attr); rc != DVID_OK) return rc;
     hipLaunchKernelGGL(nms_frame_kernel, dim3(n_img), dim3(1024), smem, s, cand_boxes, cand_scores, cand_labels, n, npad, img_w, img_h,
                        iou, use_nms, out_cap, out_boxes, out_scores, out_labels, out_counts);
     LAUNCH_CHECK();

@@ -266,7 +266,7 @@ struct ConvOpts {
 int conv_run(const ConvW& w, const half_t* in, int n, int h, int wd, void* out, hipStream_t s, const ConvOpts& o = {});
 // Linear on [rows, in] fp16
 int linear_run(const ConvW& w, const half_t* in, int rows, void* out, int relu, int out_f32, hipStream_t s);
-// DTYPE float32: the same layers on csrc/f32.hip (fp32 NHWC activations, un-rounded weights)
+// DTYPE float32: the same layers on the fp32 kernels (csrc/f32.hip and the f32_* kernels beside each fp16 one; fp32 NHWC activations, un-rounded weights)
 struct ConvOpts32 {
     int relu = 0;
     const float* res = nullptr;

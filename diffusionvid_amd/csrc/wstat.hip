@@ -462,10 +462,7 @@ int ws2_launch_k(const IgemmParams& p, hipStream_t s) {
     constexpr int smem = Ws2Smem<K, D>::kBytes;
     static_assert(smem <= 160 * 1024, "LDS");
     static std::atomic<unsigned long long> attr_set{0};          // one bit per device: the attribute belongs to (function, device)
-    if (first_on_device(attr_set)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&wstat2_kernel<K, D, HAS_RES, RELU>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        mark_on_device(attr_set);
-    }
+    if (const int rc = allow_dynamic_lds(&wstat2_kernel<K, D, HAS_RES, RELU>, smem, attr_set); rc != DVID_OK) return rc;
     hipLaunchKernelGGL((wstat2_kernel<K, D, HAS_RES, RELU>), dim3(256), dim3(512), smem, s, p, p.Cout / 256);
     LAUNCH_CHECK();
     return DVID_OK;
@@ -483,10 +480,7 @@ int ws_launch_k(const IgemmParams& p, hipStream_t s) {
     constexpr int smem = WsSmem<K, D, TN, HAS_RES>::kBytes;
     static_assert(smem <= 160 * 1024, "LDS");
     static std::atomic<unsigned long long> attr_set{0};          // one bit per device: the attribute belongs to (function, device)
-    if (first_on_device(attr_set)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&wstat_kernel<K, D, TN, HAS_RES, RELU>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        mark_on_device(attr_set);
-    }
+    if (const int rc = allow_dynamic_lds(&wstat_kernel<K, D, TN, HAS_RES, RELU>, smem, attr_set); rc != DVID_OK) return rc;
     hipLaunchKernelGGL((wstat_kernel<K, D, TN, HAS_RES, RELU>), dim3(256), dim3(512), smem, s, p, p.Cout / (256 * TN));
     LAUNCH_CHECK();
     return DVID_OK;

@@ -70,7 +70,7 @@ def conv2d_nhwc(x, w_packed, kpad, bias, cout, kh, kw, stride, pad, relu=False, 
     return out
 
 
-# ---- DTYPE float32 forms (csrc/f32.hip): fp32 NHWC activations, un-rounded weights, fp32 MFMA --------------------------------------
+# ---- DTYPE float32 forms (csrc/f32.hip for conv / linear, the f32_* kernels of csrc/roialign.hip, attention.hip, dynconv.hip): fp32 NHWC activations, un-rounded weights, fp32 MFMA --------------------------------------
 def pack_conv_weight_f32(w, scale_rows=False):
     """OIHW fp32 (or [out, in]) -> fp32 [cout, kpad], k = (ky*kw+kx)*cin4 + c with cin4 = cin rounded up to 4, kpad to 16 (zeros).
     scale_rows: additionally multiply each row by the power of two that puts its largest magnitude in [0.5, 1) and return
@@ -268,7 +268,7 @@ def swin_window_attn_f16(qkv16, qkv_bias16, relbias, B, H, W, nheads, shift, out
 
 
 def swin_window_attn_f32(qkv, qkv_bias, relbias, B, H, W, nheads, shift, out=None, window=7):
-    """the fp32 form of swin_window_attn_f16 (csrc/f32.hip)"""
+    """the fp32 form of swin_window_attn_f16 (csrc/attention.hip: f32_swin_window_attn_kernel / f32_swin_window12_attn_kernel)"""
     return _swin_window_attn("dvid_swin_window_attn_f32", torch.float32, qkv, qkv_bias, relbias, B, H, W, nheads, shift, out, window)
 
 

@@ -172,7 +172,7 @@ int dvid_local_xattn(dvid_model* m, int stage, const float* query, int rows, int
 int dvid_roialign_v2_multilevel(const void* p3, const void* p4, const void* p5, int n_frames, int height, int width,
                                 int channels, const float* boxes, int boxes_per_frame, void* roi_out /* fp16 [R,49,C] */,
                                 float* mean_out /* [R,C] or NULL */, void* stream);
-/* The DTYPE float32 forms of the stand-alone ops (csrc/f32.hip): fp32 NHWC pyramids -> fp32 [R,49,C] tiles; fp32 conv / linear with
+/* The DTYPE float32 forms of the stand-alone ops (csrc/f32.hip for conv / linear; the others beside their fp16 kernels in csrc/roialign.hip, attention.hip, dynconv.hip): fp32 NHWC pyramids -> fp32 [R,49,C] tiles; fp32 conv / linear with
  * w [cout][kpad] fp32, k = (ky*kw+kx)*cin + c, cin % 4 == 0, kpad = round_up(kh*kw*cin, 16) zero-padded, and row_scale [cout] (may be
  * NULL): out channel n = act(acc_n * row_scale[n] + bias[n] + residual) -- the model packs each row times a power of two that puts its
  * largest magnitude in [0.5, 1) and hands 2^-e here, which keeps the split-operand products at fp32 grade for small weights; w_hi / w_lo
@@ -317,7 +317,7 @@ int dvid_swin_window_attn_f16(const void* qkv, const void* qkv_bias16, const flo
  * w = 7 forwards to them.  w = 12 (the 384-pretrained Swin sizes): table [(2w-1)^2 = 529][nheads] -> out [nheads][144][160] floats
  * (pitch = w*w rounded up to a multiple of 32), columns 144..159 zero; the token map is padded to multiples of 12 and rolled by -shift,
  * 0 <= shift < w (DVID_ERR_ARG otherwise), attended per 12x12 window (csrc/attention.hip: swin_window12_attn_kernel; fp32:
- * csrc/f32.hip: f32_swin_window12_attn_kernel).  C = 32 * nheads, DVID_ERR_UNSUPPORTED otherwise. */
+ * csrc/attention.hip: f32_swin_window12_attn_kernel).  C = 32 * nheads, DVID_ERR_UNSUPPORTED otherwise. */
 int dvid_swin_pack_relbias_ws(const float* table, int nheads, int window, float* out);
 int dvid_swin_window_attn_f16_ws(const void* qkv, const void* qkv_bias16, const float* relbias, void* out, int batch, int H, int W, int C,
                                  int nheads, int shift, int window, void* stream);

@@ -1,5 +1,5 @@
 """The Swin backbone's own kernels, each on its own through the C ABI, against float64 references of the operations
-(tests/_swin_ref.py): swin_window_attn_kernel<4> (csrc/attention.hip), f32_swin_window_attn_kernel (csrc/f32.hip) and
+(tests/_swin_ref.py): swin_window_attn_kernel<4> (csrc/attention.hip), f32_swin_window_attn_kernel (csrc/attention.hip) and
 patch_merge_ln_kernel (csrc/elementwise.hip).  The backbone tests run them only inside ~20 layers, on one geometry whose token
 maps never pad along W and never merge an odd map; a slip in a border window is diluted there before anything is compared.
 

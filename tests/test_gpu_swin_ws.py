@@ -1,6 +1,6 @@
 """The 12x12 Swin window-attention kernels (the 384-pretrained sizes), each on its own through the C ABI's `_ws` entries, against the
 float64 reference of tests/_swin_ws_ref.py: swin_window12_attn_kernel<2> (csrc/attention.hip) and f32_swin_window12_attn_kernel
-(csrc/f32.hip).  Same bounds and the same guarded, NaN-filled, launched-twice outputs as tests/test_gpu_swin.py: fp16 4e-3 of RMS +
+(csrc/attention.hip).  Same bounds and the same guarded, NaN-filled, launched-twice outputs as tests/test_gpu_swin.py: fp16 4e-3 of RMS +
 4e-3 relative, fp32 2e-5 + 2e-5.  tests/test_swin_ws_ref.py shows on the CPU that every case of ATTN_CASES below tells each of five
 index mistakes from the right answer by more than 20 times the fp16 bound; the 1x1 map is run as an edge case only.
 """

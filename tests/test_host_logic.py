@@ -77,7 +77,7 @@ def test_default_library_configuration_is_the_benchmarked_one():
 
 
 def test_split_operand_arithmetic_bound():
-    """The arithmetic of the DTYPE float32 path's split-operand products (csrc/f32.hip: f32x3_igemm_kernel), restated in numpy -- no GPU: a value v is
+    """The arithmetic of the DTYPE float32 path's split-operand products (csrc/f32_split.h, used by f32x3_igemm_kernel and its four siblings), restated in numpy -- no GPU: a value v is
     carried as hi = fp16(v), lo = fp16(v - hi); a dot product is accumulated in fp32 from lo_a hi_b + hi_a lo_b + hi_a hi_b (each fp16 x fp16 product is
     exact in fp32).  With the weight rows scaled by a power of two to a largest magnitude in [0.5, 1) (ops.pack_conv_weight_f32(scale_rows=True), what
     make_conv does) the result is as close to the exact dot product as a plain fp32 evaluation is for O(1) activations, where an fp16-operand product

@@ -1,4 +1,4 @@
-"""Stand-alone timing of the DTYPE float32 DynamicConv kernels (csrc/f32.hip) at 104 frames x 300 boxes:
+"""Stand-alone timing of the DTYPE float32 DynamicConv kernels (csrc/dynconv.hip: f32_dynconv_kernel, f32x3_dynconv_kernel) at 104 frames x 300 boxes:
 python tools/lab/bench_f32_dynconv.py [boxes]  ->  ms and TB/s of the 226 KB per box (128 KB parameters + 2 x 49 KB tiles), f32_split 1 and 0."""
 import sys
 
