@@ -31,9 +31,10 @@ def _iou(box, area, boxes, areas):
         return inter / (area + areas - inter)
 
 
-def seq_nms_class(boxes, scores):
+def seq_nms_class(boxes, scores, trace=None):
     """One class of one video.  boxes: list over frames of [n_f, 4] float32, scores: list of [n_f] float32; both are changed in place
-    (suppressed rows zeroed, path rows rescored).  Returns (deleted: list of bool [n_f], rounds)."""
+    (suppressed rows zeroed, path rows rescored).  Returns (deleted: list of bool [n_f], rounds).  A list given as `trace` receives one
+    (root frame, path) per round: path[i] is the in-class index of the path's box in frame root + i."""
     F = len(boxes)
     deleted = [np.zeros(len(s), dtype=bool) for s in scores]
     on_path = [np.zeros(len(s), dtype=bool) for s in scores]
@@ -82,6 +83,8 @@ def seq_nms_class(boxes, scores):
             path.append(j)
         root = f
         path.reverse()
+        if trace is not None:
+            trace.append((root, list(path)))
         fresh = np.float32(np.float64(maxsum) / len(path))
         for i, p in enumerate(path):
             scores[root + i][p] = fresh
@@ -110,8 +113,9 @@ def seq_nms_class(boxes, scores):
     return deleted, rounds
 
 
-def seq_nms_video(dets, counts, num_classes, progress=None):
-    """dets [frames, cap, 6], counts [frames] -> (keep [frames, cap] uint8, scores [frames, cap] float32), as ops.seq_nms_video."""
+def seq_nms_video(dets, counts, num_classes, progress=None, trace=None):
+    """dets [frames, cap, 6], counts [frames] -> (keep [frames, cap] uint8, scores [frames, cap] float32), as ops.seq_nms_video.
+    `progress(c, rounds)` is called per class that has a box; a dict given as `trace` receives {c: seq_nms_class's trace}."""
     dets = np.asarray(dets, dtype=np.float32)
     counts = np.asarray(counts).astype(np.int64)
     F, cap = dets.shape[:2]
@@ -124,13 +128,27 @@ def seq_nms_video(dets, counts, num_classes, progress=None):
             continue
         boxes = [dets[f, rows[f], :4].copy() for f in range(F)]
         scores = [dets[f, rows[f], 4].copy() for f in range(F)]
-        deleted, rounds = seq_nms_class(boxes, scores)
+        deleted, rounds = seq_nms_class(boxes, scores, None if trace is None else trace.setdefault(c, []))
         if progress is not None:
             progress(c, rounds)
         for f in range(F):
             keep[f, rows[f]] = ~deleted[f]
             out[f, rows[f]] = scores[f]
     return keep, out
+
+
+def seq_nms_rounds(dets, counts, num_classes, video_starts=None):
+    """(keep, scores, rounds [n_videos, num_classes] int32): seq_nms_video per video, with the paths each class gave up -- the status
+    words of ops.seq_nms_video(..., return_status=True)"""
+    dets, counts = np.asarray(dets, dtype=np.float32), np.asarray(counts)
+    starts = [0, len(counts)] if video_starts is None else [int(v) for v in video_starts]
+    keep = np.zeros(dets.shape[:2], dtype=np.uint8)
+    out = np.zeros(dets.shape[:2], dtype=np.float32)
+    rounds = np.zeros((len(starts) - 1, num_classes), dtype=np.int32)
+    for v in range(len(starts) - 1):
+        a, b = starts[v], starts[v + 1]
+        keep[a:b], out[a:b] = seq_nms_video(dets[a:b], counts[a:b], num_classes, progress=lambda c, r, v=v: rounds.__setitem__((v, c - 1), r))
+    return keep, out, rounds
 
 
 def class_counts(dets, counts, num_classes):

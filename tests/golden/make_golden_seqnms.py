@@ -16,7 +16,22 @@ result as `keep` [frames, cap] (uint8) and `scores` [frames, cap] (the rescored 
   e  a tiny box at the image origin whose IoU with an already-zeroed (0, 0, 0, 0) box is >= 0.3
   f  one 40-frame track whose sequential float32 sum differs from the float64 sum in the rescored bits (asserted here)
 
-The fixture lives in tests/golden/seqnms/: tests/test_golden_regeneration.py requires every .npz directly under tests/golden/ to come
+A second file, g20_seq_nms_bounds.npz, holds videos that reach the second trip of every loop of csrc/seqnms.hip (a 256-thread workgroup,
+64-lane waves, 64-bit link words); every score is a multiple of 1/8, so ties are frequent.  This generator asserts what each is for:
+
+  g   304 frames, 2 to 8 boxes each and one empty frame: class 3's best path of the first round lies wholly behind frame 256; class 7
+      has a trunk that forks into two branches of equal sum ending at frames 209 and 259 (the lower frame wins), and three successive
+      paths rooted behind frame 0, the second in front of the first's root; class 12 has two equal tracks that merge (the DP's
+      predecessor tie)
+  h   8 frames in which class 5 holds 63, 64, 65, 128, 129, 256, 257 and 320 boxes in sixteen clusters, interleaved with a small class 9:
+      at least 8 rounds, a rescored box at in-class index >= 256, a backpointer >= 64 on a taken path
+  i0, i1, i2   three videos of 9, 1 and 5 frames for ONE call: in i0 every class has links; i1 is a single frame; i2 mixes live classes
+      with classes that have boxes but no link.  Most frames hold fewer rows than `cap`, and the rows behind `counts` are copies of live
+      rows, not zeros; they come back keep 0, score 0.  A few rows in front of `counts` carry label 0 or 31.  The reference never sees
+      those (its class lists are 1..30), so they are left out of the comparison with it and stored with the restatement's result, which
+      is this project's contract: kept, score unchanged.
+
+The fixtures live in tests/golden/seqnms/: tests/test_golden_regeneration.py requires every .npz directly under tests/golden/ to come
 out of make_golden.py, which this generator must not touch.
 """
 import os
@@ -32,6 +47,9 @@ import _ref_shims as S  # noqa: E402
 S.install()
 
 import torch  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(HERE))
+import _seq_nms_host as H  # noqa: E402
 
 from mega_core.structures.bounding_box import BoxList  # noqa: E402
 from seq_nms import seq_nms  # noqa: E402
@@ -187,6 +205,164 @@ def case_f():
     raise AssertionError("case f must tell the float32 accumulation from a float64 one")
 
 
+G = 0.125
+WIDE = (63, 64, 65, 128, 129, 256, 257, 320)
+
+
+def case_g():
+    v = Video(304, 200)
+    v.track(3, 20, 41, (60, 40, 160, 120), (1, 0), 0.5, dup=1, grid=G)
+    v.track(3, 262, 304, (60, 40, 160, 120), (1, 0), 0.875, dup=1, grid=G)                                # 36.75 behind frame 256: round 1
+    # class 7: the trunk forks at frame 200 into P (10 x 0.75, to frame 209) and Q (60 x 0.125, to frame 259): 20 + 7.5 either way
+    v.track(7, 160, 200, (300, 100, 400, 200), (0, 0), 0.5, dup=0)
+    v.track(7, 200, 210, (267, 100, 367, 200), (-4, 0), 0.75, dup=0)
+    v.track(7, 200, 260, (333, 100, 433, 200), (1, 0), 0.125, dup=0)
+    v.track(7, 100, 131, (300, 240, 400, 340), (0, 0), 0.25, dup=1, grid=G)                               # in front of the first path's root
+    # class 12: A and B (equal scores, 50..59) both link to the tail's first box at frame 60
+    v.track(12, 50, 60, (167, 220, 267, 320), (0, 0), 0.5, dup=0)
+    v.track(12, 50, 60, (233, 220, 333, 320), (0, 0), 0.5, dup=0)
+    v.track(12, 60, 70, (200, 220, 300, 320), (0, 0), 0.625, dup=0)
+    for f in range(304):                                                                                  # clutter away from the tracks
+        for _ in range(2):
+            x, y = v.rng.uniform(450, 560), v.rng.uniform(0, 300)
+            v.add(f, (x, y, x + v.rng.uniform(20, 70), y + v.rng.uniform(20, 50)), G * v.rng.randint(1, 4), (3, 7, 12, 21)[v.rng.randint(4)])
+    v.rows[150] = []
+    return v.packed()
+
+
+def case_h():
+    v = Video(len(WIDE), 201)
+    for f, n in enumerate(WIDE):
+        for k in range(n):                                                                                # sixteen clusters, 160 x 90 apart
+            c = k % 16
+            x, y = 30 + 150 * (c % 4) + v.rng.uniform(-32, 32), 15 + 85 * (c // 4) + v.rng.uniform(-20, 20)
+            v.add(f, (x, y, x + 80 + v.rng.uniform(-24, 24), y + 50 + v.rng.uniform(-14, 14)), G * v.rng.randint(1, 8), 5)
+    v.track(9, 0, len(WIDE), (250, 150, 330, 230), (3, 1), 0.75, dup=4, grid=G)
+    return v.packed()
+
+
+def _garbage(v, extra):
+    """packed, with `extra` more rows per frame and every row behind counts a copy of a live row of the video (score and label included)"""
+    dets, counts = v.packed()
+    dets = np.concatenate([dets, np.zeros((dets.shape[0], extra, 6), dtype=np.float32)], axis=1)
+    live = dets[np.arange(dets.shape[1])[None, :] < counts[:, None]]
+    live = live[(live[:, 5] >= 1) & (live[:, 5] <= NUM_CLASSES)]
+    for f in range(dets.shape[0]):
+        k = dets.shape[1] - counts[f]
+        dets[f, counts[f]:] = live[v.rng.randint(len(live), size=k)]
+    return dets, counts
+
+
+def _cell(c):
+    x, y = 8 + 105 * ((c - 1) % 6), 6 + 70 * ((c - 1) // 6)
+    return (x, y, x + 70, y + 45)
+
+
+def case_i0():
+    v = Video(9, 202)
+    for c in range(1, NUM_CLASSES + 1):
+        v.track(c, c % 3, 9 - c % 2, _cell(c), (2, 1), lambda f, c=c: G * (2 + (c + f) % 5), dup=1 + c % 2, grid=G)
+        if c % 3:                                                                                         # a second, shorter track that crosses the first's 0.3 ring
+            x0, y0 = _cell(c)[:2]
+            v.track(c, 2, 7, (x0 + 45, y0 + 6, x0 + 115, y0 + 51), (-6, 0), G * (1 + c % 4), dup=c % 2, grid=G)
+    for f in (0, 3, 4, 8):
+        v.add(f, _cell(4), 0.875, 0)                                                                      # on top of a live track
+        v.add(f, _cell(31 - f), 0.875, 31)
+    v.clutter(3, [2, 11, 29], grid=G)
+    for f in (1, 5):
+        v.clutter(1, [6], grid=G)
+    return _garbage(v, 4)
+
+
+def case_i1():
+    v = Video(1, 203)
+    for c in (1, 7, 30):
+        v.track(c, 0, 1, _cell(c), (0, 0), 0.5, dup=2, grid=G)
+    v.add(0, _cell(7), 0.25, 31)
+    return _garbage(v, 3)
+
+
+LIVE_I2, LONE_I2, FAR_I2 = (2, 5, 9, 14, 30), (1, 8, 20), 17
+
+
+def case_i2():
+    v = Video(5, 204)
+    for c in LIVE_I2:
+        v.track(c, c % 2, 5, _cell(c), (3, 0), lambda f, c=c: G * (1 + (c * f) % 6), dup=2, grid=G)
+    for c in LONE_I2:                                                                                     # never in two adjacent frames
+        for f in (0, 2, 4):
+            v.add(f, _cell(c), 0.5, c)
+            v.add(f, _cell(c), 0.25, c)
+    for f in range(5):                                                                                    # adjacent frames, too far apart to link
+        v.add(f, (100 * f, 290, 100 * f + 60, 340), 0.375, FAR_I2)
+    v.add(1, _cell(5), 0.75, 0)
+    v.add(3, _cell(9), 0.75, 31)
+    for f in (0, 4):
+        v.clutter(4, [2, 5], grid=G)
+    return _garbage(v, 2)
+
+
+def _in_class(dets, counts, c):
+    """per frame the rows of class c, in order"""
+    return [np.nonzero(dets[f, :counts[f], 5] == c)[0] for f in range(len(counts))]
+
+
+def check_bounds(name, dets, counts, keep, scores):
+    """what each g20 case is for, from the arrays and the restatement (tests/test_seq_nms.py asserts the same of the stored file)"""
+    trace = {}
+    hk, hs = H.seq_nms_video(dets, counts, NUM_CLASSES, trace=trace)
+    live = np.arange(dets.shape[1])[None, :] < counts[:, None]
+    alien = live & ((dets[:, :, 5] < 1) | (dets[:, :, 5] > NUM_CLASSES))
+    assert (hk[alien] == 1).all() and np.array_equal(hs[alien], dets[:, :, 4][alien])
+    assert np.array_equal(hk[~alien], keep[~alien]) and np.array_equal(hs[~alien].view(np.uint32), scores[~alien].view(np.uint32)), name
+    assert not keep[~live].any() and not scores[~live].any()
+    assert (dets[:, :, 4] * 8 == np.round(dets[:, :, 4] * 8)).all(), "scores on the 1/8 grid"
+    tab = H.class_counts(dets, counts, NUM_CLASSES)
+    ends = {c: [(root, root + len(p) - 1) for root, p in t] for c, t in trace.items()}
+    if name == "g":
+        assert len(counts) >= 300 and counts[150] == 0 and ((counts >= 2) & (counts <= 8))[np.arange(len(counts)) != 150].all()
+        assert ends[3][0][0] > 256 and ends[3][0][1] >= 256, "class 3: the first round's winner lies behind frame 256"
+        assert ends[7][0] == (160, 209) and (200, 259) in ends[7][1:3], "class 7: of the two equal sums the lower frame wins"
+        assert all(r > 0 for r, _ in ends[7][:3]) and ends[7][1][1] < ends[7][0][0], "class 7: three paths rooted behind frame 0, the second in front of the first's root"
+        r59 = _in_class(dets, counts, 12)[59]
+        a, b = (int(np.nonzero(dets[59, r59, 0] == x)[0][0]) for x in (167, 233))
+        assert ends[12][0] == (50, 69) and trace[12][0][1][9] == min(a, b), "class 12: of two equal predecessors the lower row stays"
+    if name == "h":
+        assert tuple(tab[:, 4]) == WIDE and (tab[:, 8] > 0).all() and len(trace[5]) >= 8
+        rows = _in_class(dets, counts, 5)
+        assert any(((keep[f, r] == 1) & (scores[f, r] != dets[f, r, 4]))[256:].any() for f, r in enumerate(rows)), "a rescored box at in-class index >= 256"
+        assert any(i >= 64 for _, p in trace[5] for i in p[:-1]), "a backpointer >= 64 on a taken path"
+        assert any(not np.array_equal(np.sort(r), np.arange(len(r))) for r in rows), "the classes' rows interleave"
+    if name == "i0":
+        assert len(counts) == 9 and all(len(trace.get(c, ())) >= 1 for c in range(1, NUM_CLASSES + 1)), "every class has links"
+    if name == "i1":
+        assert len(counts) == 1 and (hk[live] == 1).all()
+    if name == "i2":
+        assert len(counts) == 5 and all(len(trace[c]) >= 1 for c in LIVE_I2) and all(tab[:, c - 1].sum() > 0 and not trace[c] for c in LONE_I2 + (FAR_I2,))
+        assert all(not (tab[:-1, c - 1] * tab[1:, c - 1]).any() for c in LONE_I2) and (tab[:-1, FAR_I2 - 1] * tab[1:, FAR_I2 - 1]).all()
+    if name.startswith("i"):
+        assert (counts < dets.shape[1]).sum() * 2 > len(counts) and (dets[~live][:, 4] > 0).all() and (dets[~live][:, 5] >= 1).all()
+        if name != "i1":
+            assert (dets[:, :, 5][live] == 0).any()
+        assert (dets[:, :, 5][live] == 31).any()
+    return len(trace)
+
+
+def main_bounds():
+    arrs = {}
+    for name, make in (("g", case_g), ("h", case_h), ("i0", case_i0), ("i1", case_i1), ("i2", case_i2)):
+        dets, counts = make()
+        keep, scores = run_reference(dets.copy(), counts)
+        alien = (np.arange(dets.shape[1])[None, :] < counts[:, None]) & ((dets[:, :, 5] < 1) | (dets[:, :, 5] > NUM_CLASSES))
+        assert not keep[alien].any()                                         # the reference never saw them: the restatement's result instead
+        keep[alien], scores[alien] = 1, dets[:, :, 4][alien]
+        classes = check_bounds(name, dets, counts, keep, scores)
+        arrs.update({name + "_dets": dets, name + "_counts": counts, name + "_keep": keep, name + "_scores": scores})
+        print("case", name, "frames", dets.shape[0], "cap", dets.shape[1], "boxes", int(counts.sum()), "kept", int(keep.sum()), "classes", classes)
+    np.savez_compressed(os.path.join(OUT, "g20_seq_nms_bounds.npz"), **arrs)
+    print("wrote g20_seq_nms_bounds")
+
+
 def main():
     arrs = {}
     for name, make in (("a", case_a), ("b", case_b), ("c", case_c), ("d", case_d), ("e", case_e), ("f", case_f)):
@@ -219,3 +395,4 @@ def main():
 
 if __name__ == "__main__":
     main()
+    main_bounds()

@@ -2,6 +2,7 @@
 
 tests/golden/seqnms/g19_seq_nms.npz is what the reference's seq_nms.py returned (tests/golden/make_golden_seqnms.py); the restatement in
 tests/_seq_nms_host.py must equal it exactly, and stands in for the kernel where the engine is exercised without a GPU.
+g20_seq_nms_bounds.npz beside it holds the videos that reach the second trip of every loop of the kernel (tests/test_gpu_seq_nms.py).
 """
 import functools
 import os
@@ -19,16 +20,35 @@ import _seq_nms_host as H
 
 G19 = "seqnms/g19_seq_nms"
 CASES = "abcdef"
+G20 = "seqnms/g20_seq_nms_bounds"
+CASES20 = ("g", "h", "i0", "i1", "i2")
+WIDE = (63, 64, 65, 128, 129, 256, 257, 320)
+
+
+@pytest.fixture(scope="module")
+def regenerated(tmp_path_factory):
+    """one run of the generator for both files"""
+    out = tmp_path_factory.mktemp("seqnms")
+    env = dict(os.environ, DVID_GOLDEN_OUT=str(out))
+    subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "make_golden_seqnms.py")], check=True, env=env, capture_output=True)
+    return out
 
 
 @pytest.mark.skipif(not os.path.isdir("/root/reference/mega_core"), reason="the reference tree is only present in the build container")
-def test_fixture_regenerates_bit_identically(tmp_path):
-    env = dict(os.environ, DVID_GOLDEN_OUT=str(tmp_path))
-    subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "make_golden_seqnms.py")], check=True, env=env, capture_output=True)
-    new, old = np.load(tmp_path / "g19_seq_nms.npz"), golden(G19)
+def test_fixture_regenerates_bit_identically(regenerated):
+    new, old = np.load(regenerated / "g19_seq_nms.npz"), golden(G19)
     assert sorted(new.files) == sorted(old.files) and len(old.files) == 4 * len(CASES)
     for k in old.files:
         assert new[k].dtype == old[k].dtype and new[k].tobytes() == old[k].tobytes(), k
+
+
+@pytest.mark.skipif(not os.path.isdir("/root/reference/mega_core"), reason="the reference tree is only present in the build container")
+def test_bounds_fixture_regenerates_bit_identically(regenerated):
+    new, old = np.load(regenerated / "g20_seq_nms_bounds.npz"), golden(G20)
+    assert sorted(new.files) == sorted(old.files) and len(old.files) == 4 * len(CASES20)
+    for k in old.files:
+        assert new[k].dtype == old[k].dtype and new[k].tobytes() == old[k].tobytes(), k
+    assert os.path.getsize(os.path.join(ROOT, "tests", "golden", G20 + ".npz")) < 128 << 10
 
 
 def test_fixture_holds_the_cases_it_is_for():
@@ -40,6 +60,78 @@ def test_fixture_holds_the_cases_it_is_for():
     live = np.arange(z["f_dets"].shape[1])[None, :] < z["f_counts"][:, None]
     s64 = np.float32(z["f_dets"][:, :, 4][live].astype(np.float64).sum() / 40)
     assert (z["f_scores"][live] != s64).all()          # the float64 sum gives other bits: case f pins the float32 accumulation
+
+
+def _in_class(dets, counts, c):
+    return [np.nonzero(dets[f, :counts[f], 5] == c)[0] for f in range(len(counts))]
+
+
+def test_bounds_fixture_holds_the_cases_it_is_for():
+    """the properties make_golden_seqnms.py asserted when it wrote g20, derived again from the stored arrays and the restatement"""
+    z = golden(G20)
+    for case in CASES20:
+        dets, counts, keep, scores = (z[case + "_" + k] for k in ("dets", "counts", "keep", "scores"))
+        live = np.arange(dets.shape[1])[None, :] < counts[:, None]
+        assert (dets[:, :, 4] * 8 == np.round(dets[:, :, 4] * 8)).all()          # the coarse score grid: ties are frequent
+        assert not keep[~live].any() and not scores[~live].any()
+    trace = {c: {} for c in CASES20}
+    for c in CASES20:
+        H.seq_nms_video(z[c + "_dets"], z[c + "_counts"], 30, trace=trace[c])
+    ends = {c: {k: [(root, root + len(p) - 1) for root, p in t] for k, t in trace[c].items()} for c in CASES20}
+
+    # g: long
+    dets, counts = z["g_dets"], z["g_counts"]
+    assert len(counts) >= 300 and counts[150] == 0 and ((counts >= 2) & (counts <= 8))[np.arange(len(counts)) != 150].all()
+    assert ends["g"][3][0][0] > 256 and ends["g"][3][0][1] >= 256          # class 3's first winner lies behind frame 256
+    assert ends["g"][7][0] == (160, 209) and (200, 259) in ends["g"][7][1:3]          # two equal sums: the lower frame wins, the other branch follows
+    assert all(r > 0 for r, _ in ends["g"][7][:3]) and ends["g"][7][1][1] < ends["g"][7][0][0]          # three roots > 0, one in front of the last root
+    r59 = _in_class(dets, counts, 12)[59]
+    a, b = (int(np.nonzero(dets[59, r59, 0] == x)[0][0]) for x in (167, 233))
+    assert ends["g"][12][0] == (50, 69) and trace["g"][12][0][1][9] == min(a, b)          # two equal predecessors: the lower row stays
+
+    # h: wide
+    dets, counts, keep, scores = z["h_dets"], z["h_counts"], z["h_keep"], z["h_scores"]
+    tab = H.class_counts(dets, counts, 30)
+    assert tuple(tab[:, 4]) == WIDE and (tab[:, 8] > 0).all() and len(trace["h"][5]) >= 8
+    rows = _in_class(dets, counts, 5)
+    assert any(((keep[f, r] == 1) & (scores[f, r] != dets[f, r, 4]))[256:].any() for f, r in enumerate(rows))
+    assert any(i >= 64 for _, p in trace["h"][5] for i in p[:-1])          # a backpointer >= 64 on a taken path
+    assert any(not np.array_equal(np.sort(r), np.arange(len(r))) for r in rows)          # the two classes' rows interleave
+
+    # i: busy
+    assert [len(z["i%d_counts" % v]) for v in range(3)] == [9, 1, 5]
+    assert all(len(trace["i0"].get(c, ())) >= 1 for c in range(1, 31))          # every class of video 0 gives up a path
+    t2, tab = trace["i2"], H.class_counts(z["i2_dets"], z["i2_counts"], 30)
+    live2 = [c for c in range(1, 31) if t2.get(c)]
+    idle2 = [c for c in range(1, 31) if tab[:, c - 1].any() and not t2.get(c)]
+    assert len(live2) >= 3 and len(idle2) >= 3
+    assert any(not (tab[:-1, c - 1] * tab[1:, c - 1]).any() for c in idle2) and any((tab[:-1, c - 1] * tab[1:, c - 1]).any() for c in idle2)
+    for v in range(3):
+        dets, counts, keep, scores = (z["i%d_%s" % (v, k)] for k in ("dets", "counts", "keep", "scores"))
+        live = np.arange(dets.shape[1])[None, :] < counts[:, None]
+        assert (counts < dets.shape[1]).sum() * 2 > len(counts) and (dets[~live][:, 4] > 0).all() and (dets[~live][:, 5] >= 1).all()
+        alien = live & ((dets[:, :, 5] < 1) | (dets[:, :, 5] > 30))
+        assert (dets[:, :, 5][alien] == 31).any() and (v == 1 or (dets[:, :, 5][alien] == 0).any())
+        assert (keep[alien] == 1).all() and np.array_equal(scores[alien], dets[:, :, 4][alien])          # the restatement's: the reference never saw them
+
+
+@pytest.mark.parametrize("case", CASES20)
+def test_restatement_equals_the_reference_exactly_on_the_bounds(case):
+    z = golden(G20)
+    keep, scores, rounds = H.seq_nms_rounds(z[case + "_dets"], z[case + "_counts"], 30)
+    assert np.array_equal(keep, z[case + "_keep"])
+    assert np.array_equal(scores.view(np.uint32), z[case + "_scores"].view(np.uint32))
+    assert rounds.shape == (1, 30) and (rounds >= 0).all()
+
+
+def test_rounds_helper_leaves_the_results_alone():
+    z = golden(G19)
+    keep, scores = H.seq_nms_video(z["a_dets"], z["a_counts"], 30)
+    seen, trace = {}, {}
+    k2, s2, rounds = H.seq_nms_rounds(z["a_dets"], z["a_counts"], 30)
+    k3, s3 = H.seq_nms_video(z["a_dets"], z["a_counts"], 30, progress=seen.__setitem__, trace=trace)
+    assert np.array_equal(keep, k2) and np.array_equal(keep, k3) and scores.tobytes() == s2.tobytes() == s3.tobytes()
+    assert [int(rounds[0, c - 1]) for c in seen] == list(seen.values()) == [len(trace[c]) for c in seen] and rounds.sum() == sum(seen.values()) > 0
 
 
 @pytest.mark.parametrize("case", CASES)
