@@ -54,13 +54,14 @@ struct PixelNorm {
     }
 };
 
-// detectron2 FPN.forward over three levels (strides 8/16/32): lateral 1x1 (+ nearest-x2 top-down sum fused in the
-// epilogue), 3x3 output conv.  cin / lat / pout = the levels' inputs (c3, c4, c5), lateral buffers and outputs, NHWC fp16 or fp32;
-// sh / sw = their heights / widths.
+// detectron2 FPN.forward over the model's levels (strides 8/16/32, with the p2 level 4/8/16/32), bottom level last: lateral 1x1 (+
+// nearest-x2 top-down sum fused in the epilogue), 3x3 output conv.  Every array is indexed by stage, 0 = res2 / level 2 .. 3 = res5 /
+// level 5, and read from index 4 - fpn_levels on: cin / lat / pout = the levels' inputs (c2..c5), lateral buffers and outputs, NHWC fp16
+// or fp32; sh / sw = their heights / widths.
 template <typename T>
 int run_fpn(dvid_model* m, T* const* cin, T* const* lat, T* const* pout, int n, const int* sh, const int* sw, hipStream_t s) {
-    for (int l = 2; l >= 0; --l) {
-        const T* res = (l < 2) ? lat[l + 1] : nullptr;
+    for (int l = 3; l >= 4 - m->fpn_levels; --l) {
+        const T* res = (l < 3) ? lat[l + 1] : nullptr;
         if constexpr (std::is_same<T, float>::value) {
             TRY(conv_run32(m->lateral[l], cin[l], n, sh[l], sw[l], lat[l], s, {.res = res, .res_mode = res ? 2 : 0}));
             TRY(conv_run32(m->output[l], lat[l], n, sh[l], sw[l], pout[l], s));
@@ -109,8 +110,8 @@ int run_chains(dvid_model* m, int n, hipStream_t s, Body&& body) {
 template <typename T>
 struct ChainSlices {
     T *img, *bx, *by, *t1, *t2, *sc;
-    T* stage_out[4];          // res3..res5 outputs persist for the FPN (c3, c4, c5); res2 has none
-    T* lat[3];
+    T* stage_out[4];          // res3..res5 outputs persist for the FPN (c3, c4, c5); res2's (c2) only in a model with the p2 level
+    T* lat[4];                // by stage, as run_fpn reads them; [0] null without the p2 level
     ChainSlices(dvid_model* m, int f0, int height, int width) {
         const size_t fo = (size_t)f0, px = (size_t)height * width, px4 = px / 16, big = fo * px4 * 256;
         img = m->img8.as<T>() + fo * px * (16 / sizeof(T));          // NHWC8 fp16 / NHWC4 fp32: 16 bytes per pixel
@@ -119,17 +120,19 @@ struct ChainSlices {
         t1 = m->bufT1.as<T>() + big;
         t2 = m->bufT2.as<T>() + big;
         sc = m->bufSC.as<T>() + big;
-        stage_out[0] = nullptr;
+        const bool p2 = m->fpn_levels == 4;
+        stage_out[0] = p2 ? m->c2.as<T>() + big : nullptr;
         stage_out[1] = m->c3.as<T>() + fo * (px4 / 4) * 512;
         stage_out[2] = m->c4.as<T>() + fo * (px4 / 16) * 1024;
         stage_out[3] = m->c5.as<T>() + fo * (px4 / 64) * 2048;
-        for (int l = 0; l < 3; ++l) lat[l] = m->lat[l].as<T>() + fo * (px4 / (4 << (2 * l))) * 256;
+        lat[0] = p2 ? m->lat[0].as<T>() + big : nullptr;
+        for (int l = 1; l < 4; ++l) lat[l] = m->lat[l].as<T>() + fo * (px4 >> (2 * l)) * 256;
     }
 };
 
 // detectron2 build_resnet_fpn_backbone with DTYPE float32: normaliser -> NHWC4, BasicStem (7x7 / 2 + FrozenBN folded + ReLU + max pool),
 // the bottleneck stages layer by layer, FPN; every tensor fp32 (csrc/f32.hip; prep / max pool: csrc/elementwise.hip)
-int backbone_resnet_f32(dvid_model* m, const float* const* frames, int n, int height, int width, float* p3, float* p4, float* p5, hipStream_t s) {
+int backbone_resnet_f32(dvid_model* m, const float* const* frames, int n, int height, int width, float* const* pyr, hipStream_t s) {
     const PixelNorm px(m->cfg);
     return run_chains(m, n, s, [&](int f0, int nf, hipStream_t cs) -> int {
         const ChainSlices<float> k(m, f0, height, width);
@@ -165,13 +168,14 @@ int backbone_resnet_f32(dvid_model* m, const float* const* frames, int n, int he
             sh[st] = h;
             sw[st] = w;
         }
-        float* pout[3] = {p3 + (size_t)f0 * sh[1] * sw[1] * 256, p4 + (size_t)f0 * sh[2] * sw[2] * 256, p5 + (size_t)f0 * sh[3] * sw[3] * 256};
-        return run_fpn<float>(m, stage_out + 1, k.lat, pout, nf, sh + 1, sw + 1, cs);
+        float* pout[4];
+        for (int l = 0; l < 4; ++l) pout[l] = pyr[l] ? pyr[l] + (size_t)f0 * sh[l] * sw[l] * 256 : nullptr;
+        return run_fpn<float>(m, stage_out, k.lat, pout, nf, sh, sw, cs);
     });
 }
 
 // Swin-Transformer + FPN with DTYPE float32 (swintransformer.py:464-751): the fp16 path's launch sequence with fp32 operands everywhere
-int backbone_swin_f32(dvid_model* m, const float* const* frames, int n, int height, int width, float* p3, float* p4, float* p5, hipStream_t s) {
+int backbone_swin_f32(dvid_model* m, const float* const* frames, int n, int height, int width, float* const* pyr, hipStream_t s) {
     const PixelNorm px(m->cfg);
     float* img = m->img8.as<float>();
     TRY(dvid_f32_prep_images_launch(frames, img, n, height, width, px.mean, px.stdv, s));
@@ -184,7 +188,7 @@ int backbone_swin_f32(dvid_model* m, const float* const* frames, int n, int heig
     float* qkv = m->sw_qkv16.as<float>();
     float* attn = m->sw_attn16.as<float>();
     float* hid = m->sw_h16.as<float>();
-    float* stage_out[4] = {nullptr, m->c3.as<float>(), m->c4.as<float>(), m->c5.as<float>()};
+    float* stage_out[4] = {m->c2.as<float>(), m->c3.as<float>(), m->c4.as<float>(), m->c5.as<float>()};          // (c2: null without the p2 level, and stage 0 has no out norm then)
     const int ws = m->cfg.swin_window;                           // 7 or 12 (dvid_model_finalize)
     int sh[4], sw[4];
     for (int st = 0; st < 4; ++st) {
@@ -217,14 +221,13 @@ int backbone_swin_f32(dvid_model* m, const float* const* frames, int n, int heig
             x2 = t;
         }
     }
-    float* lat[3] = {m->lat[0].as<float>(), m->lat[1].as<float>(), m->lat[2].as<float>()};
-    float* pout[3] = {p3, p4, p5};
-    return run_fpn<float>(m, stage_out + 1, lat, pout, n, sh + 1, sw + 1, s);
+    float* lat[4] = {m->lat[0].as<float>(), m->lat[1].as<float>(), m->lat[2].as<float>(), m->lat[3].as<float>()};
+    return run_fpn<float>(m, stage_out, lat, pyr, n, sh, sw, s);
 }
 
 // detectron2 build_resnet_fpn_backbone (DTYPE float16): normaliser, stem + max pool, the bottleneck stages (res2 / res3 on the fused
 // block kernels where their shape rules pick them), FPN; fp16 NHWC
-int backbone_resnet_f16(dvid_model* m, const float* const* frames, int n, int height, int width, half_t* p3, half_t* p4, half_t* p5, hipStream_t s) {
+int backbone_resnet_f16(dvid_model* m, const float* const* frames, int n, int height, int width, half_t* const* pyr, hipStream_t s) {
     const PixelNorm px(m->cfg);
     return run_chains(m, n, s, [&](int f0, int nf, hipStream_t cs) -> int {
         const ChainSlices<half_t> k(m, f0, height, width);
@@ -276,7 +279,7 @@ int backbone_resnet_f16(dvid_model* m, const float* const* frames, int n, int he
                 for (int b = 0; b < nb; ++b) {
                     const Block& blk = m->blocks[0][b];
                     const Block* nxt = b + 1 < nb ? &m->blocks[0][b + 1] : r3;
-                    half_t* dst = cur == bx ? by : bx;
+                    half_t* dst = (b == nb - 1 && stage_out[0]) ? stage_out[0] : (cur == bx ? by : bx);          // (c2, with the p2 level)
                     TRY(bneck_tail(ta, blk.c2.w, blk.c2.bias, blk.c3.w, blk.c3.bias, cur, blk.has_sc ? blk.sc.w : nullptr,
                                    blk.has_sc ? blk.sc.bias : nullptr, nxt ? nxt->c1.w : nullptr, nxt ? nxt->c1.bias : nullptr,
                                    nxt ? nxt->c1.cout : 0, dst, nxt ? tb : nullptr, nf, h, w, cs));
@@ -344,13 +347,14 @@ int backbone_resnet_f16(dvid_model* m, const float* const* frames, int n, int he
             sw[st] = w;
         }
         // FPN: outputs go to the caller's [n, ...] tensors at this chain's frame offset
-        half_t* pout[3] = {p3 + (size_t)f0 * sh[1] * sw[1] * 256, p4 + (size_t)f0 * sh[2] * sw[2] * 256, p5 + (size_t)f0 * sh[3] * sw[3] * 256};
-        return run_fpn<half_t>(m, stage_out + 1, k.lat, pout, nf, sh + 1, sw + 1, cs);
+        half_t* pout[4];
+        for (int l = 0; l < 4; ++l) pout[l] = pyr[l] ? pyr[l] + (size_t)f0 * sh[l] * sw[l] * 256 : nullptr;
+        return run_fpn<half_t>(m, stage_out, k.lat, pout, nf, sh, sw, cs);
     });
 }
 
 // Swin-Transformer + FPN (DTYPE float16, swintransformer.py:464-751): fp32 token stream, fp16 MFMA operands
-int backbone_swin_f16(dvid_model* m, const float* const* frames, int n, int height, int width, half_t* p3, half_t* p4, half_t* p5, hipStream_t s) {
+int backbone_swin_f16(dvid_model* m, const float* const* frames, int n, int height, int width, half_t* const* pyr, hipStream_t s) {
     const PixelNorm px(m->cfg);
     TRY(dvid_prep_images_launch(frames, m->img8.as<half_t>(), n, height, width, px.mean, px.inv_std, s));
     // patch embedding: 4x4/4 conv (implicit GEMM on NHWC8) -> fp32 tokens -> LayerNorm  (swintransformer.py:441-458)
@@ -363,7 +367,7 @@ int backbone_swin_f16(dvid_model* m, const float* const* frames, int n, int heig
     half_t* qkv16 = m->sw_qkv16.as<half_t>();
     half_t* attn16 = m->sw_attn16.as<half_t>();
     half_t* h16 = m->sw_h16.as<half_t>();
-    half_t* stage_out[4] = {nullptr, m->c3.as<half_t>(), m->c4.as<half_t>(), m->c5.as<half_t>()};
+    half_t* stage_out[4] = {m->c2.as<half_t>(), m->c3.as<half_t>(), m->c4.as<half_t>(), m->c5.as<half_t>()};          // (c2: null without the p2 level, and stage 0 has no out norm then)
     const int ws = m->cfg.swin_window;                           // 7 or 12 (dvid_model_finalize)
     int sh[4], sw[4];
     for (int st = 0; st < 4; ++st) {
@@ -394,17 +398,17 @@ int backbone_swin_f16(dvid_model* m, const float* const* frames, int n, int heig
             x2 = t;
         }
     }
-    half_t* lat[3] = {m->lat[0].as<half_t>(), m->lat[1].as<half_t>(), m->lat[2].as<half_t>()};
-    half_t* pout[3] = {p3, p4, p5};
-    return run_fpn<half_t>(m, stage_out + 1, lat, pout, n, sh + 1, sw + 1, s);
+    half_t* lat[4] = {m->lat[0].as<half_t>(), m->lat[1].as<half_t>(), m->lat[2].as<half_t>(), m->lat[3].as<half_t>()};
+    return run_fpn<half_t>(m, stage_out, lat, pyr, n, sh, sw, s);
 }
 
 // ---- entry points: the checks, the precision switch and the contiguous-images form, once for both backbones ----------------------------
-typedef int (*BackboneF16)(dvid_model*, const float* const*, int, int, int, half_t*, half_t*, half_t*, hipStream_t);
-typedef int (*BackboneF32)(dvid_model*, const float* const*, int, int, int, float*, float*, float*, hipStream_t);
+// (pyr: the outputs by stage, [0] = p2 or null .. [3] = p5)
+typedef int (*BackboneF16)(dvid_model*, const float* const*, int, int, int, half_t* const*, hipStream_t);
+typedef int (*BackboneF32)(dvid_model*, const float* const*, int, int, int, float* const*, hipStream_t);
 
 int backbone_frames(dvid_model* m, int type, const char* missing, BackboneF16 f16, BackboneF32 f32, const float* const* frames, int n, int height,
-                    int width, void* p3, void* p4, void* p5, void* stream) {
+                    int width, void* const* levels, int n_levels, void* stream) {
     g_err[0] = 0;
     if (!frames || n <= 0) FAIL(DVID_ERR_ARG, "no frames");
     if (!m || !m->finalized || !m->has_backbone || m->cfg.backbone_type != type) FAIL(DVID_ERR_STATE, "%s", missing);
@@ -412,10 +416,25 @@ int backbone_frames(dvid_model* m, int type, const char* missing, BackboneF16 f1
     if (n > m->ws_frames || height > m->ws_h || width > m->ws_w || height % 32 || width % 32)
         FAIL(DVID_ERR_STATE, "workspace reserved for %d frames of up to %dx%d, got %d of %dx%d", m->ws_frames, m->ws_h, m->ws_w, n,
              height, width);
+    if (!pyramid_ok(levels, n_levels) || n_levels != m->fpn_levels)
+        FAIL(DVID_ERR_ARG, "the model's backbone makes %d levels: levels must hold that many maps, finest first (got n_levels %d)", m->fpn_levels, n_levels);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (m->precision == 1)          // DTYPE float32: p3 / p4 / p5 are fp32 NHWC
-        return f32(m, frames, n, height, width, reinterpret_cast<float*>(p3), reinterpret_cast<float*>(p4), reinterpret_cast<float*>(p5), s);
-    return f16(m, frames, n, height, width, reinterpret_cast<half_t*>(p3), reinterpret_cast<half_t*>(p4), reinterpret_cast<half_t*>(p5), s);
+    void* pyr[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int l = 0; l < n_levels; ++l) pyr[4 - n_levels + l] = levels[l];
+    if (m->precision == 1)          // DTYPE float32: the maps are fp32 NHWC
+        return f32(m, frames, n, height, width, reinterpret_cast<float* const*>(pyr), s);
+    return f16(m, frames, n, height, width, reinterpret_cast<half_t* const*>(pyr), s);
+}
+
+// the three-pointer entries: the array form with n_levels 3, refused by a model that has the p2 level
+typedef int (*LevelsEntry)(dvid_model*, const float* const*, int, int, int, void* const*, int, void*);
+int backbone_three(LevelsEntry run, dvid_model* m, const float* const* frames, int n, int height, int width, void* p3, void* p4, void* p5, void* stream) {
+    if (m && m->finalized && m->has_backbone && m->fpn_levels == 4) {
+        g_err[0] = 0;
+        FAIL(DVID_ERR_STATE, "the model has the p2 level (backbone.fpn_lateral2): call the _levels_frames form of this entry with four maps");
+    }
+    void* levels[3] = {p3, p4, p5};
+    return run(m, frames, n, height, width, levels, 3, stream);
 }
 
 // contiguous [n, 3, height, width] images as a frame table
@@ -438,8 +457,12 @@ int dvid_backbone_resnet_fpn(dvid_model* m, const float* images, int n, int heig
 }
 int dvid_backbone_resnet_fpn_frames(dvid_model* m, const float* const* frames, int n, int height, int width, void* p3, void* p4, void* p5,
                                     void* stream) {
+    return backbone_three(dvid_backbone_resnet_fpn_levels_frames, m, frames, n, height, width, p3, p4, p5, stream);
+}
+int dvid_backbone_resnet_fpn_levels_frames(dvid_model* m, const float* const* frames, int n, int height, int width, void* const* levels,
+                                           int n_levels, void* stream) {
     return backbone_frames(m, 0, "model not finalized or built without a ResNet backbone", backbone_resnet_f16, backbone_resnet_f32, frames, n, height,
-                           width, p3, p4, p5, stream);
+                           width, levels, n_levels, stream);
 }
 
 int dvid_backbone_swin_fpn(dvid_model* m, const float* images, int n, int height, int width, void* p3, void* p4, void* p5,
@@ -448,6 +471,10 @@ int dvid_backbone_swin_fpn(dvid_model* m, const float* images, int n, int height
 }
 int dvid_backbone_swin_fpn_frames(dvid_model* m, const float* const* frames, int n, int height, int width, void* p3, void* p4, void* p5,
                                   void* stream) {
-    return backbone_frames(m, 1, "model has no Swin backbone", backbone_swin_f16, backbone_swin_f32, frames, n, height, width, p3, p4, p5, stream);
+    return backbone_three(dvid_backbone_swin_fpn_levels_frames, m, frames, n, height, width, p3, p4, p5, stream);
+}
+int dvid_backbone_swin_fpn_levels_frames(dvid_model* m, const float* const* frames, int n, int height, int width, void* const* levels,
+                                         int n_levels, void* stream) {
+    return backbone_frames(m, 1, "model has no Swin backbone", backbone_swin_f16, backbone_swin_f32, frames, n, height, width, levels, n_levels, stream);
 }
 }  // extern "C"

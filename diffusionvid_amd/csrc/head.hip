@@ -5,7 +5,7 @@
 namespace {
 // One RCNNHead / RCNNHead_cond pass over `nf` frames of `M` boxes on stream `s`; ss_dev = the frames' scale / shift rows, `ss_stride`
 // floats apart (0: every frame reads the one (head, t) row).
-int rcnn_head_chain(dvid_model* m, const HeadW& hw, int is_cond, const void* p3, const void* p4, const void* p5, int nf, int height, int width,
+int rcnn_head_chain(dvid_model* m, const HeadW& hw, int is_cond, const void* const* levels, int n_levels, int nf, int height, int width,
                     int M, const float* boxes, const float* pro_features, const float* cond, float* logits, float* boxes_out,
                     float* obj_features, int* bad_box_flag, const float* ss_dev, int ss_stride, hipStream_t s) {
     const int d = m->cfg.hidden_dim, R = nf * M;
@@ -27,16 +27,16 @@ int rcnn_head_chain(dvid_model* m, const HeadW& hw, int is_cond, const void* p3,
     half_t* vt = m->vt.as<half_t>();
 
     // --- RoIAlign ---
-    const RoiLevels lv = roi_levels<half_t>(p3, p4, p5, height, width, 0, d);
+    const RoiLevels lv = roi_levels<half_t>(levels, n_levels, height, width, 0, d);
     float* pro32 = f32a;
     // A pass that gets its proposal features from the caller needs nothing of the tile before DynamicConv: the gather then runs INSIDE the
     // DynamicConv launch (csrc/dynconv.hip, FUSED_ROI) and the fp16 tile never reaches memory.  A pass without them takes the tile's mean
     // over the bins as its features (box_head.py:509-510) ahead of the self-attention: the two launches.
     const bool roi_fused = g_opt.roi_fuse && pro_features != nullptr && d == 256;
     double map_px = 0;
-    for (int l = 0; l < 3; ++l) map_px += (double)lv.h[l] * lv.w[l];
+    for (int l = 0; l < lv.n_levels; ++l) map_px += (double)lv.h[l] * lv.w[l];
     if (!roi_fused) {
-        // algorithmic bytes: the three maps of the launch's frames once + one 49 x d tile per box (the 784 taps per box go through L1)
+        // algorithmic bytes: the pyramid's maps of the launch's frames once + one 49 x d tile per box (the 784 taps per box go through L1)
         TRY(prof_other("roialign", R, d, 49, 0.0, (double)nf * map_px * d * 2.0 + (double)R * 49 * d * 2.0, s,
                        [&] { return dvid_roialign_launch(lv, d, boxes, nf, M, roi16, pro_features ? nullptr : pro32, s); }));
     }
@@ -168,7 +168,7 @@ int rcnn_head_chain(dvid_model* m, const HeadW& hw, int is_cond, const void* p3,
 }
 
 // The same pass with DTYPE float32 (the f32_* kernels of csrc/roialign.hip, attention.hip, dynconv.hip, elementwise.hip; csrc/f32.hip for the layers): fp32 RoI tiles, q / k / v, dynamic parameters, hidden layers; layer by layer.
-int rcnn_head_chain_f32(dvid_model* m, const HeadW& hw, int is_cond, const void* p3, const void* p4, const void* p5, int nf, int height, int width,
+int rcnn_head_chain_f32(dvid_model* m, const HeadW& hw, int is_cond, const void* const* levels, int n_levels, int nf, int height, int width,
                         int M, const float* boxes, const float* pro_features, const float* cond, float* logits, float* boxes_out,
                         float* obj_features, int* bad_box_flag, const float* ss_dev, int ss_stride, hipStream_t s) {
     const int d = m->cfg.hidden_dim, R = nf * M, dd = m->cfg.dim_dynamic;
@@ -186,9 +186,9 @@ int rcnn_head_chain_f32(dvid_model* m, const HeadW& hw, int is_cond, const void*
     float* hid = m->hid16.as<float>();
     float* deltas = m->deltas.as<float>();
 
-    const RoiLevels32 lv = roi_levels<float>(p3, p4, p5, height, width, 0, d);
+    const RoiLevels32 lv = roi_levels<float>(levels, n_levels, height, width, 0, d);
     double map_px = 0;
-    for (int l = 0; l < 3; ++l) map_px += (double)lv.h[l] * lv.w[l];
+    for (int l = 0; l < lv.n_levels; ++l) map_px += (double)lv.h[l] * lv.w[l];
     float* pro32 = f32a;
     TRY(prof_other("roialign_f32", R, d, 49, 0.0, (double)nf * map_px * d * 4.0 + (double)R * 49 * d * 4.0, s,
                    [&] { return dvid_f32_roialign_launch(lv, d, boxes, nf, M, roi, pro_features ? nullptr : pro32, s); }));
@@ -278,7 +278,22 @@ int dvid_rcnn_head(dvid_model* m, int head_index, int is_cond, const void* p3, c
                    const int64_t* t, const float* cond, float* logits, float* boxes_out, float* obj_features,
                    int* bad_box_flag, void* stream) {
     g_err[0] = 0;
+    if (m && m->finalized && m->has_backbone && m->fpn_levels == 4)
+        FAIL(DVID_ERR_STATE, "the model has the p2 level (backbone.fpn_lateral2): call dvid_rcnn_head_levels with its four maps");
+    const void* levels[3] = {p3, p4, p5};
+    return dvid_rcnn_head_levels(m, head_index, is_cond, levels, 3, n_frames, height, width, boxes_per_frame, boxes, pro_features, t, cond, logits,
+                                 boxes_out, obj_features, bad_box_flag, stream);
+}
+
+int dvid_rcnn_head_levels(dvid_model* m, int head_index, int is_cond, const void* const* levels, int n_levels, int n_frames,
+                          int height, int width, int boxes_per_frame, const float* boxes, const float* pro_features,
+                          const int64_t* t, const float* cond, float* logits, float* boxes_out, float* obj_features,
+                          int* bad_box_flag, void* stream) {
+    g_err[0] = 0;
     if (!m || !m->finalized) FAIL(DVID_ERR_STATE, "model not finalized");
+    if (!pyramid_ok(levels, n_levels)) FAIL(DVID_ERR_ARG, "the pyramid is 3 maps (p3..p5) or 4 (p2..p5), none of them null (got n_levels %d)", n_levels);
+    if (m->has_backbone && n_levels != m->fpn_levels)
+        FAIL(DVID_ERR_ARG, "n_levels %d, but the model's backbone makes %d levels", n_levels, m->fpn_levels);
     const std::vector<HeadW>& hv = is_cond ? m->heads_cond : m->heads;
     if (head_index < 0 || head_index >= (int)hv.size()) FAIL(DVID_ERR_ARG, "head_index %d out of range", head_index);
     if (is_cond && !cond) FAIL(DVID_ERR_ARG, "RCNNHead_cond needs cond");
@@ -342,9 +357,9 @@ int dvid_rcnn_head(dvid_model* m, int head_index, int is_cond, const void* p3, c
     // One launch sequence on the caller's stream.  (Frames are independent inside a head, but two sub-batch chains on two streams
     // measured slower -- 0.53 against 0.49 ms per pass, tools/bench_head.py -- the switch that kept that path is gone.)
     if (m->precision == 1)
-        return rcnn_head_chain_f32(m, hw, is_cond, p3, p4, p5, n_frames, height, width, M, boxes, pro_features, cond, logits, boxes_out, obj_features,
+        return rcnn_head_chain_f32(m, hw, is_cond, levels, n_levels, n_frames, height, width, M, boxes, pro_features, cond, logits, boxes_out, obj_features,
                                    bad_box_flag, ss_dev, ss_stride, s);
-    return rcnn_head_chain(m, hw, is_cond, p3, p4, p5, n_frames, height, width, M, boxes, pro_features, cond, logits, boxes_out, obj_features,
+    return rcnn_head_chain(m, hw, is_cond, levels, n_levels, n_frames, height, width, M, boxes, pro_features, cond, logits, boxes_out, obj_features,
                            bad_box_flag, ss_dev, ss_stride, s);
 }
 

@@ -73,11 +73,12 @@ int dvid_modulate_launch(const float* x, const float* scale, int scale_ld, const
 int dvid_silu_f16_launch(const float* x, half_t* y, long n, hipStream_t s);
 
 // roialign.hip
-template <typename T>          // the three FPN levels' maps: fp16 (RoiLevels) or fp32 (RoiLevels32)
-struct RoiLevelsT {
-    const T* feat[3];
-    int h[3], w[3];
-    float scale[3];
+template <typename T>          // the pyramid's maps, finest first: fp16 (RoiLevels) or fp32 (RoiLevels32).  Three levels p3..p5
+struct RoiLevelsT {            // (min_level 3) or four, p2..p5 (min_level 2): index l is level min_level + l (runtime.h: roi_levels)
+    const T* feat[4];
+    int h[4], w[4];
+    float scale[4];
+    int min_level, n_levels;
 };
 using RoiLevels = RoiLevelsT<half_t>;
 using RoiLevels32 = RoiLevelsT<float>;

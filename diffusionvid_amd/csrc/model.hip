@@ -108,7 +108,7 @@ int linear_run32(const ConvW& w, const float* in, int rows, float* out, int relu
 
 extern "C" {
 const char* dvid_last_error(void) { return g_err; }
-int dvid_version(void) { return 1; }
+int dvid_version(void) { return 2; }
 
 int dvid_model_create(const dvid_config* cfg, dvid_model** out) {
     g_err[0] = 0;
@@ -132,8 +132,8 @@ int dvid_model_create(const dvid_config* cfg, dvid_model** out) {
 int dvid_model_destroy(dvid_model* m) {
     if (!m) return DVID_OK;
     for (void* p : m->owned) (void)hipFree(p);
-    DevBuf* bufs[] = {&m->img8, &m->bufX, &m->bufY, &m->bufT1, &m->bufT2, &m->bufSC, &m->c3, &m->c4, &m->c5, &m->lat[0], &m->sw_x, &m->sw_x2, &m->sw_ln16, &m->sw_qkv16, &m->sw_attn16, &m->sw_h16,
-                      &m->lat[1], &m->lat[2], &m->roi, &m->params, &m->dyn, &m->qkv, &m->attn16, &m->f32a, &m->f32b, &m->f32c,
+    DevBuf* bufs[] = {&m->img8, &m->bufX, &m->bufY, &m->bufT1, &m->bufT2, &m->bufSC, &m->c2, &m->c3, &m->c4, &m->c5, &m->lat[0], &m->sw_x, &m->sw_x2, &m->sw_ln16, &m->sw_qkv16, &m->sw_attn16, &m->sw_h16,
+                      &m->lat[1], &m->lat[2], &m->lat[3], &m->roi, &m->params, &m->dyn, &m->qkv, &m->attn16, &m->f32a, &m->f32b, &m->f32c,
                       &m->f32d, &m->h16a, &m->h16b, &m->hid16, &m->ss, &m->deltas, &m->kvproj, &m->mem16, &m->splitk, &m->vt, &m->lkvproj, &m->lmem16};
     for (DevBuf* b : bufs) b->release();
     for (DevBuf& b : m->ss_slabs) b.release();
@@ -264,7 +264,11 @@ int dvid_workspace_reserve(dvid_model* m, int max_frames, int height, int width,
         TRY(m->c3.ensure(n * (px4 / 4) * (C0 * 2) * 2 * es, &m->ws_gen));
         TRY(m->c4.ensure(n * (px4 / 16) * (C0 * 4) * 2 * es, &m->ws_gen));
         TRY(m->c5.ensure(n * (px4 / 64) * (C0 * 8) * 2 * es, &m->ws_gen));
-        for (int l = 0; l < 3; ++l) TRY(m->lat[l].ensure(n * (px4 / (4 << (2 * l))) * 256 * 2 * es, &m->ws_gen));
+        for (int l = 1; l < 4; ++l) TRY(m->lat[l].ensure(n * (px4 >> (2 * l)) * 256 * 2 * es, &m->ws_gen));
+        if (m->fpn_levels == 4) {          // stage 0's normed output and the stride-4 lateral
+            TRY(m->c2.ensure(M0 * C0 * 2 * es, &m->ws_gen));
+            TRY(m->lat[0].ensure(n * px4 * 256 * 2 * es, &m->ws_gen));
+        }
     }
     if (m->has_backbone && m->cfg.backbone_type == 0) {
         TRY(m->img8.ensure(n * height * width * 8 * 2, &m->ws_gen));          // (fp32: NHWC4 = the same bytes)
@@ -277,7 +281,11 @@ int dvid_workspace_reserve(dvid_model* m, int max_frames, int height, int width,
         TRY(m->c3.ensure(n * (px4 / 4) * 512 * 2 * es, &m->ws_gen));
         TRY(m->c4.ensure(n * (px4 / 16) * 1024 * 2 * es, &m->ws_gen));
         TRY(m->c5.ensure(n * (px4 / 64) * 2048 * 2 * es, &m->ws_gen));
-        for (int l = 0; l < 3; ++l) TRY(m->lat[l].ensure(n * (px4 / (4 << (2 * l))) * 256 * 2 * es, &m->ws_gen));
+        for (int l = 1; l < 4; ++l) TRY(m->lat[l].ensure(n * (px4 >> (2 * l)) * 256 * 2 * es, &m->ws_gen));
+        if (m->fpn_levels == 4) {          // res2's output persists for the FPN, and the stride-4 lateral
+            TRY(m->c2.ensure(big, &m->ws_gen));
+            TRY(m->lat[0].ensure(big, &m->ws_gen));
+        }
     }
     const size_t R = n * boxes_per_frame;
     const int d = m->cfg.hidden_dim;

@@ -5,18 +5,34 @@
 extern "C" {
 int dvid_roialign_v2_multilevel(const void* p3, const void* p4, const void* p5, int n_frames, int height, int width, int channels,
                                 const float* boxes, int boxes_per_frame, void* roi_out, float* mean_out, void* stream) {
+    const void* levels[3] = {p3, p4, p5};
+    return dvid_roialign_v2_levels(levels, 3, n_frames, height, width, channels, boxes, boxes_per_frame, roi_out, mean_out, stream);
+}
+
+int dvid_roialign_v2_levels(const void* const* levels, int n_levels, int n_frames, int height, int width, int channels, const float* boxes,
+                            int boxes_per_frame, void* roi_out, float* mean_out, void* stream) {
     g_err[0] = 0;
+    if (!pyramid_ok(levels, n_levels)) FAIL(DVID_ERR_ARG, "the pyramid is 3 maps (p3..p5) or 4 (p2..p5), none of them null (got n_levels %d)", n_levels);
     if (height % 32 || width % 32) FAIL(DVID_ERR_ARG, "height/width must be multiples of 32");
-    TRY(dvid_roialign_launch(roi_levels<half_t>(p3, p4, p5, height, width, 0, channels), channels, boxes, n_frames, boxes_per_frame, reinterpret_cast<half_t*>(roi_out), mean_out,
-                             reinterpret_cast<hipStream_t>(stream)));
+    TRY(dvid_roialign_launch(roi_levels<half_t>(levels, n_levels, height, width, 0, channels), channels, boxes, n_frames, boxes_per_frame,
+                             reinterpret_cast<half_t*>(roi_out), mean_out, reinterpret_cast<hipStream_t>(stream)));
     return DVID_OK;
 }
 
 int dvid_roialign_v2_multilevel_f32(const float* p3, const float* p4, const float* p5, int n_frames, int height, int width, int channels,
                                     const float* boxes, int boxes_per_frame, float* roi_out, float* mean_out, void* stream) {
+    const float* levels[3] = {p3, p4, p5};
+    return dvid_roialign_v2_levels_f32(levels, 3, n_frames, height, width, channels, boxes, boxes_per_frame, roi_out, mean_out, stream);
+}
+
+int dvid_roialign_v2_levels_f32(const float* const* levels, int n_levels, int n_frames, int height, int width, int channels, const float* boxes,
+                                int boxes_per_frame, float* roi_out, float* mean_out, void* stream) {
     g_err[0] = 0;
+    const void* const* lp = reinterpret_cast<const void* const*>(levels);
+    if (!pyramid_ok(lp, n_levels)) FAIL(DVID_ERR_ARG, "the pyramid is 3 maps (p3..p5) or 4 (p2..p5), none of them null (got n_levels %d)", n_levels);
     if (height % 32 || width % 32) FAIL(DVID_ERR_ARG, "height/width must be multiples of 32");
-    TRY(dvid_f32_roialign_launch(roi_levels<float>(p3, p4, p5, height, width, 0, channels), channels, boxes, n_frames, boxes_per_frame, roi_out, mean_out, reinterpret_cast<hipStream_t>(stream)));
+    TRY(dvid_f32_roialign_launch(roi_levels<float>(lp, n_levels, height, width, 0, channels), channels, boxes, n_frames, boxes_per_frame, roi_out, mean_out,
+                                 reinterpret_cast<hipStream_t>(stream)));
     return DVID_OK;
 }
 

@@ -63,14 +63,15 @@ __device__ __forceinline__ Tap axis_tap(float y, int limit) {
     return t;
 }
 
-// detectron2 assign_boxes_to_levels (canonical 224 / level 4, levels 3..5) -> index 0..2 into the pyramid.  NaN / negative area:
-// upstream matches no level -> `valid` false (the callers write zeros).  No multiply here feeds an add: contraction cannot change it.
-__device__ __forceinline__ int box_level(float bx1, float by1, float bx2, float by2, bool& valid) {
+// detectron2 assign_boxes_to_levels (canonical 224 / level 4, levels min_level..5 with min_level 3 or 2) -> index into the pyramid,
+// 0 = its finest map.  NaN / negative area: upstream matches no level -> `valid` false (the callers write zeros).  No multiply here
+// feeds an add: contraction cannot change it.
+__device__ __forceinline__ int box_level(float bx1, float by1, float bx2, float by2, int min_level, bool& valid) {
     const float area = (bx2 - bx1) * (by2 - by1);
     valid = area >= 0.f;
     float lvf = floorf(4.f + log2f(sqrtf(area) / 224.f + 1e-8f));
-    lvf = fminf(fmaxf(lvf, 3.f), 5.f);
-    return valid ? (int)lvf - 3 : 0;
+    lvf = fminf(fmaxf(lvf, (float)min_level), 5.f);
+    return valid ? (int)lvf - min_level : 0;
 }
 
 // Bins p = grp, grp + 8, ... of box `box` for the 8 channels [8 ln, 8 ln + 8): sink(p, half8) receives each finished bin; macc
@@ -81,7 +82,7 @@ __device__ __forceinline__ void gather_box(const RoiLevels& lv, const float* __r
     const int img = box / boxes_per_img;
     const float bx1 = boxes[box * 4 + 0], by1 = boxes[box * 4 + 1], bx2 = boxes[box * 4 + 2], by2 = boxes[box * 4 + 3];
     bool valid_box;
-    const int level = box_level(bx1, by1, bx2, by2, valid_box);
+    const int level = box_level(bx1, by1, bx2, by2, lv.min_level, valid_box);
 
     const half_t* feat = lv.feat[level];
     const int H = lv.h[level], W = lv.w[level];

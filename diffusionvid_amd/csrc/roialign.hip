@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void f32_roialign_kernel(RoiLevels32 lv, const
     const int grp = tid >> 5, ln = tid & 31;
     const float bx1 = boxes[box * 4 + 0], by1 = boxes[box * 4 + 1], bx2 = boxes[box * 4 + 2], by2 = boxes[box * 4 + 3];
     bool valid_box;
-    const int level = box_level(bx1, by1, bx2, by2, valid_box);
+    const int level = box_level(bx1, by1, bx2, by2, lv.min_level, valid_box);
     const int H = lv.h[level], W = lv.w[level];
     const float sc = lv.scale[level];
     const float* feat = lv.feat[level] + (long)img * H * W * 256;

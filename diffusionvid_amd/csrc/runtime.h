@@ -188,7 +188,8 @@ struct dvid_model {
     ConvW stem, stem_s2d;      // NHWC8 7x7/2 form and the 2x2 space-to-depth 4x4/1 form of the same layer
     bool use_s2d = true;       // dvid_set_stem_layout(m, 0): the NHWC8 form
     std::vector<Block> blocks[4];
-    ConvW lateral[3], output[3];  // index 0 -> level 3
+    int fpn_levels = 3;           // 3: p3..p5; 4: p2..p5 (backbone.fpn_lateral2.weight was set, dvid_model_finalize)
+    ConvW lateral[4], output[4];  // index 0 -> level 2 (used when fpn_levels == 4), 1..3 -> levels 3..5
     // Swin backbone (backbone_type 1)
     ConvW swin_patch;
     LNW swin_patch_norm;
@@ -208,7 +209,7 @@ struct dvid_model {
 
     // workspace
     int ws_frames = 0, ws_h = 0, ws_w = 0, ws_boxes = 0;
-    DevBuf img8, bufX, bufY, bufT1, bufT2, bufSC, c3, c4, c5, lat[3];
+    DevBuf img8, bufX, bufY, bufT1, bufT2, bufSC, c2, c3, c4, c5, lat[4];          // c2, lat[0]: models with the p2 level only
     DevBuf sw_x, sw_x2, sw_ln16, sw_qkv16, sw_attn16, sw_h16;   // Swin token buffers
     DevBuf roi, params, dyn, qkv, attn16, f32a, f32b, f32c, f32d, h16a, h16b, hid16, ss, deltas, kvproj, mem16, splitk, vt;
     // (head slot, t) -> device scale/shift row [bt_out], sub-allocated from slabs of kSsSlabRows rows (a sampler that walks all
@@ -278,19 +279,28 @@ struct ConvOpts32 {
 int conv_run32(const ConvW& w, const float* in, int n, int h, int wd, float* out, hipStream_t s, const ConvOpts32& o = {});
 int linear_run32(const ConvW& w, const float* in, int rows, float* out, int relu, hipStream_t s, int ldc = 0);
 
-// The three FPN levels (strides 8 / 16 / 32) of a `height` x `width` image as RoIAlign reads them, starting at frame `frame_offset` of
-// each [n, h, w, channels] map
+// The FPN levels of a `height` x `width` image as RoIAlign reads them (detectron2 ROIPooler as built at box_head.py:250-271), finest
+// first and ending at p5: n_levels 3 = p3..p5 (strides 8 / 16 / 32), 4 = p2..p5 (strides 4 .. 32); starting at frame `frame_offset` of
+// each [n, h, w, channels] map.  The callers have checked n_levels (pyramid_ok).
 template <typename T>
-RoiLevelsT<T> roi_levels(const void* p3, const void* p4, const void* p5, int height, int width, size_t frame_offset, int channels) {
-    RoiLevelsT<T> lv;
-    const void* pl[3] = {p3, p4, p5};
-    for (int l = 0; l < 3; ++l) {
-        lv.h[l] = height >> (3 + l);
-        lv.w[l] = width >> (3 + l);
-        lv.feat[l] = reinterpret_cast<const T*>(pl[l]) + frame_offset * lv.h[l] * lv.w[l] * channels;
-        lv.scale[l] = 1.f / (float)(8 << l);
+RoiLevelsT<T> roi_levels(const void* const* levels, int n_levels, int height, int width, size_t frame_offset, int channels) {
+    RoiLevelsT<T> lv = {};
+    lv.n_levels = n_levels;
+    lv.min_level = 6 - n_levels;
+    for (int l = 0; l < n_levels; ++l) {
+        const int stride = 4 << (lv.min_level - 2 + l);
+        lv.h[l] = height / stride;
+        lv.w[l] = width / stride;
+        lv.feat[l] = reinterpret_cast<const T*>(levels[l]) + frame_offset * lv.h[l] * lv.w[l] * channels;
+        lv.scale[l] = 1.f / (float)stride;
     }
     return lv;
+}
+inline bool pyramid_ok(const void* const* levels, int n_levels) {
+    if (!levels || (n_levels != 3 && n_levels != 4)) return false;
+    for (int l = 0; l < n_levels; ++l)
+        if (!levels[l]) return false;
+    return true;
 }
 
 #pragma GCC visibility pop

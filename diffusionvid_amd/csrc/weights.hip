@@ -296,6 +296,8 @@ int dvid_model_finalize(dvid_model* m) {
     if (m->finalized) return DVID_OK;
     const dvid_config& c = m->cfg;
     m->has_backbone = c.backbone_type == 1 ? c.swin_depths[0] > 0 : c.res_blocks[0] > 0;
+    // the p2 level: present when its lateral is (as the attention stages below); the rest of the level's tensors are then needed
+    const int fpn_levels = m->get("backbone.fpn_lateral2.weight") ? 4 : 3;
     if (m->has_backbone && c.backbone_type == 0) {
         const std::string bu = "backbone.bottom_up.";
         TRY(make_conv_bn(m, bu + "stem.conv1", 2, 3, 8, &m->stem));
@@ -356,14 +358,15 @@ int dvid_model_finalize(dvid_model* m) {
                 TRY(make_ln(m, p + ".norm", &S.down_norm));
                 TRY(make_linear(m, p + ".reduction", false, &S.down_red));
             }
-            S.has_out = st >= 1;                       // out_indices (1, 2, 3)
+            S.has_out = st >= 1 || fpn_levels == 4;          // out_indices (1, 2, 3), or (0, 1, 2, 3) with the p2 level
             if (S.has_out) TRY(make_ln(m, bu + "norm" + std::to_string(st), &S.out_norm));
         }
     }
     if (m->has_backbone) {
-        for (int l = 0; l < 3; ++l) {
-            const std::string lat = "backbone.fpn_lateral" + std::to_string(l + 3);
-            const std::string outn = "backbone.fpn_output" + std::to_string(l + 3);
+        m->fpn_levels = fpn_levels;
+        for (int l = 4 - fpn_levels; l < 4; ++l) {
+            const std::string lat = "backbone.fpn_lateral" + std::to_string(l + 2);
+            const std::string outn = "backbone.fpn_output" + std::to_string(l + 2);
             NEED(lw, lat + ".weight");
             NEED(lb, lat + ".bias");
             NEED(ow, outn + ".weight");

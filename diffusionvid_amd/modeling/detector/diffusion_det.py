@@ -28,6 +28,7 @@ from ...structures.image_list import ImageList, to_image_list
 from ...utils import synthetic
 from ..roi_heads.box_head.box_head import DynamicHead
 
+_PYRAMIDS = (["p3", "p4", "p5"], ["p2", "p3", "p4", "p5"])          # MODEL.ROI_HEADS.IN_FEATURES values that are built
 _DEPTH_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
 # size2config of mega_core/modeling/backbone/swintransformer.py:655-712 (head dim 32 in all of them; the 384-pretrained sizes use
 # 12x12 windows)
@@ -124,17 +125,32 @@ class DiffusionDet(nn.Module):
                     "and GLOBAL.STOP_UPDATE_AFTER_INIT_TEST True (got %d, %d, %d, %d, %s)"
                     % (self.key_frame_location, self.all_frame_interval, self.infer_batch, mega.MAX_OFFSET,
                        mega.GLOBAL.STOP_UPDATE_AFTER_INIT_TEST))
-        if list(self.in_features) != ["p3", "p4", "p5"]:
-            raise NotImplementedError("ROI_HEADS.IN_FEATURES must be [p3, p4, p5] (configs/vid_*_DiffusionVID.yaml)")
+        # Two pyramids are built: p3..p5 over res3..res5 (the reference's configs/vid_*_DiffusionVID.yaml) and p2..p5 over res2..res5 (its
+        # default node, diffusion_det.py:155-159, and every published still-image DiffusionDet model).  The pooler's levels and the FPN's
+        # inputs must name the same one; every other combination is refused here, before any weight is made.
+        self.in_features = list(self.in_features)
+        if self.in_features not in _PYRAMIDS:
+            raise NotImplementedError("MODEL.ROI_HEADS.IN_FEATURES must be [p3, p4, p5] or [p2, p3, p4, p5], got %s (MODEL.FPN.IN_FEATURES %s)"
+                                      % (self.in_features, list(cfg.MODEL.FPN.IN_FEATURES)))
+        self.fpn_levels = tuple(int(f[1:]) for f in self.in_features)          # (3, 4, 5) or (2, 3, 4, 5)
         self.swin = None
         if cfg.MODEL.BACKBONE.NAME == "build_swintransformer_fpn_backbone":
             if cfg.MODEL.SWIN.SIZE not in _SWIN_SIZES:
                 raise NotImplementedError("Swin size %r is not built (known: %s)" % (cfg.MODEL.SWIN.SIZE, ", ".join(_SWIN_SIZES)))
-            if tuple(cfg.MODEL.SWIN.OUT_FEATURES) != (1, 2, 3):
-                raise NotImplementedError("MODEL.SWIN.OUT_FEATURES must be (1, 2, 3)")
+            want = tuple(l - 2 for l in self.fpn_levels)
+            if tuple(cfg.MODEL.SWIN.OUT_FEATURES) != want:
+                raise NotImplementedError("MODEL.ROI_HEADS.IN_FEATURES %s needs MODEL.SWIN.OUT_FEATURES %s, got %s"
+                                          % (self.in_features, want, tuple(cfg.MODEL.SWIN.OUT_FEATURES)))
+            if len(cfg.MODEL.FPN.IN_FEATURES) != len(want):
+                raise NotImplementedError("MODEL.ROI_HEADS.IN_FEATURES %s needs %d entries in MODEL.FPN.IN_FEATURES, got %s"
+                                          % (self.in_features, len(want), list(cfg.MODEL.FPN.IN_FEATURES)))
             self.swin = dict(getattr(cfg.MODEL.SWIN, "CONFIG_OVERRIDE", None) or _SWIN_SIZES[cfg.MODEL.SWIN.SIZE])
             self.res_blocks = (0, 0, 0, 0)
         elif cfg.MODEL.BACKBONE.NAME == "build_resnet_fpn_backbone":
+            want = ["res%d" % l for l in self.fpn_levels]
+            if list(cfg.MODEL.FPN.IN_FEATURES) != want:
+                raise NotImplementedError("MODEL.ROI_HEADS.IN_FEATURES %s needs MODEL.FPN.IN_FEATURES %s, got %s"
+                                          % (self.in_features, want, list(cfg.MODEL.FPN.IN_FEATURES)))
             if cfg.MODEL.RESNETS.DEPTH not in _DEPTH_BLOCKS or cfg.MODEL.RESNETS.STRIDE_IN_1X1:
                 raise NotImplementedError("ResNet depth %s / STRIDE_IN_1X1 unsupported" % cfg.MODEL.RESNETS.DEPTH)
             self.res_blocks = getattr(cfg.MODEL.RESNETS, "BLOCKS_OVERRIDE", None) or _DEPTH_BLOCKS[cfg.MODEL.RESNETS.DEPTH]
@@ -193,7 +209,8 @@ class DiffusionDet(nn.Module):
                                        num_cls=d.NUM_CLS, num_reg=d.NUM_REG, num_heads=d.NUM_HEADS,
                                        num_heads_cond=d.NUM_HEADS_LOCAL, pooler=cfg.MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION,
                                        prior_prob=d.PRIOR_PROB,
-                                       local_stages=int(cfg.MODEL.VID.ROI_BOX_HEAD.ATTENTION.STAGE) if self.local_box_enable else 0)
+                                       local_stages=int(cfg.MODEL.VID.ROI_BOX_HEAD.ATTENTION.STAGE) if self.local_box_enable else 0,
+                                       fpn_levels=self.fpn_levels)
         self.head = DynamicHead(cfg, None, engine_provider=self._get_engine)
         self.num_heads_local = self.head.num_heads_local
         self.top_k = self.head.top_k
@@ -796,7 +813,7 @@ class DiffusionDet(nn.Module):
                 return out
             out = {k: torch.cat([src[k][i0:i1] for src, i0, i1 in runs]) for k in keys}
             if with_feats:
-                out["feats"] = [torch.cat([src["feats"][l][i0:i1] for src, i0, i1 in runs]) for l in range(3)]
+                out["feats"] = [torch.cat([src["feats"][l][i0:i1] for src, i0, i1 in runs]) for l in range(len(self.in_features))]
             return out
 
         fired = on_global is None or not ref_g

@@ -91,7 +91,10 @@ class DynamicHead(nn.Module):
         eng = self._engine()
         feats = self._as_nhwc(features, eng)
         bs, num_boxes = init_bboxes.shape[:2]
-        height, width = feats[0].shape[1] * 8, feats[0].shape[2] * 8
+        if len(feats) not in (3, 4):
+            raise ops._lib.DvidError("DynamicHead: the pyramid is [p3, p4, p5] or [p2, p3, p4, p5], got %d maps" % len(feats))
+        stride = 32 >> (len(feats) - 1)          # of the finest map: 8 for p3..p5, 4 for p2..p5
+        height, width = feats[0].shape[1] * stride, feats[0].shape[2] * stride
         eng.reserve(max(bs, self.infer_batch), height, width, num_boxes)
         t_host = torch.as_tensor(t).to("cpu", torch.int64)
         flag = self._bad_flag(init_bboxes.device)

@@ -117,15 +117,30 @@ def linear_f32(x, w_packed, kpad, bias, relu=0, row_scale=None, w_split=None):
     return conv2d_nhwc_f32(x.view(rows, 1, 1, k), w_packed, kpad, bias, w_packed.shape[0], 1, 1, 1, 0, relu=relu, row_scale=row_scale, w_split=w_split).view(rows, -1)
 
 
+def _pyramid(feats_nhwc, height, width, what):
+    """The maps as the `levels, n_levels` arguments of the library's _levels entries: three maps p3..p5 or four p2..p5, finest first;
+    the finest map decides the stride (8 or 4) and every map must have its level's size."""
+    feats = list(feats_nhwc)
+    if len(feats) not in (3, 4):
+        raise _lib.DvidError(f"{what}: the pyramid is 3 maps (p3, p4, p5) or 4 (p2, p3, p4, p5), got {len(feats)}")
+    stride = 32 >> (len(feats) - 1)
+    for l, f in enumerate(feats):
+        if f.dim() != 4 or f.shape[1] * (stride << l) != height or f.shape[2] * (stride << l) != width:
+            raise _lib.DvidError(f"{what}: map {l} of {len(feats)} must be NHWC at stride {stride << l} of the {height} x {width} image "
+                                 f"(height / feats[0].shape[1] is {stride} for {len(feats)} maps), got shape {tuple(f.shape)}")
+    return (C.c_void_p * len(feats))(*[ptr(f) for f in feats]), len(feats)
+
+
 def roialign_f32(feats_nhwc, boxes, height, width, want_mean=False):
-    """feats_nhwc: [p3, p4, p5] fp32 NHWC; boxes fp32 [n, M, 4] -> roi fp32 [n*M, 49, C] (+ mean fp32 [n*M, C])."""
-    p3, p4, p5 = (_cuda(f, torch.float32) for f in feats_nhwc)
+    """feats_nhwc: [p3, p4, p5] or [p2, p3, p4, p5] fp32 NHWC; boxes fp32 [n, M, 4] -> roi fp32 [n*M, 49, C] (+ mean fp32 [n*M, C])."""
+    feats = [_cuda(f, torch.float32) for f in feats_nhwc]
+    levels, nl = _pyramid(feats, height, width, "roialign_f32")
     boxes = _cuda(boxes, torch.float32)
     n, M = boxes.shape[:2]
-    c = p3.shape[-1]
+    c = feats[0].shape[-1]
     roi = torch.empty((n * M, 49, c), dtype=torch.float32, device=boxes.device)
     mean = torch.empty((n * M, c), dtype=torch.float32, device=boxes.device) if want_mean else None
-    call("dvid_roialign_v2_multilevel_f32", ptr(p3), ptr(p4), ptr(p5), n, height, width, c, ptr(boxes), M, ptr(roi), ptr(mean), stream_ptr())
+    call("dvid_roialign_v2_levels_f32", levels, nl, n, height, width, c, ptr(boxes), M, ptr(roi), ptr(mean), stream_ptr())
     return (roi, mean) if want_mean else roi
 
 
@@ -180,15 +195,15 @@ def linear(x16, w_packed, kpad, bias, relu=False, out_f32=True):
 
 
 def roialign(feats_nhwc, boxes, height, width, want_mean=False):
-    """feats_nhwc: [p3,p4,p5] fp16 NHWC; boxes fp32 [n, M, 4] -> roi fp16 [n*M, 49, C] (+ mean fp32 [n*M, C])."""
-    p3, p4, p5 = (_cuda(f, torch.float16) for f in feats_nhwc)
+    """feats_nhwc: [p3, p4, p5] or [p2, p3, p4, p5] fp16 NHWC; boxes fp32 [n, M, 4] -> roi fp16 [n*M, 49, C] (+ mean fp32 [n*M, C])."""
+    feats = [_cuda(f, torch.float16) for f in feats_nhwc]
+    levels, nl = _pyramid(feats, height, width, "roialign")
     boxes = _cuda(boxes, torch.float32)
     n, M = boxes.shape[:2]
-    c = p3.shape[-1]
+    c = feats[0].shape[-1]
     roi = torch.empty((n * M, 49, c), dtype=torch.float16, device=boxes.device)
     mean = torch.empty((n * M, c), dtype=torch.float32, device=boxes.device) if want_mean else None
-    call("dvid_roialign_v2_multilevel", ptr(p3), ptr(p4), ptr(p5), n, height, width, c, ptr(boxes), M, ptr(roi), ptr(mean),
-         stream_ptr())
+    call("dvid_roialign_v2_levels", levels, nl, n, height, width, c, ptr(boxes), M, ptr(roi), ptr(mean), stream_ptr())
     return (roi, mean) if want_mean else roi
 
 
@@ -573,6 +588,9 @@ class Model:
         self.local_stages = 0
         while f"head.local_attention.{self.local_stages}.0.in_proj_weight" in state_dict:
             self.local_stages += 1
+        # the pyramid: four levels (p2..p5) when the state dict carries the stride-4 lateral, as the library infers it; a head-only model
+        # takes what rcnn_head is given
+        self.fpn_levels = 4 if self.has_backbone and "backbone.fpn_lateral2.weight" in state_dict else 3
         self._lkv = {}                   # stage -> (memory tensor, its version, groups) whose K / V projections the library holds
 
     def take_range_flag(self):
@@ -608,18 +626,24 @@ class Model:
             self._ws = key
 
     def backbone(self, images, frames_per_launch=None):
-        """images fp32 NCHW [n,3,H,W] in [0,1] -> (p3, p4, p5) fp16 (precision float32: fp32) NHWC.  frames_per_launch: run the n frames as
-        consecutive launch sequences of at most that many frames (same results; smaller activation working set)."""
+        """images fp32 NCHW [n,3,H,W] in [0,1] -> [p3, p4, p5], or [p2, p3, p4, p5] for a model with the p2 level, fp16 (precision float32:
+        fp32) NHWC.  frames_per_launch: run the n frames as consecutive launch sequences of at most that many frames (same results;
+        smaller activation working set)."""
         images = _cuda(images, torch.float32)
         n, _, h, w = images.shape
         dev = images.device
-        outs = [torch.empty((n, h >> s, w >> s, self.hidden_dim), dtype=self.feat_dtype, device=dev) for s in (3, 4, 5)]
-        fn = "dvid_backbone_swin_fpn" if self.backbone_kind == "swin" else "dvid_backbone_resnet_fpn"
+        outs = self._empty_pyramid(n, h, w, dev)
+        fn = "dvid_backbone_swin_fpn_levels_frames" if self.backbone_kind == "swin" else "dvid_backbone_resnet_fpn_levels_frames"
         step = n if not frames_per_launch else max(1, min(n, int(frames_per_launch)))
         for a in range(0, n, step):
             b = min(n, a + step)
-            call(fn, self.handle, ptr(images[a:b]), b - a, h, w, ptr(outs[0][a:b]), ptr(outs[1][a:b]), ptr(outs[2][a:b]), stream_ptr())
+            table = (C.c_void_p * (b - a))(*[images[i].data_ptr() for i in range(a, b)])
+            levels = (C.c_void_p * len(outs))(*[ptr(o[a:b]) for o in outs])
+            call(fn, self.handle, table, b - a, h, w, levels, len(outs), stream_ptr())
         return outs
+
+    def _empty_pyramid(self, n, h, w, dev):
+        return [torch.empty((n, h >> s, w >> s, self.hidden_dim), dtype=self.feat_dtype, device=dev) for s in range(6 - self.fpn_levels, 6)]
 
     def backbone_frames(self, frames):
         """The same over a LIST of per-frame tensors, each fp32 [1, 3, H, W] (or [3, H, W]) on the device, all of one size: the
@@ -634,14 +658,16 @@ class Model:
             keep.append(f if f.is_contiguous() else f.contiguous())
         n = len(keep)
         dev = first.device
-        outs = [torch.empty((n, h >> s, w >> s, self.hidden_dim), dtype=self.feat_dtype, device=dev) for s in (3, 4, 5)]
+        outs = self._empty_pyramid(n, h, w, dev)
         table = (C.c_void_p * n)(*[f.data_ptr() for f in keep])
-        fn = "dvid_backbone_swin_fpn_frames" if self.backbone_kind == "swin" else "dvid_backbone_resnet_fpn_frames"
-        call(fn, self.handle, table, n, h, w, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), stream_ptr())
+        levels = (C.c_void_p * len(outs))(*[ptr(o) for o in outs])
+        fn = "dvid_backbone_swin_fpn_levels_frames" if self.backbone_kind == "swin" else "dvid_backbone_resnet_fpn_levels_frames"
+        call(fn, self.handle, table, n, h, w, levels, len(outs), stream_ptr())
         return outs          # `keep` may die here: the stream-ordered caching allocator re-uses a frame's block only behind this stream's reads
 
     def rcnn_head(self, head_index, feats_nhwc, height, width, boxes, pro_features, t, cond=None, bad_flag=None):
-        """One RCNNHead / RCNNHead_cond pass.  boxes [n, M, 4]; pro_features [n*M, d] or None; t: int64 [n] (CPU)."""
+        """One RCNNHead / RCNNHead_cond pass over the maps it is given, [p3, p4, p5] or [p2, p3, p4, p5].  boxes [n, M, 4]; pro_features
+        [n*M, d] or None; t: int64 [n] (CPU)."""
         boxes = _cuda(boxes, torch.float32)
         n, M = boxes.shape[:2]
         dev = boxes.device
@@ -659,9 +685,9 @@ class Model:
             pro_features = _cuda(pro_features, torch.float32)
         if cond is not None:
             cond = _cuda(cond, torch.float32)
-        call("dvid_rcnn_head", self.handle, head_index, int(cond is not None), ptr(feats_nhwc[0]), ptr(feats_nhwc[1]),
-             ptr(feats_nhwc[2]), n, height, width, M, ptr(boxes), ptr(pro_features), tp, ptr(cond), ptr(logits), ptr(boxes_out),
-             ptr(obj), ptr(bad_flag), stream_ptr())
+        levels, nl = _pyramid(feats_nhwc, height, width, "rcnn_head")
+        call("dvid_rcnn_head_levels", self.handle, head_index, int(cond is not None), levels, nl, n, height, width, M, ptr(boxes),
+             ptr(pro_features), tp, ptr(cond), ptr(logits), ptr(boxes_out), ptr(obj), ptr(bad_flag), stream_ptr())
         return logits, boxes_out, obj
 
     def invalidate_memory(self):

@@ -100,12 +100,22 @@ def align_and_update_state_dicts(model_state_dict, loaded_state_dict):
     return missed
 
 
+# The stride-4 level of a p2..p5 model (MODEL.ROI_HEADS.IN_FEATURES [p2, p3, p4, p5]): a checkpoint trained on p3..p5 has none of them
+LEVEL2_NAMES = ("fpn_lateral2.weight", "fpn_lateral2.bias", "fpn_output2.weight", "fpn_output2.bias", "bottom_up.norm0.weight", "bottom_up.norm0.bias")
+
+
 def load_state_dict(model, loaded_state_dict, skip_modules=None):
-    """model_serialization.py:140-156 for a DiffusionDet model: strip `module.`, rename heads, suffix-match, strict load."""
+    """model_serialization.py:140-156 for a DiffusionDet model: strip `module.`, rename heads, suffix-match, strict load.  The reference
+    leaves a parameter that no loaded key matches at its random init and goes on; for the p2 level that would pool a quarter of the
+    boxes from noise, so a p2..p5 model refuses a checkpoint without the level's tensors."""
     model_state_dict = OrderedDict(model.state_dict())
     loaded = strip_prefix_if_present(loaded_state_dict, "module.")
     loaded = remap_diffusiondet_heads(list(model_state_dict.keys()), loaded, skip_modules)
     missed = align_and_update_state_dicts(model_state_dict, loaded)
+    no_p2 = [k for k in missed if k.endswith(LEVEL2_NAMES)]
+    if no_p2:
+        raise KeyError("the model has the p2 level (MODEL.ROI_HEADS.IN_FEATURES [p2, p3, p4, p5]) and the checkpoint does not: no tensor "
+                       "for %s; load it into a [p3, p4, p5] model" % ", ".join(no_p2))
     for name, value in model_state_dict.items():
         if isinstance(value, np.ndarray):
             model_state_dict[name] = torch.from_numpy(value)

@@ -84,7 +84,24 @@ def make_head_state_dict(seed=0, hidden=256, nheads=8, dim_ff=2048, dim_dynamic=
     return sd
 
 
-def make_backbone_state_dict(seed=1, blocks=(3, 4, 23, 3), out_channels=256, prefix="backbone."):
+def _check_fpn_levels(fpn_levels):
+    if tuple(fpn_levels) not in ((3, 4, 5), (2, 3, 4, 5)):
+        raise ValueError("fpn_levels must be (3, 4, 5) or (2, 3, 4, 5), got %r" % (tuple(fpn_levels),))
+    return tuple(fpn_levels)
+
+
+def _fpn_level(g, sd, prefix, lvl, c, out_channels):
+    sd[f"{prefix}fpn_lateral{lvl}.weight"] = (torch.rand(out_channels, c, 1, 1, generator=g) * 2 - 1) * math.sqrt(3.0 / c)
+    sd[f"{prefix}fpn_lateral{lvl}.bias"] = (torch.rand(out_channels, generator=g) * 2 - 1) * 0.05
+    fan = out_channels * 9
+    sd[f"{prefix}fpn_output{lvl}.weight"] = (torch.rand(out_channels, out_channels, 3, 3, generator=g) * 2 - 1) * math.sqrt(3.0 / fan)
+    sd[f"{prefix}fpn_output{lvl}.bias"] = (torch.rand(out_channels, generator=g) * 2 - 1) * 0.05
+
+
+def make_backbone_state_dict(seed=1, blocks=(3, 4, 23, 3), out_channels=256, prefix="backbone.", fpn_levels=(3, 4, 5)):
+    """fpn_levels (2, 3, 4, 5) adds the stride-4 level's fpn_lateral2 / fpn_output2, drawn after everything else: a seed's other values
+    do not depend on it."""
+    fpn_levels = _check_fpn_levels(fpn_levels)
     g = torch.Generator().manual_seed(seed)
     sd = {}
 
@@ -110,19 +127,18 @@ def make_backbone_state_dict(seed=1, blocks=(3, 4, 23, 3), out_channels=256, pre
                 conv_bn(p + ".shortcut", cout, cin, 1)
             cin = cout
     for lvl, c in zip((3, 4, 5), (512, 1024, 2048)):
-        fan = c
-        sd[f"{prefix}fpn_lateral{lvl}.weight"] = (torch.rand(out_channels, c, 1, 1, generator=g) * 2 - 1) * math.sqrt(3.0 / fan)
-        sd[f"{prefix}fpn_lateral{lvl}.bias"] = (torch.rand(out_channels, generator=g) * 2 - 1) * 0.05
-        fan = out_channels * 9
-        sd[f"{prefix}fpn_output{lvl}.weight"] = (torch.rand(out_channels, out_channels, 3, 3, generator=g) * 2 - 1) * math.sqrt(3.0 / fan)
-        sd[f"{prefix}fpn_output{lvl}.bias"] = (torch.rand(out_channels, generator=g) * 2 - 1) * 0.05
+        _fpn_level(g, sd, prefix, lvl, c, out_channels)
+    if 2 in fpn_levels:
+        _fpn_level(g, sd, prefix, 2, 256, out_channels)
     return sd
 
 
 def make_swin_state_dict(seed=1, embed_dim=128, depths=(2, 2, 18, 2), heads=(4, 8, 16, 32), window=7, out_channels=256,
-                         prefix="backbone."):
+                         prefix="backbone.", fpn_levels=(3, 4, 5)):
     """Swin-Transformer + FPN parameters under the reference's names (swintransformer.py modules wrapped by
-    detectron2's FPN as `backbone.bottom_up.*`).  Values are O(1)-preserving random (not the std-0.02 default)."""
+    detectron2's FPN as `backbone.bottom_up.*`).  Values are O(1)-preserving random (not the std-0.02 default).  fpn_levels
+    (2, 3, 4, 5) adds stage 0's output norm (norm0, out_indices (0, 1, 2, 3)) and fpn_lateral2 / fpn_output2, drawn after everything else."""
+    fpn_levels = _check_fpn_levels(fpn_levels)
     g = torch.Generator().manual_seed(seed)
     sd = {}
     bu = prefix + "bottom_up."
@@ -154,21 +170,19 @@ def make_swin_state_dict(seed=1, embed_dim=128, depths=(2, 2, 18, 2), heads=(4, 
         if i >= 1:
             _ln(g, sd, f"{bu}norm{i}", C)
     for lvl, i in zip((3, 4, 5), (1, 2, 3)):
-        c = embed_dim << i
-        sd[f"{prefix}fpn_lateral{lvl}.weight"] = (torch.rand(out_channels, c, 1, 1, generator=g) * 2 - 1) * math.sqrt(3.0 / c)
-        sd[f"{prefix}fpn_lateral{lvl}.bias"] = (torch.rand(out_channels, generator=g) * 2 - 1) * 0.05
-        fan = out_channels * 9
-        sd[f"{prefix}fpn_output{lvl}.weight"] = (torch.rand(out_channels, out_channels, 3, 3, generator=g) * 2 - 1) * math.sqrt(3.0 / fan)
-        sd[f"{prefix}fpn_output{lvl}.bias"] = (torch.rand(out_channels, generator=g) * 2 - 1) * 0.05
+        _fpn_level(g, sd, prefix, lvl, embed_dim << i, out_channels)
+    if 2 in fpn_levels:
+        _ln(g, sd, f"{bu}norm0", embed_dim)
+        _fpn_level(g, sd, prefix, 2, embed_dim, out_channels)
     return sd
 
 
-def make_state_dict(seed=0, blocks=(3, 4, 23, 3), swin=None, **head_kw):
+def make_state_dict(seed=0, blocks=(3, 4, 23, 3), swin=None, fpn_levels=(3, 4, 5), **head_kw):
     sd = make_head_state_dict(seed, **head_kw)
     if swin is not None:
-        sd.update(make_swin_state_dict(seed + 1, **swin))
+        sd.update(make_swin_state_dict(seed + 1, **swin, fpn_levels=fpn_levels))
     else:
-        sd.update(make_backbone_state_dict(seed + 1, blocks))
+        sd.update(make_backbone_state_dict(seed + 1, blocks, fpn_levels=fpn_levels))
     return sd
 
 

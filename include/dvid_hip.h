@@ -133,6 +133,20 @@ int dvid_backbone_swin_fpn(dvid_model* m, const float* images, int n, int height
 int dvid_backbone_swin_fpn_frames(dvid_model* m, const float* const* frames, int n, int height, int width, void* p3, void* p4, void* p5,
                                   void* stream);
 
+/* The pyramid as an array (detectron2 FPN.forward over MODEL.FPN.IN_FEATURES, bottom level last; the reference's default node,
+ * diffusion_det.py:155-159, runs it over res2..res5, its configs/vid_*.yaml over res3..res5).  A model HAS THE p2 LEVEL when the tensor
+ * backbone.fpn_lateral2.weight was set before dvid_model_finalize; it then also needs backbone.fpn_lateral2.bias and
+ * backbone.fpn_output2.weight / .bias, a Swin model backbone.bottom_up.norm0.weight / .bias (out_indices (0,1,2,3)) as well, and the
+ * finalize fails with DVID_ERR_STATE naming the first one missing.  Its workspace holds res2's (Swin: stage 0's) output and a fourth
+ * lateral map per frame.
+ * levels: host array of n_levels output pointers, levels[0] the finest: 3 = p3, p4, p5 as above; 4 = p2 [n,h/4,w/4,256] in front of
+ * them.  n_levels must be the model's count (DVID_ERR_ARG otherwise, nothing is written).  The three-pointer entries above are these
+ * with n_levels 3, and a model with the p2 level answers them with DVID_ERR_STATE. */
+int dvid_backbone_resnet_fpn_levels_frames(dvid_model* m, const float* const* frames, int n, int height, int width, void* const* levels,
+                                           int n_levels, void* stream);
+int dvid_backbone_swin_fpn_levels_frames(dvid_model* m, const float* const* frames, int n, int height, int width, void* const* levels,
+                                         int n_levels, void* stream);
+
 /* One RCNNHead (cond == NULL) or RCNNHead_cond pass.  head_index indexes head_series, or
  * head_series_cond when is_cond.  t: host int64 [n_frames] diffusion timesteps.
  * pro_features may be NULL (-> mean of the RoI features).  Outputs: logits [R,num_classes],
@@ -143,6 +157,14 @@ int dvid_rcnn_head(dvid_model* m, int head_index, int is_cond, const void* p3, c
                    int height, int width, int boxes_per_frame, const float* boxes, const float* pro_features,
                    const int64_t* t, const float* cond, float* logits, float* boxes_out, float* obj_features,
                    int* bad_box_flag, void* stream);
+/* The same over a pyramid given as an array (detectron2 ROIPooler as built at box_head.py:250-271: one scale per entry of
+ * ROI_HEADS.IN_FEATURES, canonical size 224 at level 4): levels[0] is the finest map, n_levels 3 = p3..p5 (strides 8..32),
+ * 4 = p2..p5 (strides 4..32); DVID_ERR_ARG for any other count, a null map, or a count that differs from the model's backbone.  A
+ * head-only model takes either.  dvid_rcnn_head is this with n_levels 3; a model with the p2 level answers it with DVID_ERR_STATE. */
+int dvid_rcnn_head_levels(dvid_model* m, int head_index, int is_cond, const void* const* levels, int n_levels, int n_frames,
+                          int height, int width, int boxes_per_frame, const float* boxes, const float* pro_features,
+                          const int64_t* t, const float* cond, float* logits, float* boxes_out, float* obj_features,
+                          int* bad_box_flag, void* stream);
 
 /* cond[R,hidden] = MHA(query = obj_features[R,hidden], key = value = memory[lk,hidden]).  memory == NULL: use the K/V
  * projections kept by the last dvid_global_memory_project (lk 0 or the same row count). */
@@ -172,6 +194,13 @@ int dvid_local_xattn(dvid_model* m, int stage, const float* query, int rows, int
 int dvid_roialign_v2_multilevel(const void* p3, const void* p4, const void* p5, int n_frames, int height, int width,
                                 int channels, const float* boxes, int boxes_per_frame, void* roi_out /* fp16 [R,49,C] */,
                                 float* mean_out /* [R,C] or NULL */, void* stream);
+/* The same with the pyramid as an array (ROIPooler, box_head.py:250-271): levels[0] the finest map, n_levels 3 (p3..p5, what the entry
+ * above forwards) or 4 (p2..p5); a box goes to level clamp(floor(4 + log2(sqrt(area) / 224 + 1e-8)), 6 - n_levels, 5).  DVID_ERR_ARG for
+ * another count or a null map.  dvid_roialign_v2_levels_f32: the DTYPE float32 form (fp32 NHWC maps, fp32 tiles). */
+int dvid_roialign_v2_levels(const void* const* levels, int n_levels, int n_frames, int height, int width, int channels,
+                            const float* boxes, int boxes_per_frame, void* roi_out, float* mean_out, void* stream);
+int dvid_roialign_v2_levels_f32(const float* const* levels, int n_levels, int n_frames, int height, int width, int channels,
+                                const float* boxes, int boxes_per_frame, float* roi_out, float* mean_out, void* stream);
 /* The DTYPE float32 forms of the stand-alone ops (csrc/f32.hip for conv / linear; the others beside their fp16 kernels in csrc/roialign.hip, attention.hip, dynconv.hip): fp32 NHWC pyramids -> fp32 [R,49,C] tiles; fp32 conv / linear with
  * w [cout][kpad] fp32, k = (ky*kw+kx)*cin + c, cin % 4 == 0, kpad = round_up(kh*kw*cin, 16) zero-padded, and row_scale [cout] (may be
  * NULL): out channel n = act(acc_n * row_scale[n] + bias[n] + residual) -- the model packs each row times a power of two that puts its
