@@ -7,9 +7,13 @@
 
 namespace {
 
-__global__ void noise_to_boxes_kernel(const float* __restrict__ x, float* __restrict__ boxes, int n, float scale, float w, float h) {
+// SIZE: FrameSizeAll or FrameSizeTable (common.h); the frame of box i is i / m (m is not read by the one-size form)
+template <typename SIZE>
+__global__ void noise_to_boxes_kernel(const float* __restrict__ x, float* __restrict__ boxes, int n, float scale, SIZE size, int m) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    const int f = i / m;
+    const float w = size.width(f), h = size.height(f);
     const float4v v = *reinterpret_cast<const float4v*>(x + i * 4);
     float c[4];
 #pragma unroll
@@ -42,12 +46,12 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-__global__ void counter_normal_kernel(float* __restrict__ out, long per_image, int n_images, uint64_t key0) {
+__global__ void counter_normal_kernel(float* __restrict__ out, long per_image, int n_images, uint64_t key0, uint64_t key_stride) {
     const long quads = (per_image + 3) / 4;
     const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int img = blockIdx.y;
     if (q >= quads) return;
-    const uint64_t key = key0 + (uint64_t)img;
+    const uint64_t key = key0 + (uint64_t)img * key_stride;          // (1: consecutive keys; still images keyed by image id: the id's stride)
     uint32_t x[4];
     philox4x32_10((uint32_t)q, (uint32_t)((uint64_t)q >> 32), 0u, 0u, (uint32_t)key, (uint32_t)(key >> 32), x);
     float z[4];
@@ -162,11 +166,12 @@ __global__ __launch_bounds__(WIDE ? ROWMAX_WIDE_THREADS : 256) void topk_mask_ke
 // :649-653 (predict_noise_from_start).  Kept boxes are compacted in index order; the j-th kept box
 // consumes noise row j; the tail is replenished with fresh N(0,1) rows.
 // WIDE (c > ROWMAX_SERIAL_CLASSES): the largest score of a row by one wave, see above -- still the sigmoid of every element first, then the maximum.
-template <bool WIDE>
+// SIZE: FrameSizeAll (every frame divided by the one size, as the reference) or FrameSizeTable (frame blockIdx.x by its own row).
+template <bool WIDE, typename SIZE>
 __global__ __launch_bounds__(WIDE ? ROWMAX_WIDE_THREADS : 256) void ddim_renew_kernel(const float* __restrict__ logits, const float* __restrict__ boxes,
                                                                                        const float* __restrict__ xt, const float* __restrict__ noise,
                                                                                        const float* __restrict__ fresh, float* __restrict__ out, int m,
-                                                                                       int c, float w, float h, float scale, float sra, float srm1,
+                                                                                       int c, SIZE size, float scale, float sra, float srm1,
                                                                                        float sqrt_an, float cc, float sigma, float thr) {
     extern __shared__ int pos[];   // [m] compacted slot or -1
     __shared__ int s_remain;
@@ -200,6 +205,7 @@ __global__ __launch_bounds__(WIDE ? ROWMAX_WIDE_THREADS : 256) void ddim_renew_k
     }
     __syncthreads();
     const int remain = s_remain;
+    const float w = size.width(f), h = size.height(f);
     const float whwh[4] = {w, h, w, h};
     for (int i = tid; i < m; i += blockDim.x) {
         const int slot = pos[i];
@@ -228,17 +234,26 @@ __global__ __launch_bounds__(WIDE ? ROWMAX_WIDE_THREADS : 256) void ddim_renew_k
 
 int dvid_noise_to_boxes_launch(const float* x, float* boxes, int n, float scale, float w, float h, hipStream_t s) {
     if (n == 0) return DVID_OK;
-    hipLaunchKernelGGL(noise_to_boxes_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, x, boxes, n, scale, w, h);
+    hipLaunchKernelGGL(noise_to_boxes_kernel<FrameSizeAll>, dim3(ceil_div(n, 256)), dim3(256), 0, s, x, boxes, n, scale, FrameSizeAll{w, h}, n);
     LAUNCH_CHECK();
     return DVID_OK;
 }
 
-int dvid_counter_normal_launch(float* out, long per_image, int n_images, uint64_t key0, hipStream_t s) {
+// n boxes, m per frame: box i is scaled by sizes[i / m] (n = n_frames * m; sizes holds n / m rows)
+int dvid_noise_to_boxes_sizes_launch(const float* x, float* boxes, int n, int m, float scale, const float* sizes, hipStream_t s) {
+    if (n == 0) return DVID_OK;
+    if (m < 1 || n % m || !sizes) return DVID_ERR_ARG;
+    hipLaunchKernelGGL(noise_to_boxes_kernel<FrameSizeTable>, dim3(ceil_div(n, 256)), dim3(256), 0, s, x, boxes, n, scale, FrameSizeTable{sizes}, m);
+    LAUNCH_CHECK();
+    return DVID_OK;
+}
+
+int dvid_counter_normal_launch(float* out, long per_image, int n_images, uint64_t key0, hipStream_t s, uint64_t key_stride) {
     if (per_image <= 0 || n_images <= 0) return DVID_OK;
     const long quads = (per_image + 3) / 4;
     const long nblk = ceil_div(quads, 256L);
     if (nblk > 0x7fffffffL || n_images > 65535) return DVID_ERR_ARG;          // grid limits: x < 2^31, y < 2^16
-    hipLaunchKernelGGL(counter_normal_kernel, dim3((unsigned)nblk, (unsigned)n_images), dim3(256), 0, s, out, per_image, n_images, key0);
+    hipLaunchKernelGGL(counter_normal_kernel, dim3((unsigned)nblk, (unsigned)n_images), dim3(256), 0, s, out, per_image, n_images, key0, key_stride);
     LAUNCH_CHECK();
     return DVID_OK;
 }
@@ -265,16 +280,30 @@ int dvid_topk_mask_launch(const float* logits, int n_img, int m, int c, int k1, 
     return DVID_OK;
 }
 
+template <typename SIZE>
+static int ddim_renew_launch(const float* logits, const float* boxes, const float* xt, const float* noise, const float* fresh, float* out,
+                             int n_img, int m, int c, SIZE size, float scale, float sra, float srm1, float sqrt_an, float cc, float sigma,
+                             float thr, hipStream_t s) {
+    if (n_img == 0) return DVID_OK;
+    if (c > ROWMAX_SERIAL_CLASSES)
+        hipLaunchKernelGGL((ddim_renew_kernel<true, SIZE>), dim3(n_img), dim3(ROWMAX_WIDE_THREADS), (size_t)m * 4, s, logits, boxes, xt, noise, fresh,
+                           out, m, c, size, scale, sra, srm1, sqrt_an, cc, sigma, thr);
+    else
+        hipLaunchKernelGGL((ddim_renew_kernel<false, SIZE>), dim3(n_img), dim3(256), (size_t)m * 4, s, logits, boxes, xt, noise, fresh, out, m, c,
+                           size, scale, sra, srm1, sqrt_an, cc, sigma, thr);
+    LAUNCH_CHECK();
+    return DVID_OK;
+}
+
 int dvid_ddim_renew_launch(const float* logits, const float* boxes, const float* xt, const float* noise, const float* fresh,
                            float* out, int n_img, int m, int c, float w, float h, float scale, float sra, float srm1, float sqrt_an,
                            float cc, float sigma, float thr, hipStream_t s) {
-    if (n_img == 0) return DVID_OK;
-    if (c > ROWMAX_SERIAL_CLASSES)
-        hipLaunchKernelGGL(ddim_renew_kernel<true>, dim3(n_img), dim3(ROWMAX_WIDE_THREADS), (size_t)m * 4, s, logits, boxes, xt, noise, fresh, out,
-                           m, c, w, h, scale, sra, srm1, sqrt_an, cc, sigma, thr);
-    else
-        hipLaunchKernelGGL(ddim_renew_kernel<false>, dim3(n_img), dim3(256), (size_t)m * 4, s, logits, boxes, xt, noise, fresh, out, m, c, w, h,
-                           scale, sra, srm1, sqrt_an, cc, sigma, thr);
-    LAUNCH_CHECK();
-    return DVID_OK;
+    return ddim_renew_launch(logits, boxes, xt, noise, fresh, out, n_img, m, c, FrameSizeAll{w, h}, scale, sra, srm1, sqrt_an, cc, sigma, thr, s);
+}
+
+int dvid_ddim_renew_sizes_launch(const float* logits, const float* boxes, const float* xt, const float* noise, const float* fresh,
+                                 float* out, int n_img, int m, int c, const float* sizes, float scale, float sra, float srm1, float sqrt_an,
+                                 float cc, float sigma, float thr, hipStream_t s) {
+    if (n_img > 0 && !sizes) return DVID_ERR_ARG;
+    return ddim_renew_launch(logits, boxes, xt, noise, fresh, out, n_img, m, c, FrameSizeTable{sizes}, scale, sra, srm1, sqrt_an, cc, sigma, thr, s);
 }

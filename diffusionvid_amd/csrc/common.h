@@ -58,6 +58,20 @@ static inline int allow_dynamic_lds(Kernel* kernel, int bytes, std::atomic<unsig
     return DVID_OK;
 }
 
+// (w, h) of the un-padded frame f as the size-dependent box kernels read it (noise_to_boxes, ddim_renew, the clip behind the NMS): one
+// size for every frame, two kernel arguments -- a video -- or row f of a device table sizes[n_frames][2] of fp32 (w, h) -- a batch of
+// still images, each with its own size.  The kernels are templates over the two, so both forms are the same expressions.
+struct FrameSizeAll {
+    float w, h;
+    __device__ __forceinline__ float width(int) const { return w; }
+    __device__ __forceinline__ float height(int) const { return h; }
+};
+struct FrameSizeTable {
+    const float* sizes;
+    __device__ __forceinline__ float width(int f) const { return sizes[2 * f]; }
+    __device__ __forceinline__ float height(int f) const { return sizes[2 * f + 1]; }
+};
+
 static inline long ceil_div(long a, long b) { return (a + b - 1) / b; }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 

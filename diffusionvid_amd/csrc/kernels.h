@@ -165,8 +165,14 @@ int dvid_head_tail_launch(const HeadTailParams& p, hipStream_t s);
 // boxes.hip
 int dvid_apply_deltas_launch(const float* deltas, int delta_ld, const float* boxes, float* out, int n, float wx, float wy, float ww,
                              float wh, float clamp, int* bad_flag, hipStream_t s);
-int dvid_counter_normal_launch(float* out, long per_image, int n_images, uint64_t key0, hipStream_t s);
+int dvid_counter_normal_launch(float* out, long per_image, int n_images, uint64_t key0, hipStream_t s, uint64_t key_stride = 1);          // image i: key0 + i * key_stride
 int dvid_noise_to_boxes_launch(const float* x, float* boxes, int n, float scale, float w, float h, hipStream_t s);
+// the per-frame forms (`sizes`: device fp32 [n_frames][2] = (w, h) of each frame, every entry positive and finite) of the size-dependent
+// kernels: the same kernels instantiated over FrameSizeTable (common.h).  noise_to_boxes: n boxes, m per frame
+int dvid_noise_to_boxes_sizes_launch(const float* x, float* boxes, int n, int m, float scale, const float* sizes, hipStream_t s);
+int dvid_ddim_renew_sizes_launch(const float* logits, const float* boxes, const float* xt, const float* noise, const float* fresh,
+                                 float* out, int n_img, int m, int c, const float* sizes, float scale, float sra, float srm1, float sqrt_an,
+                                 float cc, float sigma, float thr, hipStream_t s);
 int dvid_topk_mask_launch(const float* logits, int n_img, int m, int c, int k1, int k2, const float* feats, int d, float* out1,
                           float* out2, hipStream_t s);
 
@@ -190,6 +196,13 @@ size_t dvid_nms_tiled_scratch_size(int n_img, int n);
 int dvid_nms_frames_tiled_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n, float img_w,
                                  float img_h, float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels,
                                  int* out_counts, void* scratch, hipStream_t s);
+// ... and with the clip of frame f to sizes[f] (see boxes.hip above)
+int dvid_nms_frames_sizes_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n, const float* sizes,
+                                 float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels, int* out_counts,
+                                 hipStream_t s);
+int dvid_nms_frames_tiled_sizes_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n,
+                                       const float* sizes, float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores,
+                                       int* out_labels, int* out_counts, void* scratch, hipStream_t s);
 
 // seqnms.hip: Seq-NMS over videos, a workgroup per (video, class); class_counts / video_starts are host tables (include/dvid_hip.h)
 long long dvid_seq_nms_scratch_size(const int* class_counts, const int* video_starts, int n_videos, int num_classes);

@@ -113,9 +113,24 @@ int dvid_counter_normal(float* out, int64_t per_image, int n_images, uint64_t ke
     return DVID_OK;
 }
 
+int dvid_counter_normal_strided(float* out, int64_t per_image, int n_images, uint64_t key0, uint64_t key_stride, void* stream) {
+    g_err[0] = 0;
+    if (!out || per_image < 0 || n_images < 0 || n_images > 65535) FAIL(DVID_ERR_ARG, "dvid_counter_normal_strided: bad arguments");
+    TRY(dvid_counter_normal_launch(out, (long)per_image, n_images, key0, reinterpret_cast<hipStream_t>(stream), key_stride));
+    return DVID_OK;
+}
+
 int dvid_noise_to_boxes(const float* x, float* boxes, int n, float snr_scale, float img_w, float img_h, void* stream) {
     g_err[0] = 0;
     TRY(dvid_noise_to_boxes_launch(x, boxes, n, snr_scale, img_w, img_h, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_noise_to_boxes_sizes(const float* x, float* boxes, int n, int mm, float snr_scale, const float* sizes, void* stream) {
+    g_err[0] = 0;
+    if (n < 0 || mm < 1 || n % mm) FAIL(DVID_ERR_ARG, "noise_to_boxes: %d boxes are not whole frames of %d", n, mm);
+    if (n > 0 && (!x || !boxes || !sizes)) FAIL(DVID_ERR_ARG, "noise_to_boxes: null pointer");
+    TRY(dvid_noise_to_boxes_sizes_launch(x, boxes, n, mm, snr_scale, sizes, reinterpret_cast<hipStream_t>(stream)));
     return DVID_OK;
 }
 
@@ -126,6 +141,16 @@ int dvid_ddim_renew_step(const float* logits, const float* boxes, const float* x
     g_err[0] = 0;
     TRY(dvid_ddim_renew_launch(logits, boxes, x_t, noise, fresh, x_next, n_frames, mm, c, img_w, img_h, snr_scale, sqrt_recip_ac,
                                sqrt_recipm1_ac, sqrt_ac_next, coef_c, sigma, keep_thr, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_ddim_renew_step_sizes(const float* logits, const float* boxes, const float* x_t, const float* noise, const float* fresh,
+                               float* x_next, int n_frames, int mm, int c, const float* sizes, float snr_scale, float sqrt_recip_ac,
+                               float sqrt_recipm1_ac, float sqrt_ac_next, float coef_c, float sigma, float keep_thr, void* stream) {
+    g_err[0] = 0;
+    if (n_frames > 0 && !sizes) FAIL(DVID_ERR_ARG, "ddim_renew_step: null size table");
+    TRY(dvid_ddim_renew_sizes_launch(logits, boxes, x_t, noise, fresh, x_next, n_frames, mm, c, sizes, snr_scale, sqrt_recip_ac, sqrt_recipm1_ac,
+                                     sqrt_ac_next, coef_c, sigma, keep_thr, reinterpret_cast<hipStream_t>(stream)));
     return DVID_OK;
 }
 
@@ -142,9 +167,9 @@ int64_t dvid_postproc_scratch_bytes(int nsets, int n_frames, int mm) {
 
 int64_t dvid_nms_tiled_scratch_bytes(int n_frames, int n) { return (int64_t)dvid_nms_tiled_scratch_size(n_frames, n); }
 
-int dvid_postproc_topk_nms(const float* logits, const float* boxes, int nsets, int n_frames, int mm, int c, float img_w, float img_h,
-                           float iou_threshold, int use_nms, float* out_boxes, float* out_scores, int* out_labels, int* out_counts,
-                           void* scratch, void* stream) {
+// dvid_postproc_topk_nms / _sizes: nms(cb, cs, cl, tiled scratch or null, stream) launches the NMS form the shape takes with the caller's sizes
+extern "C++" template <typename NMS>
+static int postproc_topk_nms(const float* logits, const float* boxes, int nsets, int n_frames, int mm, int c, void* scratch, void* stream, NMS nms) {
     g_err[0] = 0;
     if (!scratch) FAIL(DVID_ERR_ARG, "scratch required");
     if (nsets <= 0 || n_frames < 0 || mm <= 0) FAIL(DVID_ERR_ARG, "postproc: bad sizes (%d sets, %d frames, %d boxes)", nsets, n_frames, mm);
@@ -160,13 +185,35 @@ int dvid_postproc_topk_nms(const float* logits, const float* boxes, int nsets, i
     float* cs = cb + ncand * 4;
     int* cl = reinterpret_cast<int*>(cs + ncand);
     TRY(dvid_topk_candidates_launch(logits, boxes, n_frames, nsets, mm, c, cb, cs, cl, s));
-    if (dvid_nms_frames_fits_lds((int)n))
-        TRY(dvid_nms_frames_launch(cb, cs, cl, n_frames, nsets * mm, img_w, img_h, iou_threshold, use_nms, nsets * mm, out_boxes,
-                                   out_scores, out_labels, out_counts, s));
-    else          // the shapes nms_frame_kernel cannot hold in LDS: the tiled form, its scratch behind the candidate lists
-        TRY(dvid_nms_frames_tiled_launch(cb, cs, cl, n_frames, nsets * mm, img_w, img_h, iou_threshold, use_nms, nsets * mm, out_boxes,
-                                         out_scores, out_labels, out_counts, reinterpret_cast<char*>(scratch) + postproc_cand_bytes(nsets, n_frames, mm), s));
+    // the shapes nms_frame_kernel cannot hold in LDS take the tiled form, its scratch behind the candidate lists
+    TRY(nms(cb, cs, cl, dvid_nms_frames_fits_lds((int)n) ? nullptr : reinterpret_cast<char*>(scratch) + postproc_cand_bytes(nsets, n_frames, mm), s));
     return DVID_OK;
+}
+
+int dvid_postproc_topk_nms(const float* logits, const float* boxes, int nsets, int n_frames, int mm, int c, float img_w, float img_h,
+                           float iou_threshold, int use_nms, float* out_boxes, float* out_scores, int* out_labels, int* out_counts,
+                           void* scratch, void* stream) {
+    return postproc_topk_nms(logits, boxes, nsets, n_frames, mm, c, scratch, stream, [=](const float* cb, const float* cs, const int* cl, void* tiled, hipStream_t s) {
+        return tiled ? dvid_nms_frames_tiled_launch(cb, cs, cl, n_frames, nsets * mm, img_w, img_h, iou_threshold, use_nms, nsets * mm, out_boxes, out_scores,
+                                                    out_labels, out_counts, tiled, s)
+                     : dvid_nms_frames_launch(cb, cs, cl, n_frames, nsets * mm, img_w, img_h, iou_threshold, use_nms, nsets * mm, out_boxes, out_scores, out_labels,
+                                              out_counts, s);
+    });
+}
+
+int dvid_postproc_topk_nms_sizes(const float* logits, const float* boxes, int nsets, int n_frames, int mm, int c, const float* sizes,
+                                 float iou_threshold, int use_nms, float* out_boxes, float* out_scores, int* out_labels, int* out_counts,
+                                 void* scratch, void* stream) {
+    if (n_frames > 0 && !sizes) {
+        g_err[0] = 0;
+        FAIL(DVID_ERR_ARG, "postproc: null size table");
+    }
+    return postproc_topk_nms(logits, boxes, nsets, n_frames, mm, c, scratch, stream, [=](const float* cb, const float* cs, const int* cl, void* tiled, hipStream_t s) {
+        return tiled ? dvid_nms_frames_tiled_sizes_launch(cb, cs, cl, n_frames, nsets * mm, sizes, iou_threshold, use_nms, nsets * mm, out_boxes, out_scores,
+                                                          out_labels, out_counts, tiled, s)
+                     : dvid_nms_frames_sizes_launch(cb, cs, cl, n_frames, nsets * mm, sizes, iou_threshold, use_nms, nsets * mm, out_boxes, out_scores, out_labels,
+                                                    out_counts, s);
+    });
 }
 
 int dvid_topk_candidates_stream(const float* logits, const float* boxes, int nsets, int n_frames, int mm, int c, float* cand_boxes,
@@ -193,6 +240,20 @@ int dvid_nms_frames_tiled(const float* cand_boxes, const float* cand_scores, con
         FAIL(DVID_ERR_UNSUPPORTED, "tiled NMS: %d candidates per frame exceed the limit of %d ((SAMPLE_STEP - 1) * NUM_PROPOSALS)", n, DVID_NMS_MAX_CANDIDATES);
     TRY(dvid_nms_frames_tiled_launch(cand_boxes, cand_scores, cand_labels, n_frames, n, img_w, img_h, iou_threshold, use_nms, out_cap, out_boxes,
                                      out_scores, out_labels, out_counts, scratch, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_nms_frames_tiled_sizes(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_frames, int n, const float* sizes,
+                                float iou_threshold, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels,
+                                int* out_counts, void* scratch, void* stream) {
+    g_err[0] = 0;
+    if (!cand_boxes || !cand_scores || !cand_labels || !out_boxes || !out_scores || !out_labels || !out_counts || !scratch || !sizes)
+        FAIL(DVID_ERR_ARG, "tiled NMS: null pointer");
+    if (n_frames < 0 || n < 1 || out_cap < n) FAIL(DVID_ERR_ARG, "tiled NMS: bad sizes (%d frames, %d candidates, out_cap %d)", n_frames, n, out_cap);
+    if (n > DVID_NMS_MAX_CANDIDATES)
+        FAIL(DVID_ERR_UNSUPPORTED, "tiled NMS: %d candidates per frame exceed the limit of %d ((SAMPLE_STEP - 1) * NUM_PROPOSALS)", n, DVID_NMS_MAX_CANDIDATES);
+    TRY(dvid_nms_frames_tiled_sizes_launch(cand_boxes, cand_scores, cand_labels, n_frames, n, sizes, iou_threshold, use_nms, out_cap, out_boxes,
+                                           out_scores, out_labels, out_counts, scratch, reinterpret_cast<hipStream_t>(stream)));
     return DVID_OK;
 }
 

@@ -291,10 +291,11 @@ __global__ __launch_bounds__(1024) void topk_stream_kernel(const float* __restri
     }
 }
 
-// one workgroup (1024 threads) per frame; n = nsets * m candidates (<= 1024)
+// one workgroup (1024 threads) per frame; n = nsets * m candidates (<= 1024).  SIZE (common.h): the frame's (w, h) -- one for all frames or
+// the frame's row of a table -- read by the final clip alone: max_coord, the class offsets and the IoU never see it.
+template <typename SIZE>
 __global__ __launch_bounds__(1024) void nms_frame_kernel(const float* __restrict__ cand_boxes, const float* __restrict__ cand_scores,
-                                                          const int* __restrict__ cand_labels, int n, int npad, float img_w,
-                                                          float img_h, float iou_thr, int use_nms, int out_cap,
+                                                          const int* __restrict__ cand_labels, int n, int npad, SIZE size, float iou_thr, int use_nms, int out_cap,
                                                           float* __restrict__ out_boxes, float* __restrict__ out_scores,
                                                           int* __restrict__ out_labels, int* __restrict__ out_counts) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -382,6 +383,7 @@ __global__ __launch_bounds__(1024) void nms_frame_kernel(const float* __restrict
     }
     __syncthreads();
     const int nkeep = __float_as_int(redf[0]);
+    const float img_w = size.width(f), img_h = size.height(f);
     for (int s = tid; s < out_cap; s += blockDim.x) {
         float4v b = {0.f, 0.f, 0.f, 0.f};
         float sc = 0.f;
@@ -510,9 +512,10 @@ __global__ __launch_bounds__(256) void nms_tiled_mask_kernel(const float* __rest
 }
 
 // one workgroup (256 threads) per frame; dynamic LDS: two blocks of NMS_SWEEP_ROWS x words mask words, then keep_slot[n]
+template <typename SIZE>
 __global__ __launch_bounds__(NMS_SWEEP_THREADS) void nms_tiled_sweep_kernel(
     const float* __restrict__ cand_boxes, const float* __restrict__ cand_scores, const int* __restrict__ cand_labels,
-    const int* __restrict__ sorder, const u64* __restrict__ mask, int n, int words, float img_w, float img_h, int use_nms, int out_cap,
+    const int* __restrict__ sorder, const u64* __restrict__ mask, int n, int words, SIZE size, int use_nms, int out_cap,
     float* __restrict__ out_boxes, float* __restrict__ out_scores, int* __restrict__ out_labels, int* __restrict__ out_counts) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int PER = NMS_SWEEP_ROWS * 64 / NMS_SWEEP_THREADS;       // staged words per thread at the widest matrix (64 words)
@@ -581,6 +584,7 @@ __global__ __launch_bounds__(NMS_SWEEP_THREADS) void nms_tiled_sweep_kernel(
     __syncthreads();
     const int nkeep = s_nkeep;
     if (tid == 0) out_counts[f] = nkeep;
+    const float img_w = size.width(f), img_h = size.height(f);
     for (int s = tid; s < out_cap; s += NMS_SWEEP_THREADS) {
         float4v b = {0.f, 0.f, 0.f, 0.f};
         float sc = 0.f;
@@ -661,19 +665,34 @@ static size_t nms_frame_lds_bytes(int n) {
 // THE dispatch rule of the two NMS forms: nms_frame_kernel runs every shape it holds in LDS, the tiled form the others
 bool dvid_nms_frames_fits_lds(int n) { return n <= 1024 && nms_frame_lds_bytes(n) <= 160 * 1024; }
 
-int dvid_nms_frames_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n, float img_w,
-                           float img_h, float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels,
-                           int* out_counts, hipStream_t s) {
+template <typename SIZE>
+static int nms_frames_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n, SIZE size, float iou,
+                             int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels, int* out_counts, hipStream_t s) {
     if (n_img == 0) return DVID_OK;
     if (!dvid_nms_frames_fits_lds(n) || out_cap < n) return DVID_ERR_UNSUPPORTED;
     const int npad = next_pow2(n);
     const size_t smem = nms_frame_lds_bytes(n);
-    static std::atomic<unsigned long long> attr{0};          // one bit per device: the attribute belongs to (function, device)
-    if (const int rc = allow_dynamic_lds(&nms_frame_kernel, 160 * 1024, attr); rc != DVID_OK) return rc;
-    hipLaunchKernelGGL(nms_frame_kernel, dim3(n_img), dim3(1024), smem, s, cand_boxes, cand_scores, cand_labels, n, npad, img_w, img_h,
+    static std::atomic<unsigned long long> attr{0};          // one bit per device: the attribute belongs to (function, device); one per SIZE
+    if (const int rc = allow_dynamic_lds(&nms_frame_kernel<SIZE>, 160 * 1024, attr); rc != DVID_OK) return rc;
+    hipLaunchKernelGGL(nms_frame_kernel<SIZE>, dim3(n_img), dim3(1024), smem, s, cand_boxes, cand_scores, cand_labels, n, npad, size,
                        iou, use_nms, out_cap, out_boxes, out_scores, out_labels, out_counts);
     LAUNCH_CHECK();
     return DVID_OK;
+}
+
+int dvid_nms_frames_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n, float img_w,
+                           float img_h, float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels,
+                           int* out_counts, hipStream_t s) {
+    return nms_frames_launch(cand_boxes, cand_scores, cand_labels, n_img, n, FrameSizeAll{img_w, img_h}, iou, use_nms, out_cap, out_boxes, out_scores,
+                             out_labels, out_counts, s);
+}
+
+int dvid_nms_frames_sizes_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n, const float* sizes,
+                                 float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels, int* out_counts,
+                                 hipStream_t s) {
+    if (n_img > 0 && !sizes) return DVID_ERR_ARG;
+    return nms_frames_launch(cand_boxes, cand_scores, cand_labels, n_img, n, FrameSizeTable{sizes}, iou, use_nms, out_cap, out_boxes, out_scores,
+                             out_labels, out_counts, s);
 }
 
 // Frames per chunk of the tiled form: as many as keep the chunk's bit matrices within NMS_TILED_MATRIX_CEILING (2 MiB per frame at
@@ -691,9 +710,11 @@ size_t dvid_nms_tiled_scratch_size(int n_img, int n) {
     return 256 + fc * n * (16 + 4 + 4 + (size_t)((n + 63) / 64) * 8);          // 256: the launcher aligns its base
 }
 
-int dvid_nms_frames_tiled_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n, float img_w,
-                                 float img_h, float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels,
-                                 int* out_counts, void* scratch, hipStream_t s) {
+// size_of(f0): the SIZE of the chunk of frames that starts at frame f0 (the kernels index it by the frame inside the chunk)
+template <typename SIZE_OF>
+static int nms_frames_tiled_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n, SIZE_OF size_of,
+                                   float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels, int* out_counts,
+                                   void* scratch, hipStream_t s) {
     if (n_img == 0) return DVID_OK;
     if (n < 1 || n > DVID_NMS_MAX_CANDIDATES || out_cap < n || !scratch) return DVID_ERR_UNSUPPORTED;
     const int npad = next_pow2(n), words = (n + 63) / 64;
@@ -716,10 +737,25 @@ int dvid_nms_frames_tiled_launch(const float* cand_boxes, const float* cand_scor
                                sarea, n, words, iou, mask);
             LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(nms_tiled_sweep_kernel, dim3(nf), dim3(NMS_SWEEP_THREADS), sweep_lds, s, cb, cs, cl, sorder, mask, n, words, img_w, img_h,
-                           use_nms, out_cap, out_boxes + (size_t)f0 * out_cap * 4, out_scores + (size_t)f0 * out_cap,
+        hipLaunchKernelGGL(nms_tiled_sweep_kernel<decltype(size_of(f0))>, dim3(nf), dim3(NMS_SWEEP_THREADS), sweep_lds, s, cb, cs, cl, sorder, mask, n, words,
+                           size_of(f0), use_nms, out_cap, out_boxes + (size_t)f0 * out_cap * 4, out_scores + (size_t)f0 * out_cap,
                            out_labels + (size_t)f0 * out_cap, out_counts + f0);
         LAUNCH_CHECK();
     }
     return DVID_OK;
+}
+
+int dvid_nms_frames_tiled_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n, float img_w,
+                                 float img_h, float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores, int* out_labels,
+                                 int* out_counts, void* scratch, hipStream_t s) {
+    return nms_frames_tiled_launch(cand_boxes, cand_scores, cand_labels, n_img, n, [=](int) { return FrameSizeAll{img_w, img_h}; }, iou, use_nms,
+                                   out_cap, out_boxes, out_scores, out_labels, out_counts, scratch, s);
+}
+
+int dvid_nms_frames_tiled_sizes_launch(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_img, int n,
+                                       const float* sizes, float iou, int use_nms, int out_cap, float* out_boxes, float* out_scores,
+                                       int* out_labels, int* out_counts, void* scratch, hipStream_t s) {
+    if (n_img > 0 && !sizes) return DVID_ERR_ARG;
+    return nms_frames_tiled_launch(cand_boxes, cand_scores, cand_labels, n_img, n, [=](int f0) { return FrameSizeTable{sizes + (size_t)f0 * 2}; }, iou,
+                                   use_nms, out_cap, out_boxes, out_scores, out_labels, out_counts, scratch, s);
 }

@@ -326,3 +326,50 @@ def inference(model, dataset, indices, device, output_folder=None, gt_boxlists=N
     ev = vid_eval.do_vid_evaluation(source, preds, output_folder, motion_specific=motion_specific, logger=logger,
                                     motion_ious=motion_ious)
     return preds, (ev if motion_specific else ev[0])
+
+
+# ---- still images ------------------------------------------------------------------------------------------------------------------
+def coco_results(predictions, label_map=None):
+    """{image_id: BoxList} -> the COCO result list: one dict(image_id, category_id, bbox [x, y, w, h], score) per detection, boxes in the
+    BoxList's own image size.  label_map: model label (1 ..) -> category id, a dict or a callable; None keeps the labels."""
+    to_cat = (lambda l: l) if label_map is None else (label_map if callable(label_map) else label_map.__getitem__)
+    out = []
+    for image_id in sorted(predictions):
+        bl = predictions[image_id].convert("xyxy")
+        boxes = bl.bbox.detach().cpu().double()
+        scores = bl.get_field("scores").detach().cpu().double().tolist()
+        labels = bl.get_field("labels").detach().cpu().tolist()
+        for (x1, y1, x2, y2), s, l in zip(boxes.tolist(), scores, labels):
+            out.append({"image_id": int(image_id), "category_id": to_cat(int(l)), "bbox": [x1, y1, x2 - x1, y2 - y1], "score": s})
+    return out
+
+
+def write_coco_results(predictions, path, label_map=None):
+    import json
+    res = coco_results(predictions, label_map)
+    with open(path, "w") as f:
+        json.dump(res, f)
+    return res
+
+
+def inference_images(model, loader, output_folder=None, label_map=None):
+    """Still images: `loader` yields (images, image_ids, original (w, h) per image) batches (data/datasets/still.py: batches, or a DataLoader
+    over StillImageDataset with OrientationBatchSampler and collate_images); every batch goes through model.detect_images with its ids
+    -- so an image's draws, and with them its detections, do not depend on its batch -- and every BoxList is mapped back to the image's
+    original size (BoxList.resize).  -> {image_id: BoxList} on the host; with `output_folder` also `predictions.pth` (that dict) and
+    `coco_results.json` (coco_results with `label_map`).  Evaluation against COCO annotations is not part of this package."""
+    import os
+    predictions = {}
+    cpu = torch.device("cpu")
+    with torch.no_grad():
+        for images, image_ids, sizes in loader:
+            out = model.detect_images(images, image_ids)
+            for bl, image_id, size in zip(out, image_ids, sizes):
+                if int(image_id) in predictions:
+                    raise ValueError("image id %d appears twice" % int(image_id))
+                predictions[int(image_id)] = bl.to(cpu).resize((int(size[0]), int(size[1])))
+    if output_folder:
+        os.makedirs(output_folder, exist_ok=True)
+        torch.save(predictions, os.path.join(output_folder, "predictions.pth"))
+        write_coco_results(predictions, os.path.join(output_folder, "coco_results.json"), label_map)
+    return predictions

@@ -4,7 +4,7 @@ mega_core/modeling/detector/diffusion_det.py:188-896 (inference only) driving li
 Surface kept for `tools/test_net.py`-style callers: `DiffusionDet(cfg)`, `nn.Module` with the
 reference's state_dict names (backbone.bottom_up.*, backbone.fpn_*, head.*, diffusion buffers),
 `.to(device)`, `.eval()`, `forward(images: dict, targets=None) -> list[BoxList]` with the input
-keys of vid_mega.py:236-248, `[]` on calls whose frame_id is not a multiple of INPUT.INFER_BATCH,
+keys of vid_mega.py:236-248 (anything else -- a batch of still images, each with its own size -- goes to `detect_images`), `[]` on calls whose frame_id is not a multiple of INPUT.INFER_BATCH,
 ValueError for targets at test time, AssertionError for degenerate predicted boxes.
 
 The video state machine (per-video reset, local frame queue, once-per-video global memory,
@@ -247,6 +247,8 @@ class DiffusionDet(nn.Module):
         self.host_wait_s = 0.0      # seconds this process spent blocked in the per-batch device->host result copy
         self.video_index = 0
         self.demo = False
+        # images per launch sequence of detect_images; None: INFER_BATCH * LOOKAHEAD_BATCHES, the video path's group (_extract)
+        self.still_chunk = None
 
     # ---- engine (repacked weights on the GPU) -------------------------------------------------
     def _get_engine(self):
@@ -318,6 +320,10 @@ class DiffusionDet(nn.Module):
     def forward(self, images, targets=None):
         if self.training:
             raise NotImplementedError("training is out of scope of the MI355X inference path")
+        if not isinstance(images, dict):          # a batch of still images: no video protocol, no video state
+            if targets is not None and not self.demo:
+                raise ValueError("In testing mode, targets should be None")
+            return self.detect_images(images)
         images = dict(images)
         self._result_cls = self.boxlist_cls or _result_class(images["cur"])
         images["cur"] = to_image_list(images["cur"])
@@ -331,6 +337,96 @@ class DiffusionDet(nn.Module):
             with torch.cuda.device(self.device):
                 return self._forward_test(images["cur"], infos, targets)
         return self._forward_test(images["cur"], infos, targets)
+
+    # ---- still images ---------------------------------------------------------------------------------------------------
+    def detect_images(self, images, image_ids=None):
+        """Detections of a batch of still images, each with its own size -> one BoxList per image, carrying the image's own (w, h).
+
+        images: an ImageList (this package's or another's: `.tensors` [n, 3, H, W] fp32 in [0, 1], `.image_sizes` the un-padded (h, w)), or a
+        list of [3, h, w] tensors, which are zero-padded to one canvas divisible by 32 -- the raw image is padded, the backbone normalises
+        behind it, as the reference's collator and normalizer do (the published DiffusionDet pads after normalising; not built).
+        Every size-dependent step -- the noise boxes' extent, x_start's normalisation, the clip -- reads the image's own (w, h) from one
+        table, checked on the host and uploaded before any kernel is queued.  SAMPLE_STEP 1: backbone, the NUM_HEADS heads at t = 999 on
+        the image's `box_init` draw, top-k / NMS; SAMPLE_STEP > 1: the DDIM loop of _ddim_ensemble from the image's `img` draw.
+        Draws are keyed by image -- noise_fn(kind, image_id, step, 0, (M, 4)), image_ids defaulting to 0 .. n-1 -- and every stage is
+        per-image independent, so an image's detections depend neither on what shares its batch nor on the chunking (launch sequences
+        of `still_chunk` images).  Reads and writes no video state; never replayed from a hipGraph."""
+        if self.training:
+            raise NotImplementedError("training is out of scope of the MI355X inference path")
+        vid = self.cfg.MODEL.VID
+        if vid.MEGA.GLOBAL.ENABLE:
+            raise NotImplementedError("detect_images: MODEL.VID.MEGA.GLOBAL.ENABLE is True, and a still image has no global memory to condition on")
+        if vid.ROI_BOX_HEAD.ATTENTION.ENABLE:
+            raise NotImplementedError("detect_images: MODEL.VID.ROI_BOX_HEAD.ATTENTION.ENABLE is True, and a still image has no local memory to condition on")
+        if self.num_heads_local > 0:
+            raise NotImplementedError("detect_images: MODEL.DiffusionDet.NUM_HEADS_LOCAL is %d: the conditioned heads have nothing to be conditioned on "
+                                      "(still images need NUM_HEADS_LOCAL 0)" % self.num_heads_local)
+        result_cls = self.boxlist_cls or _result_class(images)
+        if isinstance(images, torch.Tensor):
+            images = list(images) if images.dim() == 4 else [images]
+        imgs = to_image_list(images, self.size_divisibility)
+        n, ch, H, W = imgs.tensors.shape
+        if ch != 3 or H % self.size_divisibility or W % self.size_divisibility:
+            raise ValueError("detect_images: the canvas must be [n, 3, H, W] with H and W multiples of %d, got %s"
+                             % (self.size_divisibility, tuple(imgs.tensors.shape)))
+        sizes_wh = [(int(s[1]), int(s[0])) for s in imgs.image_sizes]
+        if len(sizes_wh) != n or any(not (0 < w <= W and 0 < h <= H) for w, h in sizes_wh):
+            raise ValueError("detect_images: image_sizes must hold one (h, w) inside the %d x %d canvas per image, got %s" % (H, W, list(imgs.image_sizes)))
+        ids = list(range(n)) if image_ids is None else [int(i) for i in image_ids]
+        if len(ids) != n:
+            raise ValueError("detect_images: %d image_ids for %d images" % (len(ids), n))
+        if n == 0:
+            return []
+        if self.device.type == "cuda" and self.device.index is not None:
+            with torch.cuda.device(self.device):
+                return self._detect_images(imgs.tensors, sizes_wh, ids, result_cls)
+        return self._detect_images(imgs.tensors, sizes_wh, ids, result_cls)
+
+    def _still_draws(self, kind, ids, step):
+        """[n, M, 4]: the draw of every image of the batch, keyed by its id; an injected noise_fn draws on the host and ONE tensor is uploaded"""
+        shape = (self.num_proposals, 4)
+        if getattr(self.noise_fn, "on_device", False):
+            return self.noise_fn.draw_ids(kind, ids, step, shape, self.device)          # one launch for consecutive ids
+        if self.noise_fn is not None:
+            return torch.stack([self.noise_fn(kind, i, step, 0, shape) for i in ids]).to(self.device, torch.float32)
+        return torch.randn((len(ids),) + shape, device=self.device)
+
+    def _detect_images(self, canvas, sizes_wh, ids, result_cls):
+        eng = self._get_engine()
+        n, M = canvas.shape[0], self.num_proposals
+        H, W = canvas.shape[-2:]
+        pairs = self._time_pairs()
+        # every upload of the call -- the size table, the frames of a host-side loader, the draws -- BEFORE any kernel is queued (the rule
+        # of _extract: a host->device copy from pageable memory blocks the host until the stream has drained)
+        sizes = ops.FrameSizes(torch.tensor(sizes_wh, dtype=torch.float32), self.device)
+        canvas = canvas.to(self.device, torch.float32).contiguous()
+        if self.sampling_timesteps == 1:
+            box_init = self._still_draws("box_init", ids, 0)
+        else:
+            draws = {"img": self._still_draws("img", ids, 0)}
+            for step, (_, time_next) in enumerate(pairs):
+                if time_next >= 0:
+                    draws[step] = (self._still_draws("ddim", ids, step), self._still_draws("renew", ids, step))
+        cap = max(1, int(self.still_chunk or self.infer_batch * self.lookahead))
+        eng.reserve(min(cap, n), H, W, M)
+        outs = []
+        for a in range(0, n, cap):
+            b = min(n, a + cap)
+            feats = eng.backbone_frames([canvas[i:i + 1] for i in range(a, b)])
+            fs = sizes[a:b]
+            if self.sampling_timesteps == 1:
+                t = torch.full((b - a,), pairs[0][0], dtype=torch.long)
+                logits, boxes = self.head.plain_heads(feats, ops.noise_to_boxes(box_init[a:b], self.scale, fs), t)
+                if self.debug_taps is not None:
+                    self.debug_taps.setdefault("still_final_0", []).append((logits, boxes))
+                outs.append(ops.postproc_topk_nms(logits, boxes, fs, None, 0.5, self.use_nms))
+            else:
+                chunk = {k: (v[a:b] if k == "img" else (v[0][a:b], v[1][a:b])) for k, v in draws.items()}
+                outs.append(self._ddim_ensemble(feats, fs, b - a, ids[a], pairs, fs, None, chunk, skip_last=True))
+        results = []          # the host reads the counts only behind the last chunk's launches
+        for k, out in enumerate(outs):
+            results += self._to_boxlists(*out, sizes_wh[k * cap:(k + 1) * cap], result_cls=result_cls)
+        return results
 
     def _reset_video(self):
         self._ahead = {}
@@ -385,8 +481,11 @@ class DiffusionDet(nn.Module):
 
     def model_predictions(self, backbone_feats, images_whwh, x, t, box_extract=0):
         """diffusion_det.py:655-677.  images_whwh: (w, h) of the un-padded frame (same for all frames)."""
-        w, h = images_whwh
-        x_boxes = ops.noise_to_boxes(x, self.scale, w, h)
+        if isinstance(images_whwh, ops.FrameSizes):          # still images: frame f by its own row
+            x_boxes = ops.noise_to_boxes(x, self.scale, images_whwh)
+        else:
+            w, h = images_whwh
+            x_boxes = ops.noise_to_boxes(x, self.scale, w, h)
         if box_extract:
             return self.head(backbone_feats, x_boxes, t, None, box_extract)
         outputs_class, outputs_coord = self.head(backbone_feats, x_boxes, t, None)
@@ -907,17 +1006,18 @@ class DiffusionDet(nn.Module):
         return ([f.index_select(0, sel) for f in src["feats"]],
                 tuple(src[k].index_select(0, sel) for k in ("logits", "boxes", "obj")))
 
-    def _ddim_ensemble(self, feats_cur, whwh, batch, frame_id, pairs, w, h, draws=None):
+    def _ddim_ensemble(self, feats_cur, whwh, batch, frame_id, pairs, w, h, draws=None, skip_last=None):
         """SAMPLE_STEP > 1 (diffusion_det.py:551-627): every step re-runs the 3 heads + global attention +
         cond head on the current noisy boxes, renews low-score boxes, and all but the last step feed the
-        NMS ensemble."""
+        NMS ensemble.  whwh = w: an ops.FrameSizes (h None) for still images, every frame by its own size."""
+        skip_last = self.skip_unobservable if skip_last is None else skip_last
         if draws is None:
             draws = self._ddim_draws(batch, frame_id, pairs)
         img = draws["img"]
         coef = {t: (float(self._sr_host[t]), float(self._srm1_host[t])) for t, _ in pairs}
         ens_logits, ens_boxes = [], []
         for step, (time, time_next) in enumerate(pairs):
-            if time_next < 0 and self.skip_unobservable:
+            if time_next < 0 and skip_last:
                 continue            # nothing reads the last step's outputs (diffusion_det.py:573-575, :607-627)
             t = torch.full((batch,), time, dtype=torch.long)
             outputs_class, outputs_coord = self.model_predictions(feats_cur, whwh, img, t)
@@ -936,7 +1036,8 @@ class DiffusionDet(nn.Module):
             ens_boxes.append(outputs_coord[-1])
         return ops.postproc_topk_nms(torch.stack(ens_logits), torch.stack(ens_boxes), w, h, 0.5, self.use_nms)
 
-    def _to_boxlists(self, ob, osc, ol, oc, size_wh):
+    def _to_boxlists(self, ob, osc, ol, oc, size_wh, result_cls=None):
+        """size_wh: (w, h) of every frame, or a list of one (w, h) per frame (still images)"""
         flat = getattr(ob, "_dvid_flat", None)
         t0 = time.perf_counter()
         if self.results_on_host and flat is not None:
@@ -949,8 +1050,9 @@ class DiffusionDet(nn.Module):
             raise ops._lib.DvidError("DTYPE float32: an activation exceeded the fp16 range (65504) of the split-operand products; the detections of this batch are "
                                      "not valid.  ops.set_option('f32_split', 0) runs the same layers on the fp32 MFMA, which has no range limit")
         results = []
+        result_cls = result_cls or getattr(self, "_result_cls", None) or BoxList
         for b, k in enumerate(counts):
-            bl = (getattr(self, "_result_cls", None) or BoxList)(ob[b, :k], size_wh, mode="xyxy")
+            bl = result_cls(ob[b, :k], size_wh[b] if isinstance(size_wh, list) else size_wh, mode="xyxy")
             bl.add_field("scores", osc[b, :k])
             labels = ol[b, :k].to(torch.int64)
             bl.add_field("labels", labels)

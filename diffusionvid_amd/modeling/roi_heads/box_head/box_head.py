@@ -136,6 +136,24 @@ class DynamicHead(nn.Module):
                                                                       cond=attn_, bad_flag=flag)
         return class_logits2[None], bboxes2[None]
 
+    def plain_heads(self, features, init_bboxes, t):
+        """The NUM_HEADS RCNNHeads on `init_bboxes` and nothing else -> (class_logits [B, M, C], bboxes [B, M, 4]): what forward computes for
+        a model without attention, with no cache popped or filled and no memory read (the detector's still-image path)."""
+        eng = self._engine()
+        feats = self._as_nhwc(features, eng)
+        if len(feats) not in (3, 4):
+            raise ops._lib.DvidError("DynamicHead: the pyramid is [p3, p4, p5] or [p2, p3, p4, p5], got %d maps" % len(feats))
+        bs, num_boxes = init_bboxes.shape[:2]
+        stride = 32 >> (len(feats) - 1)
+        height, width = feats[0].shape[1] * stride, feats[0].shape[2] * stride
+        eng.reserve(bs, height, width, num_boxes)
+        t_host = torch.as_tensor(t).to("cpu", torch.int64)
+        flag = self._bad_flag(init_bboxes.device)
+        class_logits, bboxes, proposal_features = None, init_bboxes, None
+        for i in range(self.num_heads):
+            class_logits, bboxes, proposal_features = eng.rcnn_head(i, feats, height, width, bboxes, proposal_features, t_host, bad_flag=flag)
+        return class_logits, bboxes
+
     # device flag standing in for `assert (pred_boxes[:, 2:] >= pred_boxes[:, :2]).all()` (box_head.py:588)
     def _bad_flag(self, device):
         f = getattr(self, "_flag", None)

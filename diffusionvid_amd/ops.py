@@ -319,21 +319,70 @@ def resize_u8_to_f32(src_hwc, oh, ow, ph, pw, xtab, ytab):
     return out
 
 
-def noise_to_boxes(x, snr_scale, img_w, img_h):
+class FrameSizes:
+    """The per-frame size table of the `_sizes` entry points, checked once on the host and uploaded once: rows (w, h) fp32 [n, 2], every
+    entry positive and finite.  `fs[a:b]` is the table of frames a..b (views of both copies, nothing checked or uploaded again)."""
+
+    def __init__(self, sizes, device, _checked=None):
+        if _checked is not None:
+            self.host, self.dev = _checked
+            return
+        host = torch.as_tensor(sizes).detach().to("cpu", torch.float32)          # a device tensor is read back: the check is on the host
+        if host.dim() != 2 or host.shape[1] != 2:
+            raise _lib.DvidError(f"sizes must be [n_frames, 2] rows of (w, h), got {tuple(host.shape)}")
+        if not bool(torch.isfinite(host).all()) or not bool((host > 0).all()):
+            raise _lib.DvidError("sizes: every (w, h) must be positive and finite")
+        self.host = host.contiguous()
+        self.dev = self.host.to(device)
+
+    def __len__(self):
+        return self.host.shape[0]
+
+    def __getitem__(self, sl):
+        if not isinstance(sl, slice) or sl.step not in (None, 1):
+            raise TypeError("FrameSizes takes contiguous slices")
+        return FrameSizes(None, None, _checked=(self.host[sl], self.dev[sl]))
+
+
+def _is_sizes(img_w):
+    return isinstance(img_w, FrameSizes) or (isinstance(img_w, torch.Tensor) and img_w.dim() >= 1)
+
+
+def frame_sizes(sizes, n, device):
+    """-> the device table [n, 2] of a `sizes` argument: a FrameSizes as it is, a tensor (host or device) checked and uploaded"""
+    fs = sizes if isinstance(sizes, FrameSizes) else FrameSizes(sizes, device)
+    if len(fs) != n:
+        raise _lib.DvidError(f"sizes holds {len(fs)} rows for {n} frames")
+    return fs.dev
+
+
+def noise_to_boxes(x, snr_scale, img_w, img_h=None):
+    """x [..., 4] noise -> xyxy boxes scaled to (img_w, img_h); img_w a `sizes` tensor [n, 2]: x is [n, M, 4], frame f scaled to sizes[f]."""
     x = _cuda(x, torch.float32)
     out = torch.empty_like(x)
+    if _is_sizes(img_w):
+        if x.dim() != 3 or x.shape[-1] != 4:
+            raise _lib.DvidError(f"noise_to_boxes with a sizes table takes x [n, M, 4], got {tuple(x.shape)}")
+        sizes = frame_sizes(img_w, x.shape[0], x.device)
+        if x.numel():
+            call("dvid_noise_to_boxes_sizes", ptr(x), ptr(out), x.numel() // 4, x.shape[1], float(snr_scale), ptr(sizes), stream_ptr())
+        return out
     call("dvid_noise_to_boxes", ptr(x), ptr(out), x.numel() // 4, float(snr_scale), float(img_w), float(img_h), stream_ptr())
     return out
 
 
-def counter_normal(key0, n_images, shape, device=None):
-    """[n_images, *shape] N(0, 1) draws generated on the device: image i is the stream keyed `key0 + i` (dvid_counter_normal)."""
+def counter_normal(key0, n_images, shape, device=None, key_stride=1):
+    """[n_images, *shape] N(0, 1) draws generated on the device: image i is the stream keyed `key0 + i * key_stride` (dvid_counter_normal,
+    dvid_counter_normal_strided)."""
     if not torch.cuda.is_available():
         raise _lib.DvidError("no HIP device visible: counter_normal draws on the GPU (no CPU fallback; the CPU restatement is oracle/noise.py)")
     out = torch.empty((n_images,) + tuple(shape), dtype=torch.float32, device=device or torch.device("cuda", torch.cuda.current_device()))
     per = 1
     for v in shape:
         per *= int(v)
+    if int(key_stride) != 1:
+        call("dvid_counter_normal_strided", ptr(out), per, int(n_images), int(key0) & 0xFFFFFFFFFFFFFFFF, int(key_stride) & 0xFFFFFFFFFFFFFFFF, stream_ptr())
+        return out
     call("dvid_counter_normal", ptr(out), per, int(n_images), int(key0) & 0xFFFFFFFFFFFFFFFF, stream_ptr())
     return out
 
@@ -345,6 +394,12 @@ def ddim_renew_step(logits, boxes, x_t, noise, fresh, whwh, snr_scale, sqrt_reci
     noise, fresh = _cuda(noise, torch.float32), _cuda(fresh, torch.float32)
     n, M, c = logits.shape
     out = torch.empty_like(x_t)
+    if _is_sizes(whwh):          # a sizes table [n, 2]: frame f normalised by its own (w, h)
+        sizes = frame_sizes(whwh, n, logits.device)
+        call("dvid_ddim_renew_step_sizes", ptr(logits), ptr(boxes), ptr(x_t), ptr(noise), ptr(fresh), ptr(out), n, M, c, ptr(sizes),
+             float(snr_scale), float(sqrt_recip_ac), float(sqrt_recipm1_ac), float(sqrt_ac_next), float(coef_c), float(sigma), float(keep_thr),
+             stream_ptr())
+        return out
     call("dvid_ddim_renew_step", ptr(logits), ptr(boxes), ptr(x_t), ptr(noise), ptr(fresh), ptr(out), n, M, c, float(whwh[0]),
          float(whwh[1]), float(snr_scale), float(sqrt_recip_ac), float(sqrt_recipm1_ac), float(sqrt_ac_next), float(coef_c),
          float(sigma), float(keep_thr), stream_ptr())
@@ -377,8 +432,9 @@ def postproc_scratch_bytes(nsets, n_frames, m):
     return int(_lib.load().dvid_postproc_scratch_bytes(int(nsets), int(n_frames), int(m)))
 
 
-def postproc_topk_nms(logits, boxes, img_w, img_h, iou=0.5, use_nms=True):
-    """logits [S, n, M, C] (or [n, M, C]), boxes [S, n, M, 4] -> (boxes [n,S*M,4], scores, labels int32, counts int32)."""
+def postproc_topk_nms(logits, boxes, img_w, img_h=None, iou=0.5, use_nms=True):
+    """logits [S, n, M, C] (or [n, M, C]), boxes [S, n, M, 4] -> (boxes [n,S*M,4], scores, labels int32, counts int32).
+    img_w a `sizes` tensor [n, 2]: frame f is clipped to sizes[f]."""
     if logits.dim() == 3:
         logits, boxes = logits[None], boxes[None]
     logits, boxes = _cuda(logits, torch.float32), _cuda(boxes, torch.float32)
@@ -386,6 +442,11 @@ def postproc_topk_nms(logits, boxes, img_w, img_h, iou=0.5, use_nms=True):
     dev = logits.device
     ob, osc, ol, oc = split_detection_buffer(torch.empty((n * S * M * 6 + n,), dtype=torch.float32, device=dev), n, S * M)
     scratch = torch.empty(((postproc_scratch_bytes(S, n, M) + 3) // 4,), dtype=torch.float32, device=dev)
+    if _is_sizes(img_w):
+        sizes = frame_sizes(img_w, n, dev)
+        call("dvid_postproc_topk_nms_sizes", ptr(logits), ptr(boxes), S, n, M, c, ptr(sizes), float(iou), int(use_nms),
+             ptr(ob), ptr(osc), ptr(ol), ptr(oc), ptr(scratch), stream_ptr())
+        return ob, osc, ol, oc
     call("dvid_postproc_topk_nms", ptr(logits), ptr(boxes), S, n, M, c, float(img_w), float(img_h), float(iou), int(use_nms),
          ptr(ob), ptr(osc), ptr(ol), ptr(oc), ptr(scratch), stream_ptr())
     return ob, osc, ol, oc
@@ -408,7 +469,7 @@ def topk_candidates_stream(logits, boxes):
     return cb, cs, cl
 
 
-def nms_frames_tiled(cand_boxes, cand_scores, cand_labels, img_w, img_h, iou=0.5, use_nms=True):
+def nms_frames_tiled(cand_boxes, cand_scores, cand_labels, img_w, img_h=None, iou=0.5, use_nms=True):
     """The tiled NMS on its own, at any 1 <= N <= NMS_MAX_CANDIDATES: cand_boxes [n, N, 4] (unclipped xyxy), cand_scores [n, N], cand_labels
     [n, N] int32 -> (boxes [n, N, 4], scores, labels int32, counts int32) as postproc_topk_nms returns them."""
     cand_boxes, cand_scores = _cuda(cand_boxes, torch.float32), _cuda(cand_scores, torch.float32)
@@ -418,6 +479,11 @@ def nms_frames_tiled(cand_boxes, cand_scores, cand_labels, img_w, img_h, iou=0.5
     dev = cand_boxes.device
     ob, osc, ol, oc = split_detection_buffer(torch.empty((n * N * 6 + n,), dtype=torch.float32, device=dev), n, N)
     scratch = torch.empty((max(1, (int(_lib.load().dvid_nms_tiled_scratch_bytes(n, N)) + 3) // 4),), dtype=torch.float32, device=dev)
+    if _is_sizes(img_w):          # a sizes table [n, 2]: frame f is clipped to sizes[f]
+        sizes = frame_sizes(img_w, n, dev)
+        call("dvid_nms_frames_tiled_sizes", ptr(cand_boxes), ptr(cand_scores), ptr(cand_labels), n, N, ptr(sizes), float(iou),
+             int(use_nms), N, ptr(ob), ptr(osc), ptr(ol), ptr(oc), ptr(scratch), stream_ptr())
+        return ob, osc, ol, oc
     call("dvid_nms_frames_tiled", ptr(cand_boxes), ptr(cand_scores), ptr(cand_labels), n, N, float(img_w), float(img_h), float(iou),
          int(use_nms), N, ptr(ob), ptr(osc), ptr(ol), ptr(oc), ptr(scratch), stream_ptr())
     return ob, osc, ol, oc

@@ -259,5 +259,19 @@ class DeviceNoise:
         from .. import ops
         return ops.counter_normal(self.key(kind, frame_id, step, first_image), n_images, shape, device)
 
+    def draw_ids(self, kind, ids, step, shape, device=None):
+        """[len(ids), *shape]: the draws keyed (kind, id, step, image 0) of a batch of still images -- ONE launch when the ids are
+        consecutive (their keys lie a fixed stride apart), else one per run of consecutive ids"""
+        import torch
+        from .. import ops
+        ids = [int(i) for i in ids]
+        stride = self.key(kind, 1, step, 0) - self.key(kind, 0, step, 0)
+        runs, a = [], 0
+        for b in range(1, len(ids) + 1):
+            if b == len(ids) or ids[b] != ids[b - 1] + 1:
+                runs.append(ops.counter_normal(self.key(kind, ids[a], step, 0), b - a, shape, device, key_stride=stride))
+                a = b
+        return runs[0] if len(runs) == 1 else torch.cat(runs)
+
     def __call__(self, kind, frame_id, step, image, shape, video=None):
         return self.draw(kind, frame_id, step, image, 1, shape)[0]

@@ -228,7 +228,16 @@ int dvid_select_topk_features(const float* logits, int n_frames, int m, int num_
 /* N(0, 1) draws as a pure function of (key, element index): out[i][e], i < n_images, e < per_image, = element e of the stream
  * keyed key0 + i.  Philox4x32-10 + fp64 Box-Muller rounded to fp32; oracle/noise.py restates it on the CPU (same values). */
 int dvid_counter_normal(float* out, int64_t per_image, int n_images, uint64_t key0, void* stream);
+/* The same with image i keyed key0 + i * key_stride (key_stride 1 is dvid_counter_normal): one launch for a batch of still images whose
+ * draws are keyed by consecutive image ids, which lie a fixed stride apart in key space. */
+int dvid_counter_normal_strided(float* out, int64_t per_image, int n_images, uint64_t key0, uint64_t key_stride, void* stream);
 int dvid_noise_to_boxes(const float* x, float* boxes, int n, float snr_scale, float img_w, float img_h, void* stream);
+/* The `_sizes` entries (dvid_version >= 3): the four size-dependent steps for a batch of still images, each with its own size.  Same
+ * arguments as their siblings, with `sizes` where img_w, img_h stood: a DEVICE table of fp32 [n_frames][2], row f = (w, h) of the
+ * un-padded frame f.  Precondition: every entry is positive and finite (not checked on the device).  The same kernels and the same
+ * expressions: a table whose rows are all (w, h) gives the bits of the sibling called with (w, h).
+ * dvid_noise_to_boxes_sizes: n boxes, m per frame (n a multiple of m, the table holds n / m rows): box i is scaled by row i / m. */
+int dvid_noise_to_boxes_sizes(const float* x, float* boxes, int n, int m, float snr_scale, const float* sizes, void* stream);
 /* Box renewal + DDIM update (eta = 1) of diffusion_det.py:559-596 (+ :649-653, :666-672): per frame, boxes whose
  * sigmoid(max logit) > keep_thr are kept (index order), updated as x0*sqrt_ac_next + coef_c*eps + sigma*noise[j],
  * and the tail is refilled from `fresh`.  All tensors [n_frames, m, 4] (logits [n_frames, m, c]). */
@@ -236,6 +245,10 @@ int dvid_ddim_renew_step(const float* logits, const float* boxes, const float* x
                          float* x_next, int n_frames, int m, int c, float img_w, float img_h, float snr_scale,
                          float sqrt_recip_ac, float sqrt_recipm1_ac, float sqrt_ac_next, float coef_c, float sigma, float keep_thr,
                          void* stream);
+/* ... every frame's x_start normalised by its own row of `sizes` (see dvid_noise_to_boxes_sizes) */
+int dvid_ddim_renew_step_sizes(const float* logits, const float* boxes, const float* x_t, const float* noise, const float* fresh,
+                               float* x_next, int n_frames, int m, int c, const float* sizes, float snr_scale, float sqrt_recip_ac,
+                               float sqrt_recipm1_ac, float sqrt_ac_next, float coef_c, float sigma, float keep_thr, void* stream);
 /* logits [nsets, n_frames, m, c], boxes [nsets, n_frames, m, 4]; outputs [n_frames, nsets*m, ...] sorted by
  * descending score, first counts[f] entries valid.  scratch: >= dvid_postproc_scratch_bytes(nsets, n_frames, m) bytes, 16-byte aligned.
  * nsets * m candidates per frame, at most DVID_NMS_MAX_CANDIDATES (DVID_ERR_UNSUPPORTED beyond: torchvision's batched_nms itself
@@ -246,7 +259,11 @@ int dvid_ddim_renew_step(const float* logits, const float* boxes, const float* x
 int dvid_postproc_topk_nms(const float* logits, const float* boxes, int nsets, int n_frames, int m, int c, float img_w,
                            float img_h, float iou_threshold, int use_nms, float* out_boxes, float* out_scores,
                            int* out_labels, int* out_counts, void* scratch, void* stream);
-/* Bytes of scratch dvid_postproc_topk_nms needs for that shape: n_frames*nsets*m*24 where the single-kernel NMS runs, more where the
+/* ... frame f's survivors clipped to its own row of `sizes` (see dvid_noise_to_boxes_sizes); the selection and the NMS do not read it */
+int dvid_postproc_topk_nms_sizes(const float* logits, const float* boxes, int nsets, int n_frames, int m, int c, const float* sizes,
+                                 float iou_threshold, int use_nms, float* out_boxes, float* out_scores, int* out_labels,
+                                 int* out_counts, void* scratch, void* stream);
+/* Bytes of scratch dvid_postproc_topk_nms (and _sizes) needs for that shape: n_frames*nsets*m*24 where the single-kernel NMS runs, more where the
  * tiled form does (0 for a shape with no work). */
 int64_t dvid_postproc_scratch_bytes(int nsets, int n_frames, int m);
 /* The candidate selection of dvid_postproc_topk_nms on its own, in its streaming form (csrc/postproc.hip: topk_stream_kernel), forced at
@@ -267,6 +284,9 @@ int dvid_topk_candidates_stream(const float* logits, const float* boxes, int nse
 int dvid_nms_frames_tiled(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_frames, int n, float img_w,
                           float img_h, float iou_threshold, int use_nms, int out_cap, float* out_boxes, float* out_scores,
                           int* out_labels, int* out_counts, void* scratch, void* stream);
+int dvid_nms_frames_tiled_sizes(const float* cand_boxes, const float* cand_scores, const int* cand_labels, int n_frames, int n,
+                                const float* sizes, float iou_threshold, int use_nms, int out_cap, float* out_boxes, float* out_scores,
+                                int* out_labels, int* out_counts, void* scratch, void* stream);
 int64_t dvid_nms_tiled_scratch_bytes(int n_frames, int n);
 /* Seq-NMS (TEST.SEQ_NMS; the reference's seq_nms.py, its engine's inference.py:54-62) over the detections of n_videos videos, as one
  * launch with a workgroup per (video, class) (csrc/seqnms.hip).  dets [frames, cap, 6] (device; a row = xyxy box, score, label as a float, labels 1 ..
