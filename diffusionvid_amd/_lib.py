@@ -51,6 +51,8 @@ SIGNATURES = {
                                c_void_p, C.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dvid_global_xattn": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "dvid_global_memory_project": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "dvid_global_memory_project_groups": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "dvid_global_xattn_groups": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dvid_local_memory_project": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "dvid_local_xattn": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dvid_roialign_v2_multilevel": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
@@ -86,6 +88,10 @@ SIGNATURES = {
     "dvid_cdist": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "dvid_fps_greedy": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dvid_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "dvid_cdist_groups": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dvid_fps_greedy_groups": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dvid_gather_rows_groups": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "dvid_update_memory_groups": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dvid_conv2d_nhwc_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 13 + [c_void_p]),
     "dvid_bottleneck64_tail_f16": (c_int, [c_void_p] * 10 + [c_int] + [c_void_p] * 2 + [c_int] * 3 + [c_void_p]),
     "dvid_bottleneck128_tail_f16": (c_int, [c_void_p] * 10 + [c_int] * 3 + [c_void_p]),

@@ -416,6 +416,60 @@ int dvid_global_xattn(dvid_model* m, const float* query, int rows, const float* 
     return DVID_OK;
 }
 
+// `groups` global memories of `lk` rows each -- one per live stream -- projected as dvid_local_memory_project projects the local ones: one
+// K/V linear over all groups * lk rows, into a buffer of its OWN (gkvproj).  kvproj / mem_lk, the projection a video holds between its
+// calls, is neither read nor written.
+int dvid_global_memory_project_groups(dvid_model* m, const float* memory, int lk, int groups, void* stream) {
+    g_err[0] = 0;
+    if (!m || !m->finalized || !m->gq.w) FAIL(DVID_ERR_STATE, "model not finalized or has no global attention");
+    if (!memory || lk <= 0 || groups <= 0) FAIL(DVID_ERR_ARG, "empty global memory (%d groups of %d rows)", groups, lk);
+    if ((long)lk * groups > (1L << 24)) FAIL(DVID_ERR_ARG, "global memory of %d x %d rows", groups, lk);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int d = m->cfg.hidden_dim, n = lk * groups;
+    m->gmem_lk = m->gmem_groups = 0;
+    TRY(m->gkvproj.ensure(((size_t)n + 64) * 2 * d * 4, &m->ws_gen));
+    if (m->precision == 1) {
+        TRY(linear_run32(m->gkv, memory, n, m->gkvproj.as<float>(), 0, s));
+    } else {
+        TRY(m->gmem16.ensure((size_t)n * d * 2, &m->ws_gen));
+        TRY(dvid_f32_to_f16_launch(memory, m->gmem16.as<half_t>(), (long)n * d, s));
+        TRY(linear_run(m->gkv, m->gmem16.as<half_t>(), n, m->gkvproj.p, 0, 0, s));
+    }
+    m->gmem_lk = lk;
+    m->gmem_groups = groups;
+    return DVID_OK;
+}
+
+// out = out_proj(MHA(q_proj(query), K_g, V_g)): rows / groups consecutive query rows per group against that group's projected memory; the
+// kernels of dvid_global_xattn with batch = groups and the batch strides, Q and out projections over all rows at once.
+int dvid_global_xattn_groups(dvid_model* m, const float* query, int rows, int groups, int lk, float* out, void* stream) {
+    g_err[0] = 0;
+    if (!m || !m->finalized || !m->gq.w) FAIL(DVID_ERR_STATE, "model not finalized or has no global attention");
+    if (!query || !out || rows <= 0 || groups <= 0 || rows % groups) FAIL(DVID_ERR_ARG, "%d query rows in %d groups", rows, groups);
+    if (m->gmem_lk <= 0 || lk != m->gmem_lk || groups != m->gmem_groups)
+        FAIL(DVID_ERR_STATE, "no projected global memories of %d x %d rows (call dvid_global_memory_project_groups)", groups, lk);
+    if (rows > m->ws_frames * m->ws_boxes) FAIL(DVID_ERR_STATE, "workspace too small");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int d = m->cfg.hidden_dim, lq = rows / groups;
+    if (m->precision == 1) {
+        float* qp = m->h16a.as<float>();
+        float* at = m->attn16.as<float>();
+        const float* kv32 = m->gkvproj.as<float>();
+        TRY(linear_run32(m->gq, query, rows, qp, 0, s));
+        TRY(dvid_f32_mha_launch(qp, kv32, kv32 + d, at, groups, lq, lk, m->cfg.nheads, d, 2 * d, d, (long)lq * d, (long)lk * 2 * d, (long)lq * d, s));
+        TRY(linear_run32(m->gout, at, rows, out, 0, s));
+        return DVID_OK;
+    }
+    TRY(dvid_f32_to_f16_launch(query, m->h16a.as<half_t>(), (long)rows * d, s));
+    TRY(linear_run(m->gq, m->h16a.as<half_t>(), rows, m->h16b.p, 0, 0, s));
+    const half_t* kv = m->gkvproj.as<half_t>();
+    TRY(m->vt.ensure((size_t)groups * m->cfg.nheads * 32 * (((size_t)lk + 31) / 32 * 32 + 32) * 2, &m->ws_gen));          // per group
+    TRY(dvid_mha_mfma_launch(m->h16b.as<half_t>(), kv, kv + d, m->attn16.as<half_t>(), m->vt.as<half_t>(), groups, lq, lk, m->cfg.nheads, d, 2 * d, d,
+                             (long)lq * d, (long)lk * 2 * d, (long)lq * d, s));
+    TRY(linear_run(m->gout, m->attn16.as<half_t>(), rows, out, 0, 1, s));
+    return DVID_OK;
+}
+
 // K/V projections of `groups` local memories of `lk` rows each (box_head.py:338, :362: key = value = proposal_feats_local[stage]) into
 // the model's own buffer: one linear over all groups * lk rows.
 int dvid_local_memory_project(dvid_model* m, int stage, const float* memory, int lk, int groups, void* stream) {

@@ -213,6 +213,10 @@ int dvid_seq_nms_launch(const float* dets, const int* counts, const int* class_c
 int dvid_cdist_launch(const float* x, int n, int d, float* dist, hipStream_t s);
 int dvid_fps_launch(const float* dist, int n, int m, int bs_emul, int* idx, hipStream_t s);
 int dvid_gather_rows_launch(const float* x, const int* idx, float* y, int m, int d, hipStream_t s);
+// `groups` problems of one shape per launch, each computed as the single form computes it
+int dvid_cdist_groups_launch(const float* x, int groups, int n, int d, float* dist, hipStream_t s);
+int dvid_fps_groups_launch(const float* dist, int groups, int n, int m, int bs_emul, int* idx, hipStream_t s);
+int dvid_gather_rows_groups_launch(const float* x, const int* idx, float* y, int groups, int n, int m, int d, hipStream_t s);
 
 // DTYPE float32 (fp32 storage, fp32-grade products).  f32.hip: the implicit GEMM of every convolution and linear layer -- exact fp32 products
 // on v_mfma_f32_32x32x2_f32, or split (hi, lo) fp16 operands on three passes of the fp16 MFMA (f32_split.h)

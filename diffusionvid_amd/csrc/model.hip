@@ -108,7 +108,7 @@ int linear_run32(const ConvW& w, const float* in, int rows, float* out, int relu
 
 extern "C" {
 const char* dvid_last_error(void) { return g_err; }
-int dvid_version(void) { return 3; }
+int dvid_version(void) { return 4; }
 
 int dvid_model_create(const dvid_config* cfg, dvid_model** out) {
     g_err[0] = 0;
@@ -134,7 +134,7 @@ int dvid_model_destroy(dvid_model* m) {
     for (void* p : m->owned) (void)hipFree(p);
     DevBuf* bufs[] = {&m->img8, &m->bufX, &m->bufY, &m->bufT1, &m->bufT2, &m->bufSC, &m->c2, &m->c3, &m->c4, &m->c5, &m->lat[0], &m->sw_x, &m->sw_x2, &m->sw_ln16, &m->sw_qkv16, &m->sw_attn16, &m->sw_h16,
                       &m->lat[1], &m->lat[2], &m->lat[3], &m->roi, &m->params, &m->dyn, &m->qkv, &m->attn16, &m->f32a, &m->f32b, &m->f32c,
-                      &m->f32d, &m->h16a, &m->h16b, &m->hid16, &m->ss, &m->deltas, &m->kvproj, &m->mem16, &m->splitk, &m->vt, &m->lkvproj, &m->lmem16};
+                      &m->f32d, &m->h16a, &m->h16b, &m->hid16, &m->ss, &m->deltas, &m->kvproj, &m->mem16, &m->splitk, &m->vt, &m->lkvproj, &m->lmem16, &m->gkvproj, &m->gmem16};
     for (DevBuf* b : bufs) b->release();
     for (DevBuf& b : m->ss_slabs) b.release();
     delete m;

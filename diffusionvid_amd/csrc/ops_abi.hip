@@ -300,6 +300,49 @@ int dvid_gather_rows(const float* x, const int* idx, float* y, int mm, int d, vo
     return DVID_OK;
 }
 
+// the grouped forms: every argument is checked here, before the first launch
+static int groups_args_ok(const char* what, int groups, int n, int mm, int d) {
+    if (groups < 1 || groups > 65535 || n < 1 || mm < 1 || mm > n || d < 4 || d % 4)
+        FAIL(DVID_ERR_ARG, "%s: 1 <= groups <= 65535, 1 <= m <= n and d %% 4 == 0 (got groups %d, n %d, m %d, d %d)", what, groups, n, mm, d);
+    const long long need = (long long)groups * n * n * 4;
+    if (need > DVID_UPDATE_MEMORY_MAX_SCRATCH_BYTES)
+        FAIL(DVID_ERR_UNSUPPORTED, "%s: %d groups x %d x %d distances are %lld bytes, the limit is %lld (DVID_UPDATE_MEMORY_MAX_SCRATCH_BYTES): "
+             "run fewer groups per call", what, groups, n, n, need, (long long)DVID_UPDATE_MEMORY_MAX_SCRATCH_BYTES);
+    return DVID_OK;
+}
+int dvid_cdist_groups(const float* x, int groups, int n, int d, float* dist, void* stream) {
+    g_err[0] = 0;
+    if (const int rc = groups_args_ok("dvid_cdist_groups", groups, n, 1, d); rc != DVID_OK) return rc;          // the shape first: a caller over the limit has no buffer to give
+    if (!x || !dist) FAIL(DVID_ERR_ARG, "dvid_cdist_groups: null pointer");
+    TRY(dvid_cdist_groups_launch(x, groups, n, d, dist, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+int dvid_fps_greedy_groups(const float* dist, int groups, int n, int mm, int bs_emul, int* idx, void* stream) {
+    g_err[0] = 0;
+    if (!dist || !idx) FAIL(DVID_ERR_ARG, "dvid_fps_greedy_groups: null pointer");
+    if (const int rc = groups_args_ok("dvid_fps_greedy_groups", groups, n, mm, 4); rc != DVID_OK) return rc;
+    TRY(dvid_fps_groups_launch(dist, groups, n, mm, bs_emul, idx, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+int dvid_gather_rows_groups(const float* x, const int* idx, float* y, int groups, int n, int mm, int d, void* stream) {
+    g_err[0] = 0;
+    if (!x || !idx || !y) FAIL(DVID_ERR_ARG, "dvid_gather_rows_groups: null pointer");
+    if (groups < 1 || groups > 65535 || n < 1 || mm < 1 || d < 4 || d % 4)
+        FAIL(DVID_ERR_ARG, "dvid_gather_rows_groups: 1 <= groups <= 65535, n >= 1, m >= 1 and d %% 4 == 0 (got groups %d, n %d, m %d, d %d)", groups, n, mm, d);
+    TRY(dvid_gather_rows_groups_launch(x, idx, y, groups, n, mm, d, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+int dvid_update_memory_groups(const float* merged, int groups, int n, int d, int mm, float* dist_scratch, int* idx, float* out, void* stream) {
+    g_err[0] = 0;
+    if (const int rc = groups_args_ok("dvid_update_memory_groups", groups, n, mm, d); rc != DVID_OK) return rc;
+    if (!merged || !dist_scratch || !idx || !out) FAIL(DVID_ERR_ARG, "dvid_update_memory_groups: null pointer");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    TRY(dvid_cdist_groups_launch(merged, groups, n, d, dist_scratch, s));
+    TRY(dvid_fps_groups_launch(dist_scratch, groups, n, mm, 0, idx, s));
+    TRY(dvid_gather_rows_groups_launch(merged, idx, out, groups, n, mm, d, s));
+    return DVID_OK;
+}
+
 int dvid_conv2d_nhwc_f16(const void* in, const void* w, const float* bias, const void* residual, void* out, int n, int h, int wd,
                          int cin, int cout, int kh, int kw, int stride, int pad, int kpad, int relu, int out_f32, int residual_mode,
                          void* stream) {

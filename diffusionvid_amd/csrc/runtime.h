@@ -221,6 +221,8 @@ struct dvid_model {
     int mem_lk = 0;       // rows of the global memory whose K/V projections sit in kvproj (0: none)
     DevBuf lkvproj, lmem16;          // K | V rows of the projected local memories, [groups * lk, 2 d]
     int local_lk = 0, local_groups = 0;          // shape of what lkvproj holds (0: nothing projected)
+    DevBuf gkvproj, gmem16;          // K | V rows of `groups` projected GLOBAL memories (one per live stream), [groups * lk, 2 d]: beside kvproj, never in it
+    int gmem_lk = 0, gmem_groups = 0;          // shape of what gkvproj holds (0: nothing projected)
 
     // sub-batch chains (backbone.hip: run_chains)
     int nchain = 2;

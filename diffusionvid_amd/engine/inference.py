@@ -149,6 +149,61 @@ def compute_on_dataset(model, dataset, indices, device, timer=None, do_seq_nms=F
     return results
 
 
+def stream_schedule(dataset, n_streams, indices=None):
+    """The slot scheduling of compute_on_streams, host logic: the dataset's videos (a video = the run of indices from a frame 0 up to the
+    next one), `n_streams` at a time.  Yields one step after the other as {slot: (dataset index, item)}; a slot delivers its video's
+    calls in order, one per step, and takes the next video not yet started on the step after its own ends, so every index is delivered
+    exactly once and a slot is idle only when no video is left.  Video boundaries come from the dataset's `frame_seg_id` table (the
+    reference's VIDMEGADataset keeps it, vid_mega.py:10-33) without loading a frame; a dataset without one is read once for them."""
+    if int(n_streams) < 1:
+        raise ValueError("n_streams must be at least 1, got %r" % (n_streams,))
+    indices = list(range(len(dataset)) if indices is None else indices)
+    seg_id = getattr(dataset, "frame_seg_id", None)
+    videos = []
+    for idx in indices:
+        first = (seg_id[idx] == 0) if seg_id is not None else (dataset[idx][0]["frame_category"] == 0)
+        if first or not videos:
+            videos.append([])
+        videos[-1].append(idx)
+    videos = iter(videos)
+    slots = {s: iter(v) for s, v in zip(range(int(n_streams)), videos)}
+    while slots:
+        step = {}
+        for s in sorted(slots):
+            idx = next(slots[s], None)
+            if idx is None:          # this slot's video ended on the previous step: the next video, now
+                v = next(videos, None)
+                if v is None:
+                    del slots[s]
+                    continue
+                slots[s] = iter(v)
+                idx = next(slots[s])
+            step[s] = (idx, dataset[idx])
+        if step:
+            yield step
+
+
+def compute_on_streams(model, dataset, n_streams, indices=None, timer=None):
+    """A streaming-protocol dataset's videos `n_streams` at a time through one StreamSet (DiffusionDet.open_streams): every step is one call
+    of each running video.  Returns predictions by image id as compute_on_dataset does (CPU BoxLists), so do_vid_evaluation and
+    predictions.pth work unchanged; per stream the detections are those of compute_on_dataset on that video."""
+    model.eval()
+    streams = model.open_streams()
+    results = {}
+    cpu = torch.device("cpu")
+    for step in stream_schedule(dataset, n_streams, indices):
+        with torch.no_grad():
+            t0 = time.perf_counter()
+            out = streams.step({s: item[0] for s, (_, item) in step.items()})
+            if timer is not None:
+                if torch.cuda.is_available():
+                    torch.cuda.synchronize()
+                timer.append(time.perf_counter() - t0)
+        for s, (_, item) in step.items():
+            results.update({img_id: r.to(cpu) for img_id, r in zip(item[2], out[s])})
+    return results
+
+
 def max_detections(results):
     """largest per-frame detection count of a shard (the x4 ensemble keeps up to 3 x NUM_PROPOSALS candidates through
     NMS, diffusion_det.py:607-627, so the count is a property of the data, not of the config)"""

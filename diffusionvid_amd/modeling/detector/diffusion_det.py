@@ -479,6 +479,14 @@ class DiffusionDet(nn.Module):
         self._reset_video()
         self._set_global_memory([m.to(self.device, torch.float32) for m in memory])
 
+    # ---- several live streams on this model (detector/streams.py) ------------------------------------------------
+    def open_streams(self, frames_per_launch=32):
+        """A StreamSet on this model's weights: `step({stream id: item})` runs one call of the streaming protocol of each of several
+        streams together.  frames_per_launch: frames per extraction launch sequence (32 = the 8 local + 24 global frames the reference
+        protocol's first call already runs as one).  Refused for every other protocol, with the keys and values in the message."""
+        from .streams import StreamSet
+        return StreamSet(self, frames_per_launch)
+
     def model_predictions(self, backbone_feats, images_whwh, x, t, box_extract=0):
         """diffusion_det.py:655-677.  images_whwh: (w, h) of the un-padded frame (same for all frames)."""
         if isinstance(images_whwh, ops.FrameSizes):          # still images: frame f by its own row

@@ -57,6 +57,9 @@ class DynamicHead(nn.Module):
         self.proposal_feats_global = [None, None]
         self.proposal_feats_local = [None, None]
         self.proposal_feats_local_groups = 1
+        # this repo's addition: None, or a tensor [G, lk, d] of G global memories read INSTEAD of proposal_feats_global[0] -- the pass's frames
+        # are G equal blocks, block g attending memory g (detector/streams.py sets it around a step's final stage and clears it)
+        self.proposal_feats_global_groups = None
         self.proposals_feat_cur = []
         self._engine_provider = engine_provider
 
@@ -118,10 +121,14 @@ class DynamicHead(nn.Module):
 
         if self.global_enable:
             # (with local attention also on, its product would be overwritten here: it is not launched, see the module docstring)
-            memory = self.proposal_feats_global[0]
+            grouped = self.proposal_feats_global_groups
+            memory = self.proposal_feats_global[0] if grouped is None else grouped
             if memory is None:
                 raise RuntimeError("proposal_feats_global is empty: the detector fills it from the global frames of a video")
-            attn_ = eng.global_xattn(proposal_features, memory)                           # box_head.py:366-394
+            if grouped is not None:          # [G, lk, d], one memory per live stream: frame block g attends memory g
+                attn_ = eng.global_xattn_groups(proposal_features, memory)
+            else:
+                attn_ = eng.global_xattn(proposal_features, memory)                       # box_head.py:366-394
         else:
             stage = self.local_stage - 1                                                  # the only stage whose result survives
             memory = self.proposal_feats_local[stage]

@@ -582,6 +582,64 @@ def update_erase_memory(feats_new, feats_mem, target_size):
     return gather_rows(merged, idx), idx
 
 
+# ---- the grouped forms: G independent problems of one shape per launch, each computed as the single form computes it ----
+UPDATE_MEMORY_MAX_SCRATCH_BYTES = 1 << 30          # DVID_UPDATE_MEMORY_MAX_SCRATCH_BYTES of include/dvid_hip.h
+
+
+def cdist_groups(x):
+    """x [G, n, d] -> [G, n, n]: group g bit-equal to cdist(x[g])"""
+    x = _cuda(x, torch.float32)
+    G, n, d = x.shape
+    need = G * n * n * 4
+    out = torch.empty((G, n, n) if need <= UPDATE_MEMORY_MAX_SCRATCH_BYTES else (0,), dtype=torch.float32, device=x.device)          # over the limit: the library refuses before it writes
+    call("dvid_cdist_groups", ptr(x), G, n, d, ptr(out), stream_ptr())
+    return out
+
+
+def fps_greedy_groups(dist, m, bs_emul=0):
+    """dist [G, n, n] -> int32 [G, m]: the picks of fps_greedy(dist[g], m), the G sweeps side by side (one workgroup each)"""
+    dist = _cuda(dist, torch.float32)
+    G, n = dist.shape[:2]
+    idx = torch.empty((G, m), dtype=torch.int32, device=dist.device)
+    call("dvid_fps_greedy_groups", ptr(dist), G, n, m, bs_emul, ptr(idx), stream_ptr())
+    return idx
+
+
+def gather_rows_groups(x, idx, out=None):
+    """out[g, r, :] = x[g, idx[g, r], :]; x [G, n, d], idx int32 [G, m] -> [G, m, d] (written into `out` when one is given)"""
+    x = _cuda(x, torch.float32)
+    idx = _cuda(idx, torch.int32)
+    G, n, d = x.shape
+    m = idx.shape[1]
+    if out is None:
+        out = torch.empty((G, m, d), dtype=torch.float32, device=x.device)
+    assert out.is_contiguous() and tuple(out.shape) == (G, m, d) and out.dtype == torch.float32
+    call("dvid_gather_rows_groups", ptr(x), ptr(idx), ptr(out), G, n, m, d, stream_ptr())
+    return out
+
+
+def update_erase_memory_groups(feats_new, feats_mem, target_size, out=None):
+    """update_erase_memory for G memories of one shape at once: feats_new [G, k, d], feats_mem [G, r, d] or None -> (memory
+    [G, min(r + k, target), d], idx int32 [G, target] or None), group g bit-equal to update_erase_memory(feats_new[g], feats_mem[g], target).
+    Rows in update_erase_memory's order: the memory's first, the new ones behind.  r + k <= target: the concatenation, nothing launched.
+    `out` [G, target, d]: the pruned memories are written there (it may be `feats_mem` itself: the merged rows are a copy)."""
+    if feats_new.dim() != 3 or (feats_mem is not None and (feats_mem.dim() != 3 or feats_mem.shape[0] != feats_new.shape[0] or feats_mem.shape[2] != feats_new.shape[2])):
+        raise _lib.DvidError(f"update_erase_memory_groups takes feats_new [G, k, d] and feats_mem [G, r, d], got {tuple(feats_new.shape)} and "
+                             f"{None if feats_mem is None else tuple(feats_mem.shape)}")
+    merged = _cuda(feats_new if feats_mem is None else torch.cat([feats_mem, feats_new], dim=1), torch.float32)
+    G, n, d = merged.shape
+    if n <= target_size:
+        return merged, None
+    need = G * n * n * 4
+    scratch = torch.empty((G, n, n) if need <= UPDATE_MEMORY_MAX_SCRATCH_BYTES else (0,), dtype=torch.float32, device=merged.device)
+    idx = torch.empty((G, target_size), dtype=torch.int32, device=merged.device)
+    if out is None:
+        out = torch.empty((G, target_size, d), dtype=torch.float32, device=merged.device)
+    assert out.is_contiguous() and tuple(out.shape) == (G, target_size, d) and out.dtype == torch.float32
+    call("dvid_update_memory_groups", ptr(merged), G, n, d, target_size, ptr(scratch), ptr(idx), ptr(out), stream_ptr())
+    return out, idx
+
+
 def set_option(name, value):
     """one entry of the library's option table (include/dvid_hip.h: dvid_set_option; csrc/options.h lists names and defaults)"""
     call("dvid_set_option", name.encode(), int(value))
@@ -658,6 +716,7 @@ class Model:
         # takes what rcnn_head is given
         self.fpn_levels = 4 if self.has_backbone and "backbone.fpn_lateral2.weight" in state_dict else 3
         self._lkv = {}                   # stage -> (memory tensor, its version, groups) whose K / V projections the library holds
+        self._gkv = None                 # (memory [G, lk, d], its version, its shape): the streams' global memories, projected beside the video's
 
     def take_range_flag(self):
         """DTYPE float32 with split operands: True if a launch since the last call met an activation beyond the fp16 range (65504); synchronises
@@ -781,6 +840,34 @@ class Model:
         self.ensure_memory_projected(memory)
         out = torch.empty_like(query)
         call("dvid_global_xattn", self.handle, ptr(query), query.shape[0], None, memory.shape[0], ptr(out), stream_ptr())
+        return out
+
+    def invalidate_memory_groups(self):
+        """The grouped global memories changed behind the cache's back (a write through a raw pointer: update_erase_memory_groups writing
+        a set's memories in place): the next global_xattn_groups projects K/V again.  The video's projection is not touched."""
+        self._gkv = None
+
+    def ensure_memory_groups_projected(self, memory):
+        """K / V projections of G global memories (memory [G, lk, d], one per live stream) into the engine's buffer for them unless
+        they are current: same tensor object, same version, same shape -- the rule of ensure_local_memory_projected.  That buffer is
+        separate from the one ensure_memory_projected fills, so a video's cached projection survives."""
+        hit = getattr(self, "_gkv", None)
+        if hit is None or hit[0] is not memory or hit[1] != memory._version or hit[2] != tuple(memory.shape):
+            mem = _cuda(memory, torch.float32)
+            self._gkv = None
+            call("dvid_global_memory_project_groups", self.handle, ptr(mem), mem.shape[1], mem.shape[0], stream_ptr())
+            self._gkv = (memory, memory._version, tuple(memory.shape))          # holds the tensor: its storage cannot be recycled under the cache
+
+    def global_xattn_groups(self, query, memory):
+        """cond = MHA(query, memory[g], memory[g]) per group: query [rows, d] is G consecutive blocks of rows / G, memory [G, lk, d]; block
+        g attends memory g, bit-equal to global_xattn(block g, memory[g]).  K/V are projected once per (memory object, version, shape);
+        an in-place write no version counter sees needs invalidate_memory_groups()."""
+        query = _cuda(query, torch.float32)
+        if memory.dim() != 3 or query.shape[0] % memory.shape[0]:
+            raise _lib.DvidError(f"global_xattn_groups: {query.shape[0]} query rows against memories of shape {tuple(memory.shape)} ([G, lk, d])")
+        self.ensure_memory_groups_projected(memory)
+        out = torch.empty_like(query)
+        call("dvid_global_xattn_groups", self.handle, ptr(query), query.shape[0], memory.shape[0], memory.shape[1], ptr(out), stream_ptr())
         return out
 
     def invalidate_local_memory(self):

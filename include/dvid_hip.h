@@ -172,6 +172,15 @@ int dvid_global_xattn(dvid_model* m, const float* query, int rows, const float* 
 /* Project the video's global memory [lk, hidden] to K/V once (box_head.py:366-380 re-projects the same rows on every
  * call); valid until the next call of this function. */
 int dvid_global_memory_project(dvid_model* m, const float* memory, int lk, void* stream);
+/* The global stage for several live streams that share one model (dvid_version >= 4), after dvid_local_memory_project / dvid_local_xattn:
+ * dvid_global_memory_project_groups projects `groups` memories of `lk` rows each, memory fp32 [groups * lk, hidden] (group g = rows
+ * [g lk, (g + 1) lk)), with one K/V linear over all rows, into a buffer of ITS OWN: what dvid_global_memory_project holds for a video is
+ * neither read nor written, so a video's projection survives any number of stream steps.  Valid until the next call of this function.
+ * dvid_global_xattn_groups: out[rows, hidden], rows / groups consecutive query rows per group, group g attending its own lk projected
+ * rows -- per group the value dvid_global_xattn gives on that group's memory alone; groups and lk must be what the last
+ * dvid_global_memory_project_groups projected (DVID_ERR_STATE otherwise).  DTYPE float16 and float32. */
+int dvid_global_memory_project_groups(dvid_model* m, const float* memory, int lk, int groups, void* stream);
+int dvid_global_xattn_groups(dvid_model* m, const float* query, int rows, int groups, int lk, float* out, void* stream);
 
 /* Local box-level attention (MODEL.VID.ROI_BOX_HEAD.ATTENTION.ENABLE; box_head.py:186-194, :338, :360-363).  The model has it when the
  * tensors head.local_attention.{i}.0.in_proj_weight / .0.in_proj_bias / .0.out_proj.weight / .0.out_proj.bias / .2.weight / .2.bias were
@@ -318,6 +327,21 @@ int dvid_cdist(const float* x, int n, int d, float* dist, void* stream);
 /* bs_emul: block size of the reference CUDA launch to emulate for tie-breaking (0 = fps.cu's own rule) */
 int dvid_fps_greedy(const float* dist, int n, int m, int bs_emul, int* idx, void* stream);
 int dvid_gather_rows(const float* x, const int* idx, float* y, int m, int d, void* stream);
+/* The grouped forms (dvid_version >= 4): `groups` independent problems of one shape per launch, problem g computed exactly as the entry
+ * above computes it alone (the same bits and the same picks, ties included).
+ * dvid_cdist_groups: x [groups, n, d] -> dist [groups, n, n].
+ * dvid_fps_greedy_groups: dist [groups, n, n] -> idx [groups, m]; one workgroup per problem with the running distances in registers
+ * for n <= 4096, so the groups' sweeps of m - 1 dependent steps run side by side; beyond, the single-problem sweep once per group.
+ * dvid_gather_rows_groups: y[g, r, :] = x[g, idx[g, r], :], x [groups, n, d], idx [groups, m], y [groups, m, d].
+ * dvid_update_memory_groups: the three in a row -- merged [groups, n, d] -> idx [groups, m] and out [groups, m, d], with
+ * dist_scratch >= groups * n * n floats.  Every argument is checked before the first launch: 1 <= m <= n, d % 4 == 0, groups >= 1, no
+ * null pointer (DVID_ERR_ARG), and groups * n * n * 4 bytes of scratch at most DVID_UPDATE_MEMORY_MAX_SCRATCH_BYTES
+ * (DVID_ERR_UNSUPPORTED, with the numbers in the message: prune fewer memories per call). */
+#define DVID_UPDATE_MEMORY_MAX_SCRATCH_BYTES (1ll << 30)
+int dvid_cdist_groups(const float* x, int groups, int n, int d, float* dist, void* stream);
+int dvid_fps_greedy_groups(const float* dist, int groups, int n, int m, int bs_emul, int* idx, void* stream);
+int dvid_gather_rows_groups(const float* x, const int* idx, float* y, int groups, int n, int m, int d, void* stream);
+int dvid_update_memory_groups(const float* merged, int groups, int n, int d, int m, float* dist_scratch, int* idx, float* out, void* stream);
 /* NHWC fp16 conv / linear (implicit GEMM on MFMA): w is [cout][kpad] fp16 with k = (ky*kw+kx)*cin + c,
  * kpad = round_up(kh*kw*cin, 64).  residual_mode: 0 none, 1 same shape, 2 nearest-x2 upsample.  pad < 0 (stride 1 only): |pad|
  * rows / columns before the image and as many after as keep the output at the input's size (the space-to-depth stem's 4x4 window). */
