@@ -209,6 +209,12 @@ long long dvid_seq_nms_scratch_size(const int* class_counts, const int* video_st
 int dvid_seq_nms_launch(const float* dets, const int* counts, const int* class_counts, const int* video_starts, int n_videos, int cap, int num_classes,
                         unsigned char* keep, float* scores, int* status, void* scratch, hipStream_t s);
 
+// videval.hip: the VID evaluator's greedy matching and CorLoc test, a workgroup per frame; ranges / empty_w are host tables (include/dvid_hip.h)
+int dvid_vid_eval_match_launch(const float* dets, const int* counts, int n_frames, int cap, const float* gt_boxes, const int* gt_labels,
+                               const int* gt_starts, const double* motion, const double* ranges, const double* empty_w, int n_ranges, float iou_thresh,
+                               int num_classes, signed char* match, double* weight, int* rank, double* n_pos, int* top_row, signed char* top_hit,
+                               hipStream_t s);
+
 // fps.hip
 int dvid_cdist_launch(const float* x, int n, int d, float* dist, hipStream_t s);
 int dvid_fps_launch(const float* dist, int n, int m, int bs_emul, int* idx, hipStream_t s);

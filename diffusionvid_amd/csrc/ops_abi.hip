@@ -284,6 +284,35 @@ int dvid_seq_nms_video(const float* dets, const int* counts, const int* class_co
     return DVID_OK;
 }
 
+int dvid_vid_eval_match(const float* dets, const int* counts, int n_frames, int cap, const float* gt_boxes, const int* gt_labels,
+                        const int* gt_starts, const int* gt_starts_host, int label_min, int label_max, const double* motion,
+                        const double* ranges, const double* empty_w, int n_ranges, float iou_thresh, int num_classes, signed char* match,
+                        double* weight, int* rank, double* n_pos, int* top_row, signed char* top_hit, void* stream) {
+    g_err[0] = 0;
+    if (!dets || !counts || !gt_starts || !gt_starts_host || !ranges || !empty_w || !match || !weight || !rank || !n_pos || !top_row || !top_hit)
+        FAIL(DVID_ERR_ARG, "VID evaluation: null pointer");
+    if (n_frames < 0 || cap < 1 || num_classes < 1) FAIL(DVID_ERR_ARG, "VID evaluation: bad sizes (%d frames, %d rows per frame, %d classes)", n_frames, cap, num_classes);
+    if (cap > DVID_NMS_MAX_CANDIDATES)
+        FAIL(DVID_ERR_UNSUPPORTED, "VID evaluation: %d rows per frame exceed the limit of %d (DVID_NMS_MAX_CANDIDATES)", cap, DVID_NMS_MAX_CANDIDATES);
+    if (num_classes > DVID_MAX_CLASSES)
+        FAIL(DVID_ERR_UNSUPPORTED, "VID evaluation: %d classes exceed the limit of %d (DVID_MAX_CLASSES)", num_classes, DVID_MAX_CLASSES);
+    if (n_ranges < 1 || n_ranges > DVID_VID_EVAL_MAX_RANGES)
+        FAIL(DVID_ERR_UNSUPPORTED, "VID evaluation: %d motion ranges, the limit is 1 .. %d (DVID_VID_EVAL_MAX_RANGES)", n_ranges, DVID_VID_EVAL_MAX_RANGES);
+    if (label_min < 0 || label_max > num_classes)
+        FAIL(DVID_ERR_UNSUPPORTED, "VID evaluation: labels %d .. %d leave the range 0 .. %d (num_classes)", label_min, label_max, num_classes);
+    if (gt_starts_host[0] != 0) FAIL(DVID_ERR_ARG, "VID evaluation: gt_starts[0] is %d, not 0", gt_starts_host[0]);
+    for (int f = 0; f < n_frames; ++f) {
+        const int g = gt_starts_host[f + 1] - gt_starts_host[f];
+        if (g < 0) FAIL(DVID_ERR_ARG, "VID evaluation: gt_starts decreases at frame %d", f);
+        if (g > DVID_VID_EVAL_MAX_GT)
+            FAIL(DVID_ERR_UNSUPPORTED, "VID evaluation: frame %d holds %d ground-truth boxes, the limit is %d (DVID_VID_EVAL_MAX_GT)", f, g, DVID_VID_EVAL_MAX_GT);
+    }
+    if (gt_starts_host[n_frames] > 0 && (!gt_boxes || !gt_labels)) FAIL(DVID_ERR_ARG, "VID evaluation: null ground truth");
+    TRY(dvid_vid_eval_match_launch(dets, counts, n_frames, cap, gt_boxes, gt_labels, gt_starts, motion, ranges, empty_w, n_ranges, iou_thresh, num_classes,
+                                   match, weight, rank, n_pos, top_row, top_hit, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
 int dvid_cdist(const float* x, int n, int d, float* dist, void* stream) {
     g_err[0] = 0;
     TRY(dvid_cdist_launch(x, n, d, dist, reinterpret_cast<hipStream_t>(stream)));

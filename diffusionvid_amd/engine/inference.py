@@ -349,7 +349,7 @@ def predictions_list(merged):
 
 
 def inference(model, dataset, indices, device, output_folder=None, gt_boxlists=None, max_det=None, motion_specific=False,
-              motion_ious=None, logger=None, class_module=None, seq_nms=None):
+              motion_ious=None, logger=None, class_module=None, seq_nms=None, eval_device=None):
     """Reference `inference` (mega_core/engine/inference.py:118-181) for the in-scope path: run this rank's share, gather on
     rank 0, write `predictions.pth` -- `predictions_seq_nms.pth` instead when the model's config has TEST.SEQ_NMS (:165-168; the
     step itself runs in compute_on_dataset, `seq_nms` as there) -- (`class_module`: see vid_eval.save_predictions) and evaluate as the reference's
@@ -357,7 +357,8 @@ def inference(model, dataset, indices, device, output_folder=None, gt_boxlists=N
     the predictions are mapped from the resized frame to the annotation's original size first and `result.txt` is written;
     `gt_boxlists` (a list of BoxList, one per image id) stands in for a dataset without annotations -- each prediction is
     resized to its ground truth's size the same way.  Returns (predictions list | None off rank 0, eval | None):
-    eval = the AP dict, or the list of one dict per motion range with `motion_specific`."""
+    eval = the AP dict, or the list of one dict per motion range with `motion_specific`.  eval_device: a torch.device runs the
+    evaluator's matching there (vid_eval.do_vid_evaluation's `device`); None keeps it in numpy."""
     import os
 
     from ..data.evaluation import vid_eval
@@ -379,7 +380,7 @@ def inference(model, dataset, indices, device, output_folder=None, gt_boxlists=N
     if source is None:
         return preds, None
     ev = vid_eval.do_vid_evaluation(source, preds, output_folder, motion_specific=motion_specific, logger=logger,
-                                    motion_ious=motion_ious)
+                                    motion_ious=motion_ious, device=eval_device)
     return preds, (ev if motion_specific else ev[0])
 
 

@@ -535,6 +535,64 @@ def seq_nms_video(dets, counts, num_classes, video_starts=None, return_status=Fa
     return (keep, scores, st) if return_status else (keep, scores)
 
 
+VID_EVAL_MAX_GT, VID_EVAL_MAX_RANGES = 256, 4          # include/dvid_hip.h
+
+
+def vid_eval_label_range(dets, counts, gt_labels=None):
+    """(least, greatest) label among the rows of dets [frames, cap, 6] in front of counts[f] and gt_labels; (0, 0) when there is none.
+    What dvid_vid_eval_match checks against num_classes before it launches."""
+    cap = dets.shape[1]
+    lab = dets[:, :, 5][torch.arange(cap, device=dets.device)[None, :] < counts[:, None]].to(torch.int64)
+    if gt_labels is not None:
+        lab = torch.cat((lab, gt_labels.reshape(-1).to(torch.int64)))
+    if lab.numel() == 0:
+        return 0, 0
+    lo, hi = torch.stack((lab.amin(), lab.amax())).tolist()
+    return int(lo), int(hi)
+
+
+def vid_eval_match(dets, counts, gt_boxes, gt_labels, gt_starts, num_classes, motion=None, ranges=((0.0, 1.0),), empty_w=None, iou_thresh=0.5,
+                   label_range=None, out=None):
+    """The VID evaluator's greedy matching (vid_eval.calc_prec_rec's loop) and CorLoc test for all motion ranges in one launch
+    (csrc/videval.hip).  dets [F, cap, 6] fp32 and counts [F] int32 in engine.pack_predictions' layout with the boxes in annotation
+    pixels; gt_boxes [G, 4] fp32, gt_labels [G] int32, gt_starts [F + 1] int32: the ragged ground truth (vid_eval.pack_groundtruth);
+    motion [G] float64 or None; ranges: R pairs (lo, hi); empty_w: R floats (default 0).  All tensors on the device.  Returns
+    (match [R, F, cap] int8, weight [R, F, cap] float64, rank [F, cap] int32, n_pos [R, num_classes + 1] float64, top_row [F] int32,
+    top_hit [F] int8) on the device (include/dvid_hip.h says what each holds); `out`: such a tuple to write into.  label_range: what
+    vid_eval_label_range returns, when the caller has it already."""
+    dets, counts = _cuda(dets, torch.float32), _cuda(counts, torch.int32)
+    F, cap = counts.shape[0], dets.shape[1] if dets.dim() == 3 else -1
+    assert dets.shape == (F, cap, 6), "dets is [frames, cap, 6]"
+    dev = dets.device
+    rng = torch.tensor([[float(lo), float(hi)] for lo, hi in ranges], dtype=torch.float64).reshape(-1, 2)
+    R = rng.shape[0]
+    ew = torch.zeros((R,), dtype=torch.float64) if empty_w is None else torch.tensor([float(w) for w in empty_w], dtype=torch.float64)
+    assert ew.numel() == R and num_classes >= 1, "one empty_w per range"
+    if out is None:
+        out = (torch.empty((R, F, cap), dtype=torch.int8, device=dev), torch.empty((R, F, cap), dtype=torch.float64, device=dev),
+               torch.empty((F, cap), dtype=torch.int32, device=dev), torch.zeros((R, num_classes + 1), dtype=torch.float64, device=dev),
+               torch.empty((F,), dtype=torch.int32, device=dev), torch.empty((F,), dtype=torch.int8, device=dev))
+    match, weight, rank, n_pos, top_row, top_hit = out
+    assert match.shape == weight.shape == (R, F, cap) and rank.shape == (F, cap) and n_pos.shape == (R, num_classes + 1) and \
+        top_row.shape == top_hit.shape == (F,), "output shapes"
+    assert (match.dtype, weight.dtype, rank.dtype, n_pos.dtype, top_row.dtype, top_hit.dtype) == \
+        (torch.int8, torch.float64, torch.int32, torch.float64, torch.int32, torch.int8), "output dtypes"
+    if F == 0 or cap == 0:
+        n_pos.zero_()
+        return out
+    gt_boxes, gt_labels, gt_starts = _cuda(gt_boxes, torch.float32).reshape(-1, 4), _cuda(gt_labels, torch.int32), _cuda(gt_starts, torch.int32)
+    assert gt_starts.shape == (F + 1,) and gt_labels.shape[0] == gt_boxes.shape[0], "gt_starts is [frames + 1]"
+    starts_host = gt_starts.cpu()
+    assert int(starts_host[-1]) == gt_boxes.shape[0], "gt_starts ends at the box count"
+    if motion is not None:
+        motion = _cuda(motion, torch.float64)
+        assert motion.shape == (gt_boxes.shape[0],), "one motion IoU per ground-truth box"
+    lo, hi = label_range if label_range is not None else vid_eval_label_range(dets, counts, gt_labels)
+    call("dvid_vid_eval_match", ptr(dets), ptr(counts), F, cap, ptr(gt_boxes), ptr(gt_labels), ptr(gt_starts), ptr(starts_host), int(lo), int(hi),
+         ptr(motion), ptr(rng), ptr(ew), R, float(iou_thresh), int(num_classes), *(ptr(_cuda(o)) for o in out), stream_ptr())
+    return out
+
+
 def split_detection_buffer(buf, n, cap):
     """The four post-processing outputs are views of ONE flat fp32 buffer [boxes | scores | labels(int32) |
     counts(int32)], so a caller can bring a whole batch to the host with a single D2H copy

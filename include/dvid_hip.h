@@ -323,6 +323,32 @@ int dvid_seq_nms_video(const float* dets, const int* counts, const int* class_co
  * link words and M = sum ceil(n_f / 64): round16(12 (F + 1)) + round16(8 (L + M) + 36 N + 12 F) bytes, behind round16(40 n_videos
  * num_classes) bytes of headers. */
 int64_t dvid_seq_nms_scratch_bytes(const int* class_counts, const int* video_starts, int n_videos, int num_classes);
+/* The greedy matching of the VID AP50 evaluator on the device (dvid_version >= 5; csrc/videval.hip; data/evaluation/vid_eval.py:
+ * calc_prec_rec's loop and corloc_eval_detection_vid's test), one workgroup per frame, all motion ranges in one launch.  No model handle,
+ * independent of DTYPE.
+ * in   dets [n_frames, cap, 6] fp32 (xyxy box in annotation pixels, score, label as a float), counts [n_frames] int32 (device), the
+ *      layout of engine.pack_predictions; the ragged ground truth gt_boxes [G, 4] fp32, gt_labels [G] int32, gt_starts [n_frames + 1]
+ *      int32 (device; frame f owns boxes [gt_starts[f], gt_starts[f + 1])), motion [G] float64 (device; NULL: nothing is ignored) and,
+ *      on the HOST, gt_starts_host (the same table), ranges [n_ranges, 2] and empty_w [n_ranges] float64 (a box is ignored in range r
+ *      when its motion IoU is < ranges[r][0] or > ranges[r][1]; empty_w[r] is the weight of a row in a frame without a box of its
+ *      label), and label_min / label_max: the least and the greatest label among the rows in front of counts[f] and gt_labels, which
+ *      the caller reads (ops.vid_eval_match does).
+ * out  match [n_ranges, n_frames, cap] int8 and weight [n_ranges, n_frames, cap] float64 as calc_prec_rec appends them, at the row's own
+ *      place; rank [n_frames, cap] int32: the row's position in its (frame, label) list in descending score, equal scores lower row
+ *      first (-1, match 0 and weight 0 behind counts[f]); n_pos [n_ranges, num_classes + 1] float64: the counted boxes per label;
+ *      top_row [n_frames] int32: the frame's highest-scoring row (the lowest of equal ones; -1 without rows) and top_hit [n_frames]
+ *      int8: 1 when it overlaps a box of its own label by MORE than iou_thresh.
+ * A row takes the best box of its label that no earlier row took and whose IoU is >= iou_thresh; on an exact tie the earlier box stays
+ * unless it is ignored.  The IoU is _iou_vid's, bit for bit: float32, + 1 on x2, y2 and + 1 again in the extents, one IEEE division.
+ * Before anything is launched: cap <= DVID_NMS_MAX_CANDIDATES, num_classes <= DVID_MAX_CLASSES, 1 <= n_ranges <=
+ * DVID_VID_EVAL_MAX_RANGES, 0 <= label_min and label_max <= num_classes, at most DVID_VID_EVAL_MAX_GT boxes per frame
+ * (DVID_ERR_UNSUPPORTED beyond, with the limit and the value in the message; nothing is written). */
+#define DVID_VID_EVAL_MAX_GT 256
+#define DVID_VID_EVAL_MAX_RANGES 4
+int dvid_vid_eval_match(const float* dets, const int* counts, int n_frames, int cap, const float* gt_boxes, const int* gt_labels,
+                        const int* gt_starts, const int* gt_starts_host, int label_min, int label_max, const double* motion,
+                        const double* ranges, const double* empty_w, int n_ranges, float iou_thresh, int num_classes, signed char* match,
+                        double* weight, int* rank, double* n_pos, int* top_row, signed char* top_hit, void* stream);
 int dvid_cdist(const float* x, int n, int d, float* dist, void* stream);
 /* bs_emul: block size of the reference CUDA launch to emulate for tie-breaking (0 = fps.cu's own rule) */
 int dvid_fps_greedy(const float* dist, int n, int m, int bs_emul, int* idx, void* stream);
