@@ -270,6 +270,53 @@ const std::vector<float>& time_embedding(dvid_model* m, int64_t t) {
     }
     return m->time_cache.emplace(t, std::move(out)).first->second;
 }
+
+// ---- attention against a projected memory (KvMemory, runtime.h): the video's global memory, the streams' grouped global memories and the
+// local memories are instances of these two steps; they differ in the weights, the KvMemory and the output stage of the entry point ----
+// K | V rows of `groups` memories of `lk` rows each into `mem`: one linear over all groups * lk rows.  `pad_rows`: rows the buffer is
+// asked for beyond those (see KvMemory).  The shape is cleared first and set last: a failed call leaves nothing projected.
+int kv_project(dvid_model* m, const ConvW& wkv, KvMemory& mem, const float* memory, int lk, int groups, int pad_rows, hipStream_t s) {
+    const int d = m->cfg.hidden_dim, n = lk * groups;
+    mem.lk = mem.groups = 0;
+    TRY(mem.kv.ensure(((size_t)n + pad_rows) * 2 * d * 4, &m->ws_gen));
+    if (m->precision == 1) {          // fp32 K | V rows
+        TRY(linear_run32(wkv, memory, n, mem.kv.as<float>(), 0, s));
+    } else {
+        TRY(mem.src16.ensure((size_t)n * d * 2, &m->ws_gen));
+        TRY(dvid_f32_to_f16_launch(memory, mem.src16.as<half_t>(), (long)n * d, s));
+        TRY(linear_run(wkv, mem.src16.as<half_t>(), n, mem.kv.p, 0, 0, s));
+    }
+    mem.lk = lk;
+    mem.groups = groups;
+    return DVID_OK;
+}
+
+// attn16 = MHA(q_proj(query), K_g, V_g): rows / groups consecutive query rows per group against that group's projected rows of `mem`, Q
+// projection over all rows at once; fp16 or fp32 rows as the model's precision says.  One group: batch index 0, the strides address nothing.
+int kv_attend(dvid_model* m, const ConvW& wq, const KvMemory& mem, const float* query, int rows, hipStream_t s) {
+    const int d = m->cfg.hidden_dim, nh = m->cfg.nheads, groups = mem.groups, lk = mem.lk, lq = rows / groups;
+    const long q_bs = (long)lq * d, kv_bs = (long)lk * 2 * d;
+    if (m->precision == 1) {
+        float* qp = m->h16a.as<float>();
+        const float* kv32 = mem.kv.as<float>();
+        TRY(linear_run32(wq, query, rows, qp, 0, s));
+        TRY(dvid_f32_mha_launch(qp, kv32, kv32 + d, m->attn16.as<float>(), groups, lq, lk, nh, d, 2 * d, d, q_bs, kv_bs, q_bs, s));
+        return DVID_OK;
+    }
+    TRY(dvid_f32_to_f16_launch(query, m->h16a.as<half_t>(), (long)rows * d, s));
+    TRY(linear_run(wq, m->h16a.as<half_t>(), rows, m->h16b.p, 0, 0, s));
+    const half_t* kv = mem.kv.as<half_t>();
+    TRY(m->vt.ensure((size_t)groups * nh * 32 * (((size_t)lk + 31) / 32 * 32 + 32) * 2, &m->ws_gen));          // per group
+    TRY(dvid_mha_mfma_launch(m->h16b.as<half_t>(), kv, kv + d, m->attn16.as<half_t>(), m->vt.as<half_t>(), groups, lq, lk, nh, d, 2 * d, d, q_bs, kv_bs,
+                             q_bs, s));
+    return DVID_OK;
+}
+
+// out = out_proj(attn16), the output stage of both global forms
+int global_out_proj(dvid_model* m, int rows, float* out, hipStream_t s) {
+    if (m->precision == 1) return linear_run32(m->gout, m->attn16.as<float>(), rows, out, 0, s);
+    return linear_run(m->gout, m->attn16.as<half_t>(), rows, out, 0, 1, s);
+}
 }  // namespace
 
 extern "C" {
@@ -369,20 +416,7 @@ int dvid_global_memory_project(dvid_model* m, const float* memory, int lk, void*
     g_err[0] = 0;
     if (!m || !m->finalized || !m->gq.w) FAIL(DVID_ERR_STATE, "model not finalized or has no global attention");
     if (!memory || lk <= 0) FAIL(DVID_ERR_ARG, "empty memory");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int d = m->cfg.hidden_dim;
-    m->mem_lk = 0;
-    TRY(m->kvproj.ensure((size_t)lk * 2 * d * 4, &m->ws_gen));
-    if (m->precision == 1) {          // fp32 K | V rows
-        TRY(linear_run32(m->gkv, memory, lk, m->kvproj.as<float>(), 0, s));
-        m->mem_lk = lk;
-        return DVID_OK;
-    }
-    TRY(m->mem16.ensure((size_t)lk * d * 2, &m->ws_gen));
-    TRY(dvid_f32_to_f16_launch(memory, m->mem16.as<half_t>(), (long)lk * d, s));
-    TRY(linear_run(m->gkv, m->mem16.as<half_t>(), lk, m->kvproj.p, 0, 0, s));
-    m->mem_lk = lk;
-    return DVID_OK;
+    return kv_project(m, m->gkv, m->vmem, memory, lk, 1, 0, reinterpret_cast<hipStream_t>(stream));
 }
 
 int dvid_global_xattn(dvid_model* m, const float* query, int rows, const float* memory, int lk, float* out, void* stream) {
@@ -390,123 +424,62 @@ int dvid_global_xattn(dvid_model* m, const float* query, int rows, const float* 
     if (!m || !m->finalized || !m->gq.w) FAIL(DVID_ERR_STATE, "model not finalized or has no global attention");
     if (rows > m->ws_frames * m->ws_boxes) FAIL(DVID_ERR_STATE, "workspace too small");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int d = m->cfg.hidden_dim;
     if (memory) {
         TRY(dvid_global_memory_project(m, memory, lk, stream));
-    } else if (m->mem_lk <= 0 || (lk > 0 && lk != m->mem_lk)) {
+    } else if (m->vmem.lk <= 0 || (lk > 0 && lk != m->vmem.lk)) {
         FAIL(DVID_ERR_STATE, "no projected global memory of %d rows (call dvid_global_memory_project)", lk);
     }
-    lk = m->mem_lk;
-    if (m->precision == 1) {
-        float* qp = m->h16a.as<float>();
-        float* at = m->attn16.as<float>();
-        const float* kv32 = m->kvproj.as<float>();
-        TRY(linear_run32(m->gq, query, rows, qp, 0, s));
-        TRY(dvid_f32_mha_launch(qp, kv32, kv32 + d, at, 1, rows, lk, m->cfg.nheads, d, 2 * d, d, 0, 0, 0, s));
-        TRY(linear_run32(m->gout, at, rows, out, 0, s));
-        return DVID_OK;
-    }
-    TRY(dvid_f32_to_f16_launch(query, m->h16a.as<half_t>(), (long)rows * d, s));
-    TRY(linear_run(m->gq, m->h16a.as<half_t>(), rows, m->h16b.p, 0, 0, s));
-    const half_t* kv = m->kvproj.as<half_t>();
-    TRY(m->vt.ensure((size_t)m->cfg.nheads * 32 * (((size_t)lk + 31) / 32 * 32 + 32) * 2, &m->ws_gen));
-    TRY(dvid_mha_mfma_launch(m->h16b.as<half_t>(), kv, kv + d, m->attn16.as<half_t>(), m->vt.as<half_t>(), 1, rows, lk, m->cfg.nheads,
-                             d, 2 * d, d, 0, 0, 0, s));
-    TRY(linear_run(m->gout, m->attn16.as<half_t>(), rows, out, 0, 1, s));
+    TRY(kv_attend(m, m->gq, m->vmem, query, rows, s));
+    TRY(global_out_proj(m, rows, out, s));
     return DVID_OK;
 }
 
-// `groups` global memories of `lk` rows each -- one per live stream -- projected as dvid_local_memory_project projects the local ones: one
-// K/V linear over all groups * lk rows, into a buffer of its OWN (gkvproj).  kvproj / mem_lk, the projection a video holds between its
-// calls, is neither read nor written.
+// `groups` global memories of `lk` rows each -- one per live stream -- into a KvMemory of their OWN (gmem).  vmem, the projection a video
+// holds between its calls, is neither read nor written.
 int dvid_global_memory_project_groups(dvid_model* m, const float* memory, int lk, int groups, void* stream) {
     g_err[0] = 0;
     if (!m || !m->finalized || !m->gq.w) FAIL(DVID_ERR_STATE, "model not finalized or has no global attention");
     if (!memory || lk <= 0 || groups <= 0) FAIL(DVID_ERR_ARG, "empty global memory (%d groups of %d rows)", groups, lk);
     if ((long)lk * groups > (1L << 24)) FAIL(DVID_ERR_ARG, "global memory of %d x %d rows", groups, lk);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int d = m->cfg.hidden_dim, n = lk * groups;
-    m->gmem_lk = m->gmem_groups = 0;
-    TRY(m->gkvproj.ensure(((size_t)n + 64) * 2 * d * 4, &m->ws_gen));
-    if (m->precision == 1) {
-        TRY(linear_run32(m->gkv, memory, n, m->gkvproj.as<float>(), 0, s));
-    } else {
-        TRY(m->gmem16.ensure((size_t)n * d * 2, &m->ws_gen));
-        TRY(dvid_f32_to_f16_launch(memory, m->gmem16.as<half_t>(), (long)n * d, s));
-        TRY(linear_run(m->gkv, m->gmem16.as<half_t>(), n, m->gkvproj.p, 0, 0, s));
-    }
-    m->gmem_lk = lk;
-    m->gmem_groups = groups;
-    return DVID_OK;
+    return kv_project(m, m->gkv, m->gmem, memory, lk, groups, 64, reinterpret_cast<hipStream_t>(stream));
 }
 
-// out = out_proj(MHA(q_proj(query), K_g, V_g)): rows / groups consecutive query rows per group against that group's projected memory; the
-// kernels of dvid_global_xattn with batch = groups and the batch strides, Q and out projections over all rows at once.
+// out = out_proj(MHA(q_proj(query), K_g, V_g)): rows / groups consecutive query rows per group against that group's projected memory
 int dvid_global_xattn_groups(dvid_model* m, const float* query, int rows, int groups, int lk, float* out, void* stream) {
     g_err[0] = 0;
     if (!m || !m->finalized || !m->gq.w) FAIL(DVID_ERR_STATE, "model not finalized or has no global attention");
     if (!query || !out || rows <= 0 || groups <= 0 || rows % groups) FAIL(DVID_ERR_ARG, "%d query rows in %d groups", rows, groups);
-    if (m->gmem_lk <= 0 || lk != m->gmem_lk || groups != m->gmem_groups)
+    if (m->gmem.lk <= 0 || lk != m->gmem.lk || groups != m->gmem.groups)
         FAIL(DVID_ERR_STATE, "no projected global memories of %d x %d rows (call dvid_global_memory_project_groups)", groups, lk);
     if (rows > m->ws_frames * m->ws_boxes) FAIL(DVID_ERR_STATE, "workspace too small");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int d = m->cfg.hidden_dim, lq = rows / groups;
-    if (m->precision == 1) {
-        float* qp = m->h16a.as<float>();
-        float* at = m->attn16.as<float>();
-        const float* kv32 = m->gkvproj.as<float>();
-        TRY(linear_run32(m->gq, query, rows, qp, 0, s));
-        TRY(dvid_f32_mha_launch(qp, kv32, kv32 + d, at, groups, lq, lk, m->cfg.nheads, d, 2 * d, d, (long)lq * d, (long)lk * 2 * d, (long)lq * d, s));
-        TRY(linear_run32(m->gout, at, rows, out, 0, s));
-        return DVID_OK;
-    }
-    TRY(dvid_f32_to_f16_launch(query, m->h16a.as<half_t>(), (long)rows * d, s));
-    TRY(linear_run(m->gq, m->h16a.as<half_t>(), rows, m->h16b.p, 0, 0, s));
-    const half_t* kv = m->gkvproj.as<half_t>();
-    TRY(m->vt.ensure((size_t)groups * m->cfg.nheads * 32 * (((size_t)lk + 31) / 32 * 32 + 32) * 2, &m->ws_gen));          // per group
-    TRY(dvid_mha_mfma_launch(m->h16b.as<half_t>(), kv, kv + d, m->attn16.as<half_t>(), m->vt.as<half_t>(), groups, lq, lk, m->cfg.nheads, d, 2 * d, d,
-                             (long)lq * d, (long)lk * 2 * d, (long)lq * d, s));
-    TRY(linear_run(m->gout, m->attn16.as<half_t>(), rows, out, 0, 1, s));
+    TRY(kv_attend(m, m->gq, m->gmem, query, rows, s));
+    TRY(global_out_proj(m, rows, out, s));
     return DVID_OK;
 }
 
-// K/V projections of `groups` local memories of `lk` rows each (box_head.py:338, :362: key = value = proposal_feats_local[stage]) into
-// the model's own buffer: one linear over all groups * lk rows.
+// K/V projections of `groups` local memories of `lk` rows each (box_head.py:338, :362: key = value = proposal_feats_local[stage])
 int dvid_local_memory_project(dvid_model* m, int stage, const float* memory, int lk, int groups, void* stream) {
     g_err[0] = 0;
     if (!m || !m->finalized || m->local_stages == 0) FAIL(DVID_ERR_STATE, "model not finalized or has no local attention");
     if (stage != m->local_stages - 1) FAIL(DVID_ERR_ARG, "local attention stage %d: only the last stage (%d) is computed", stage, m->local_stages - 1);
     if (!memory || lk <= 0 || groups <= 0) FAIL(DVID_ERR_ARG, "empty local memory");
     if ((long)lk * groups > (1L << 24)) FAIL(DVID_ERR_ARG, "local memory of %d x %d rows", groups, lk);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int d = m->cfg.hidden_dim, n = lk * groups;
-    m->local_lk = m->local_groups = 0;
-    TRY(m->lkvproj.ensure(((size_t)n + 64) * 2 * d * 4, &m->ws_gen));
-    if (m->precision == 1) {
-        TRY(linear_run32(m->lkv, memory, n, m->lkvproj.as<float>(), 0, s));
-    } else {
-        TRY(m->lmem16.ensure((size_t)n * d * 2, &m->ws_gen));
-        TRY(dvid_f32_to_f16_launch(memory, m->lmem16.as<half_t>(), (long)n * d, s));
-        TRY(linear_run(m->lkv, m->lmem16.as<half_t>(), n, m->lkvproj.p, 0, 0, s));
-    }
-    m->local_lk = lk;
-    m->local_groups = groups;
-    return DVID_OK;
+    return kv_project(m, m->lkv, m->lmem, memory, lk, groups, 64, reinterpret_cast<hipStream_t>(stream));
 }
 
 // out = LayerNorm(out_proj(MHA(q_proj(query), K, V))), group g's rows / groups queries against group g's lk projected memory rows
-// (box_head.py:360-363).  Q projection and the attention product are the global stage's kernels with batch strides; the out-projection,
-// its bias and the LayerNorm are one launch (csrc/localattn.hip).
+// (box_head.py:360-363); the out-projection, its bias and the LayerNorm are one launch (csrc/localattn.hip).
 int dvid_local_xattn(dvid_model* m, int stage, const float* query, int rows, int groups, int lk, float* out, void* stream) {
     g_err[0] = 0;
     if (!m || !m->finalized || m->local_stages == 0) FAIL(DVID_ERR_STATE, "model not finalized or has no local attention");
     if (stage != m->local_stages - 1) FAIL(DVID_ERR_ARG, "local attention stage %d: only the last stage (%d) is computed", stage, m->local_stages - 1);
     if (!query || !out || rows <= 0 || groups <= 0 || rows % groups) FAIL(DVID_ERR_ARG, "%d query rows in %d groups", rows, groups);
-    if (m->local_lk <= 0 || lk != m->local_lk || groups != m->local_groups)
+    if (m->lmem.lk <= 0 || lk != m->lmem.lk || groups != m->lmem.groups)
         FAIL(DVID_ERR_STATE, "no projected local memory of %d x %d rows (call dvid_local_memory_project)", groups, lk);
     if (rows > m->ws_frames * m->ws_boxes) FAIL(DVID_ERR_STATE, "workspace too small");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int d = m->cfg.hidden_dim, lq = rows / groups;
+    TRY(kv_attend(m, m->lq, m->lmem, query, rows, s));
     OutProjLnParams p;
     memset(&p, 0, sizeof(p));
     p.bias = m->lout.bias;
@@ -514,33 +487,20 @@ int dvid_local_xattn(dvid_model* m, int stage, const float* query, int rows, int
     p.beta = m->lln.b;
     p.out = out;
     p.rows = rows;
-    p.d = d;
+    p.d = m->cfg.hidden_dim;
+    p.x = m->attn16.p;
     if (m->precision == 1) {
-        float* qp = m->h16a.as<float>();
-        float* at = m->attn16.as<float>();
-        const float* kv32 = m->lkvproj.as<float>();
-        TRY(linear_run32(m->lq, query, rows, qp, 0, s));
-        TRY(dvid_f32_mha_launch(qp, kv32, kv32 + d, at, groups, lq, lk, m->cfg.nheads, d, 2 * d, d, (long)lq * d, (long)lk * 2 * d, (long)lq * d, s));
         const bool split = g_opt.f32_split != 0 && m->lout_fhi && m->lout_flo;
-        p.x = at;
         p.mode = split ? 1 : 2;
         p.wf_hi = m->lout_fhi;
         p.wf_lo = m->lout_flo;
         p.w32 = m->lout.w32;
         p.wscale = m->lout.wscale32;
         p.range_flag = m->lout.range_flag;
-        TRY(dvid_outproj_ln_launch(p, s));
-        return DVID_OK;
+    } else {
+        p.mode = 0;
+        p.wf_hi = m->lout_f;
     }
-    TRY(dvid_f32_to_f16_launch(query, m->h16a.as<half_t>(), (long)rows * d, s));
-    TRY(linear_run(m->lq, m->h16a.as<half_t>(), rows, m->h16b.p, 0, 0, s));
-    const half_t* kv = m->lkvproj.as<half_t>();
-    TRY(m->vt.ensure((size_t)groups * m->cfg.nheads * 32 * (((size_t)lk + 31) / 32 * 32 + 32) * 2, &m->ws_gen));
-    TRY(dvid_mha_mfma_launch(m->h16b.as<half_t>(), kv, kv + d, m->attn16.as<half_t>(), m->vt.as<half_t>(), groups, lq, lk, m->cfg.nheads, d, 2 * d, d,
-                             (long)lq * d, (long)lk * 2 * d, (long)lq * d, s));
-    p.x = m->attn16.p;
-    p.mode = 0;
-    p.wf_hi = m->lout_f;
     TRY(dvid_outproj_ln_launch(p, s));
     return DVID_OK;
 }

@@ -132,12 +132,7 @@ int dvid_model_create(const dvid_config* cfg, dvid_model** out) {
 int dvid_model_destroy(dvid_model* m) {
     if (!m) return DVID_OK;
     for (void* p : m->owned) (void)hipFree(p);
-    DevBuf* bufs[] = {&m->img8, &m->bufX, &m->bufY, &m->bufT1, &m->bufT2, &m->bufSC, &m->c2, &m->c3, &m->c4, &m->c5, &m->lat[0], &m->sw_x, &m->sw_x2, &m->sw_ln16, &m->sw_qkv16, &m->sw_attn16, &m->sw_h16,
-                      &m->lat[1], &m->lat[2], &m->lat[3], &m->roi, &m->params, &m->dyn, &m->qkv, &m->attn16, &m->f32a, &m->f32b, &m->f32c,
-                      &m->f32d, &m->h16a, &m->h16b, &m->hid16, &m->ss, &m->deltas, &m->kvproj, &m->mem16, &m->splitk, &m->vt, &m->lkvproj, &m->lmem16, &m->gkvproj, &m->gmem16};
-    for (DevBuf* b : bufs) b->release();
-    for (DevBuf& b : m->ss_slabs) b.release();
-    delete m;
+    delete m;          // every workspace buffer is a DevBuf member and frees itself here
     return DVID_OK;
 }
 

@@ -96,6 +96,14 @@ struct HostTensor {
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;          // one owner per allocation: a buffer frees itself where its owner dies (dvid_model_destroy)
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) {          // std::vector<DevBuf> growing (ss_slabs)
+        o.p = nullptr;
+        o.bytes = 0;
+    }
+    ~DevBuf() { release(); }
     int ensure(size_t n, std::atomic<unsigned long long>* gen = nullptr) {
         if (n <= bytes) return DVID_OK;
         if (gen && p) gen->fetch_add(1, std::memory_order_relaxed);
@@ -117,6 +125,17 @@ struct DevBuf {
     }
     template <typename T>
     T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// A memory the head attends to, as the library keeps it between calls: the K | V rows of `groups` memories of `lk` rows each, projected by
+// one linear over all groups * lk rows (head.hip: kv_project), and the shape they were projected for.  The callers ask for `kv` with 64
+// rows more than they project in the grouped forms and with none in the single one; why is unexplained: mha_mfma_kernel clamps its K
+// rows to lk - 1 and reads V through the padded transpose in `vt`, f32_mha_kernel stages only the rows below lk (attention.hip), so
+// neither reads a row behind the last group's.
+struct KvMemory {
+    DevBuf kv;           // K | V rows, [groups * lk, 2 d], fp16 or fp32 as the model's precision says
+    DevBuf src16;        // fp16 copy of the source rows (precision 0 only)
+    int lk = 0, groups = 0;          // shape of what `kv` holds (0: nothing projected)
 };
 
 struct ConvW {   // conv or linear weights in MFMA-operand layout
@@ -211,18 +230,16 @@ struct dvid_model {
     int ws_frames = 0, ws_h = 0, ws_w = 0, ws_boxes = 0;
     DevBuf img8, bufX, bufY, bufT1, bufT2, bufSC, c2, c3, c4, c5, lat[4];          // c2, lat[0]: models with the p2 level only
     DevBuf sw_x, sw_x2, sw_ln16, sw_qkv16, sw_attn16, sw_h16;   // Swin token buffers
-    DevBuf roi, params, dyn, qkv, attn16, f32a, f32b, f32c, f32d, h16a, h16b, hid16, ss, deltas, kvproj, mem16, splitk, vt;
+    DevBuf roi, params, dyn, qkv, attn16, f32a, f32b, f32c, f32d, h16a, h16b, hid16, ss, deltas, splitk, vt;
     // (head slot, t) -> device scale/shift row [bt_out], sub-allocated from slabs of kSsSlabRows rows (a sampler that walks all
     // 1000 time steps on 4 head slots ends at 16 allocations of 512 KB, not 4000 of 2 KB; rows live until the model is destroyed)
     std::map<std::pair<int, int64_t>, float*> ss_rows;
     std::vector<DevBuf> ss_slabs;
     size_t ss_slab_used = 0;          // rows taken from the last slab
 
-    int mem_lk = 0;       // rows of the global memory whose K/V projections sit in kvproj (0: none)
-    DevBuf lkvproj, lmem16;          // K | V rows of the projected local memories, [groups * lk, 2 d]
-    int local_lk = 0, local_groups = 0;          // shape of what lkvproj holds (0: nothing projected)
-    DevBuf gkvproj, gmem16;          // K | V rows of `groups` projected GLOBAL memories (one per live stream), [groups * lk, 2 d]: beside kvproj, never in it
-    int gmem_lk = 0, gmem_groups = 0;          // shape of what gkvproj holds (0: nothing projected)
+    KvMemory vmem;          // the global memory a video holds between its calls
+    KvMemory gmem;          // `groups` GLOBAL memories, one per live stream: beside vmem, never in it
+    KvMemory lmem;          // the local memories of the one observable local stage
 
     // sub-batch chains (backbone.hip: run_chains)
     int nchain = 2;

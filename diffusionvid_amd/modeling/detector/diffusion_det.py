@@ -14,6 +14,7 @@ box-level memory (the top-75 / top-25 object features of the frames in the local
 `ops` on the current stream.  Random draws go through `self.noise_fn(kind, frame_id, step, image,
 shape)` when set (parity/bench), else torch.randn on the device like the reference.
 """
+import functools
 import math
 import os
 import time
@@ -66,6 +67,29 @@ def _register_nested(root, name, tensor, buffer=False):
 
 
 _FOREIGN_BOXLIST = {}
+
+
+def take(per_frame, a, b, keys=("logits", "boxes", "obj", "k1", "k2"), with_feats=True):
+    """Frame slots [a, b) of an extraction pass as one split; per_frame[j] = (launch result dict, index inside the launch) of slot j.
+    Views when the slots sit in one launch sequence, else a concatenation."""
+    runs = []
+    for j in range(a, b):
+        src, i = per_frame[j]
+        if runs and runs[-1][0] is src:
+            runs[-1][2] = i + 1
+        else:
+            runs.append([src, i, i + 1])
+    if len(runs) == 1:
+        src, i0, i1 = runs[0]
+        out = {k: src[k][i0:i1] for k in keys}
+        if with_feats:
+            out["feats"] = [f[i0:i1] for f in src["feats"]]
+        out["_src"], out["_i0"], out["_i1"] = src, i0, i1          # lets neighbouring splits be re-joined as views
+        return out
+    out = {k: torch.cat([src[k][i0:i1] for src, i0, i1 in runs]) for k in keys}
+    if with_feats:
+        out["feats"] = [torch.cat([src["feats"][l][i0:i1] for src, i0, i1 in runs]) for l in range(len(runs[0][0]["feats"]))]
+    return out
 
 
 def _result_class(image_list):
@@ -902,65 +926,48 @@ class DiffusionDet(nn.Module):
         eng.reserve(max(b - a for a, b in bounds), fh, fw, M)
         per_frame = []          # (launch result dict, index inside the launch) for every frame slot of `total`
 
-        def take(a, b, keys=("logits", "boxes", "obj", "k1", "k2"), with_feats=True):
-            """result slots [a, b) as one split: views when they sit in one launch, else a concatenation"""
-            runs = []
-            for j in range(a, b):
-                src, i = per_frame[j]
-                if runs and runs[-1][0] is src:
-                    runs[-1][2] = i + 1
-                else:
-                    runs.append([src, i, i + 1])
-            if len(runs) == 1:
-                src, i0, i1 = runs[0]
-                out = {k: src[k][i0:i1] for k in keys}
-                if with_feats:
-                    out["feats"] = [f[i0:i1] for f in src["feats"]]
-                out["_src"], out["_i0"], out["_i1"] = src, i0, i1          # lets neighbouring splits be re-joined as views
-                return out
-            out = {k: torch.cat([src[k][i0:i1] for src, i0, i1 in runs]) for k in keys}
-            if with_feats:
-                out["feats"] = [torch.cat([src["feats"][l][i0:i1] for src, i0, i1 in runs]) for l in range(len(self.in_features))]
-            return out
-
+        split = functools.partial(take, per_frame)          # split(a, b): result slots [a, b)
         fired = on_global is None or not ref_g
         for ci, (a, a_end) in enumerate(bounds):
             feats = eng.backbone_frames(frames[a:a_end]) if as_list else eng.backbone(total[a:a_end].contiguous())
             if ci == 0 and self.after_first_launch is not None:
                 self.after_first_launch()          # e.g. the data layer's prefetch of the next group: behind this call's own uploads
             B = feats[0].shape[0]
-            if self.skip_unobservable:
-                # x4 (SURVEY.md Appendix B): of the extraction pass only the backbone features of every frame and the top-k
-                # object features of the GLOBAL frames are ever read -- the 3 heads run on the global frames of this chunk only
-                g0, g1 = max(len_l, a) - a, min(n_own, a + B) - a
-                dev, d = self.device, self.hidden_dim
-                res = {"feats": feats, "logits": torch.empty((B, M, self.num_classes), device=dev), "boxes": torch.empty((B, M, 4), device=dev),
-                       "obj": torch.empty((B, M, d), device=dev), "k1": torch.empty((B, self.top_k[0], d), device=dev),
-                       "k2": torch.empty((B, self.top_k[1], d), device=dev)}
-                if g1 > g0:
-                    t = torch.full((g1 - g0,), 999, dtype=torch.long)
-                    (cl, bx, pf), k1, k2 = self.model_predictions([f[g0:g1] for f in feats], whwh, box_init_all[a + g0:a + g1], t, box_extract=ci + 1)
-                    res["k1"][g0:g1] = k1.view(g1 - g0, self.top_k[0], d)
-                    res["k2"][g0:g1] = k2.view(g1 - g0, self.top_k[1], d)
-                per_frame += [(res, i) for i in range(B)]
-                fired = fired or self._fire_on_global(on_global, take, len_l, n_own, a + B, n_total)
-                continue
-            t = torch.full((B,), 999, dtype=torch.long)
-            (cl, bx, pf), k1, k2 = self.model_predictions(feats, whwh, box_init_all[a:a + B], t, box_extract=ci + 1)
-            res = {"feats": feats, "logits": cl, "boxes": bx, "obj": pf[0].view(B, M, self.hidden_dim),
-                   "k1": k1.view(B, self.top_k[0], self.hidden_dim), "k2": k2.view(B, self.top_k[1], self.hidden_dim)}
+            res = self._extract_launch(feats, whwh, box_init_all[a:a + B], max(len_l, a) - a, min(n_own, a + B) - a, ci)
             per_frame += [(res, i) for i in range(B)]
-            if self.debug_taps is not None:
-                self.debug_taps.setdefault("extract", []).append((cl, bx, pf[0], feats))
-            fired = fired or self._fire_on_global(on_global, take, len_l, n_own, a + B, n_total)
+            if self.debug_taps is not None and not self.skip_unobservable:
+                self.debug_taps.setdefault("extract", []).append((res["logits"], res["boxes"], res["obj"], feats))
+            fired = fired or self._fire_on_global(on_global, split, len_l, n_own, a + B, n_total)
 
-        local = take(0, len_l) if len_l else None
-        glob = take(len_l, n_own) if ref_g else None
+        local = split(0, len_l) if len_l else None
+        glob = split(len_l, n_own) if ref_g else None
         out_ahead, pos = {}, n_own
         for fb in sorted(ahead):
-            out_ahead[fb] = take(pos, pos + len(ahead[fb]))
+            out_ahead[fb] = split(pos, pos + len(ahead[fb]))
             pos += len(ahead[fb])
         return local, glob, out_ahead
+
+    def _extract_launch(self, feats, whwh, box_init, g0, g1, ci):
+        """The extraction heads + top-k selection of launch sequence `ci` over the B frames of `feats` (box_init: their draws) -> the
+        launch's result dict of per-frame tensors.  [g0, g1): the launch's global frames."""
+        B, M, d = feats[0].shape[0], self.num_proposals, self.hidden_dim
+        if self.skip_unobservable:
+            # x4 (SURVEY.md Appendix B): of the extraction pass only the backbone features of every frame and the top-k
+            # object features of the GLOBAL frames are ever read -- the 3 heads run on the global frames of this launch only
+            dev = self.device
+            res = {"feats": feats, "logits": torch.empty((B, M, self.num_classes), device=dev), "boxes": torch.empty((B, M, 4), device=dev),
+                   "obj": torch.empty((B, M, d), device=dev), "k1": torch.empty((B, self.top_k[0], d), device=dev),
+                   "k2": torch.empty((B, self.top_k[1], d), device=dev)}
+            if g1 > g0:
+                t = torch.full((g1 - g0,), 999, dtype=torch.long)
+                _, k1, k2 = self.model_predictions([f[g0:g1] for f in feats], whwh, box_init[g0:g1], t, box_extract=ci + 1)
+                res["k1"][g0:g1] = k1.view(g1 - g0, self.top_k[0], d)
+                res["k2"][g0:g1] = k2.view(g1 - g0, self.top_k[1], d)
+            return res
+        t = torch.full((B,), 999, dtype=torch.long)
+        (cl, bx, pf), k1, k2 = self.model_predictions(feats, whwh, box_init, t, box_extract=ci + 1)
+        return {"feats": feats, "logits": cl, "boxes": bx, "obj": pf[0].view(B, M, d), "k1": k1.view(B, self.top_k[0], d),
+                "k2": k2.view(B, self.top_k[1], d)}
 
     def _final_stage(self, feats, cached, whwh, w, h, pairs, items, ddim_draws, slots=None):
         """Global attention + conditioned head (+ DDIM loop) + top-k/NMS over `R` frame slots holding the batches `items`

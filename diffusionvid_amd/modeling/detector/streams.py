@@ -25,7 +25,7 @@ import torch
 
 from ... import ops
 from ...structures.image_list import to_image_list
-from .diffusion_det import _result_class
+from .diffusion_det import _result_class, take
 
 
 def refuse_unless_streaming(cfg):
@@ -238,51 +238,15 @@ class StreamSet:
         for ci, a in enumerate(range(0, n_total, cap)):
             b = min(n_total, a + cap)
             feats = eng.backbone_frames(frames[a:b]) if as_list else eng.backbone(total[a:b].contiguous())
-            B = b - a
-            g0 = max(n_local, a) - a if det.skip_unobservable else 0          # x4: only the global frames' top-k rows are read
-            if det.skip_unobservable:
-                dev = det.device
-                res = {"feats": feats, "logits": torch.empty((B, M, det.num_classes), device=dev), "boxes": torch.empty((B, M, 4), device=dev),
-                       "obj": torch.empty((B, M, d), device=dev), "k1": torch.empty((B, det.top_k[0], d), device=dev),
-                       "k2": torch.empty((B, det.top_k[1], d), device=dev)}
-                if B > g0:
-                    t = torch.full((B - g0,), 999, dtype=torch.long)
-                    _, k1, k2 = det.model_predictions([f[g0:B] for f in feats], whwh, box_init_all[a + g0:b], t, box_extract=ci + 1)
-                    res["k1"][g0:B] = k1.view(B - g0, det.top_k[0], d)
-                    res["k2"][g0:B] = k2.view(B - g0, det.top_k[1], d)
-            else:
-                t = torch.full((B,), 999, dtype=torch.long)
-                (cl, bx, pf), k1, k2 = det.model_predictions(feats, whwh, box_init_all[a:b], t, box_extract=ci + 1)
-                res = {"feats": feats, "logits": cl, "boxes": bx, "obj": pf[0].view(B, M, d), "k1": k1.view(B, det.top_k[0], d),
-                       "k2": k2.view(B, det.top_k[1], d)}
-            per_frame += [(res, i) for i in range(B)]
-
-        def take(a, b, keys, with_feats):
-            """frame slots [a, b) as one split: views when they sit in one launch sequence, else a concatenation"""
-            runs = []
-            for j in range(a, b):
-                src, i = per_frame[j]
-                if runs and runs[-1][0] is src:
-                    runs[-1][2] = i + 1
-                else:
-                    runs.append([src, i, i + 1])
-            if len(runs) == 1:
-                src, i0, i1 = runs[0]
-                out = {k: src[k][i0:i1] for k in keys}
-                if with_feats:
-                    out["feats"] = [f[i0:i1] for f in src["feats"]]
-                return out
-            out = {k: torch.cat([src[k][i0:i1] for src, i0, i1 in runs]) for k in keys}
-            if with_feats:
-                out["feats"] = [torch.cat([src["feats"][l][i0:i1] for src, i0, i1 in runs]) for l in range(len(det.in_features))]
-            return out
+            res = det._extract_launch(feats, whwh, box_init_all[a:b], max(n_local, a) - a, b - a, ci)
+            per_frame += [(res, i) for i in range(b - a)]
 
         glob = {}
         for s, (a, b) in g_at.items():
             if b > a:
-                sp = take(a, b, ("k1", "k2"), False)
+                sp = take(per_frame, a, b, keys=("k1", "k2"), with_feats=False)
                 glob[s] = (sp["k1"].reshape(-1, d), sp["k2"].reshape(-1, d))
-        return (lambda a, b: take(a, b, ("logits", "boxes", "obj"), True)), glob
+        return (lambda a, b: take(per_frame, a, b, keys=("logits", "boxes", "obj"))), glob
 
     # ---- 2. memory update -------------------------------------------------------------------------------------------------------------------
     def _update_memories(self, updates, glob):

@@ -765,7 +765,6 @@ class Model:
         _lib.check(lib.dvid_model_finalize(h), "dvid_model_finalize")
         self._ws = None
         self.chains = -1                 # the library's default until set_chains
-        self._kv_src = None
         # local box-level attention: present when the state dict carries it (the library infers the same from the tensors it was given)
         self.local_stages = 0
         while f"head.local_attention.{self.local_stages}.0.in_proj_weight" in state_dict:
@@ -773,8 +772,8 @@ class Model:
         # the pyramid: four levels (p2..p5) when the state dict carries the stride-4 lateral, as the library infers it; a head-only model
         # takes what rcnn_head is given
         self.fpn_levels = 4 if self.has_backbone and "backbone.fpn_lateral2.weight" in state_dict else 3
-        self._lkv = {}                   # stage -> (memory tensor, its version, groups) whose K / V projections the library holds
-        self._gkv = None                 # (memory [G, lk, d], its version, its shape): the streams' global memories, projected beside the video's
+        # what the library's three projected memories hold: "video" | "groups" | "local" -> (memory tensor, its version, shape key)
+        self._projected = {}
 
     def take_range_flag(self):
         """DTYPE float32 with split operands: True if a launch since the last call met an activation beyond the fp16 range (65504); synchronises
@@ -873,27 +872,35 @@ class Model:
              ptr(pro_features), tp, ptr(cond), ptr(logits), ptr(boxes_out), ptr(obj), ptr(bad_flag), stream_ptr())
         return logits, boxes_out, obj
 
+    def _project_unless_current(self, which, memory, key, project):
+        """THE cache rule of the three projected memories (`which`: "video", "groups" or "local"): the library's K / V rows are current when
+        they came from this tensor object at this version counter with this shape key; otherwise `project(memory as fp32 device tensor)`
+        runs.  The entry is dropped before the call, so a call that fails leaves nothing that points at rows never written, and it holds
+        the tensor afterwards, so the storage cannot be recycled under the cache."""
+        hit = self._projected.get(which)
+        if hit is None or hit[0] is not memory or hit[1] != memory._version or hit[2] != key:
+            self._projected.pop(which, None)
+            project(_cuda(memory, torch.float32))
+            self._projected[which] = (memory, memory._version, key)
+
     def invalidate_memory(self):
         """The global memory changed (new video, memory update, adopted memory, or an in-place write through a raw pointer,
         which no tensor version counter sees): the next global_xattn projects K/V again."""
-        self._kv_src = None
+        self._projected.pop("video", None)
 
     def ensure_memory_projected(self, memory):
-        """K / V projections of `memory` into the engine's buffers unless they are current (same tensor object, same version).
+        """K / V projections of `memory` into the engine's buffers unless they are current (_project_unless_current).
         global_xattn calls it; a captured launch sequence that READS those buffers (DiffusionDet._graphed_call) calls it before
         every replay, because the projection itself is not part of the capture."""
-        if self._kv_src is None or self._kv_src is not memory or self._kv_ver != memory._version:
-            mem = _cuda(memory, torch.float32)
-            call("dvid_global_memory_project", self.handle, ptr(mem), mem.shape[0], stream_ptr())
-            self._kv_src = memory            # holds the tensor: its storage cannot be recycled under the cache
-            self._kv_ver = memory._version
+        self._project_unless_current("video", memory, tuple(memory.shape), lambda mem: call(
+            "dvid_global_memory_project", self.handle, ptr(mem), mem.shape[0], stream_ptr()))
 
     def global_xattn(self, query, memory):
         """cond = MHA(query, memory, memory).  The K/V projections of `memory` are kept until `invalidate_memory()` (the
         detector calls it wherever it assigns the memory) or until another tensor object is passed, i.e. they are computed
-        once per memory update of a video.  The cache key is (tensor object, its version counter): an in-place torch write to
-        the memory (copy_, index_put_, ...) bumps the counter and projects again; a write through a raw pointer, which no
-        counter sees, needs `invalidate_memory()`."""
+        once per memory update of a video.  The cache key is (tensor object, its version counter, its shape): an in-place torch
+        write to the memory (copy_, index_put_, ...) bumps the counter and projects again; a write through a raw pointer, which
+        no counter sees, needs `invalidate_memory()`."""
         query = _cuda(query, torch.float32)
         self.ensure_memory_projected(memory)
         out = torch.empty_like(query)
@@ -903,18 +910,14 @@ class Model:
     def invalidate_memory_groups(self):
         """The grouped global memories changed behind the cache's back (a write through a raw pointer: update_erase_memory_groups writing
         a set's memories in place): the next global_xattn_groups projects K/V again.  The video's projection is not touched."""
-        self._gkv = None
+        self._projected.pop("groups", None)
 
     def ensure_memory_groups_projected(self, memory):
         """K / V projections of G global memories (memory [G, lk, d], one per live stream) into the engine's buffer for them unless
-        they are current: same tensor object, same version, same shape -- the rule of ensure_local_memory_projected.  That buffer is
-        separate from the one ensure_memory_projected fills, so a video's cached projection survives."""
-        hit = getattr(self, "_gkv", None)
-        if hit is None or hit[0] is not memory or hit[1] != memory._version or hit[2] != tuple(memory.shape):
-            mem = _cuda(memory, torch.float32)
-            self._gkv = None
-            call("dvid_global_memory_project_groups", self.handle, ptr(mem), mem.shape[1], mem.shape[0], stream_ptr())
-            self._gkv = (memory, memory._version, tuple(memory.shape))          # holds the tensor: its storage cannot be recycled under the cache
+        they are current (_project_unless_current).  That buffer is separate from the one ensure_memory_projected fills, so a video's
+        cached projection survives."""
+        self._project_unless_current("groups", memory, tuple(memory.shape), lambda mem: call(
+            "dvid_global_memory_project_groups", self.handle, ptr(mem), mem.shape[1], mem.shape[0], stream_ptr()))
 
     def global_xattn_groups(self, query, memory):
         """cond = MHA(query, memory[g], memory[g]) per group: query [rows, d] is G consecutive blocks of rows / G, memory [G, lk, d]; block
@@ -931,21 +934,17 @@ class Model:
     def invalidate_local_memory(self):
         """The local memory changed behind the cache's back (a write through a raw pointer, e.g. a replayed launch sequence): the next
         local_xattn projects K/V again."""
-        self._lkv = {}
+        self._projected.pop("local", None)
 
     def ensure_local_memory_projected(self, memory, groups=1, stage=None):
         """K / V projections of `groups` local memories (memory [groups * lk, d], group g = rows [g lk, (g + 1) lk)) into the engine's
-        buffer unless they are current: same tensor object, same version, same grouping -- the cache idea of ensure_memory_projected,
-        keyed per stage.  The library keeps ONE projected local memory, so projecting a stage drops the others."""
+        buffer unless they are current (_project_unless_current; the stage and the grouping are part of the key).  The library keeps ONE
+        projected local memory, so projecting a stage drops the others."""
         stage = self.local_stages - 1 if stage is None else int(stage)
         if memory.shape[0] % groups:
             raise _lib.DvidError(f"local memory of {memory.shape[0]} rows does not split into {groups} groups")
-        hit = self._lkv.get(stage)
-        if hit is None or hit[0] is not memory or hit[1] != memory._version or hit[2] != groups:
-            mem = _cuda(memory, torch.float32)
-            self._lkv = {}
-            call("dvid_local_memory_project", self.handle, stage, ptr(mem), mem.shape[0] // groups, int(groups), stream_ptr())
-            self._lkv[stage] = (memory, memory._version, groups)          # holds the tensor: its storage cannot be recycled under the cache
+        self._project_unless_current("local", memory, (stage, int(groups), tuple(memory.shape)), lambda mem: call(
+            "dvid_local_memory_project", self.handle, stage, ptr(mem), mem.shape[0] // groups, int(groups), stream_ptr()))
 
     def local_xattn(self, query, memory, groups=1, stage=None):
         """cond = LayerNorm(MHA(query, memory, memory)) of the local box-level stage `stage` (default and only legal value: the last one,

@@ -147,6 +147,49 @@ def test_global_xattn_groups_is_bit_equal_per_group(dv, precision):
         model.close()
 
 
+@pytest.mark.parametrize("precision", ["float16", "float32"])
+def test_three_projected_memories_are_independent(dv, precision):
+    """The video's global memory, the streams' grouped global memories and the local memories on ONE model: each is projected once, each
+    attention reads its own projection whatever ran between, and each gives the bits of a model that ran nothing else.  lk = 75 is no
+    multiple of 32 (the V-transpose padding); 600 query rows in 2 groups."""
+    import re
+    from diffusionvid_amd.utils import synthetic
+
+    def fresh():
+        m = dv.Model(synthetic.make_head_state_dict(0, local_stages=1), res_blocks=(0, 0, 0, 0), precision=precision)
+        m.reserve(2, 64, 64, 300)
+        return m
+    g = torch.Generator().manual_seed(33)
+    q = torch.randn(600, D, generator=g).cuda()
+    video_mem = torch.randn(75, D, generator=g).cuda()
+    group_mem = torch.randn(2, 75, D, generator=g).cuda()
+    local_mem = torch.randn(150, D, generator=g).cuda()
+    runs = {"video": lambda m: m.global_xattn(q, video_mem), "groups": lambda m: m.global_xattn_groups(q, group_mem),
+            "local": lambda m: m.local_xattn(q, local_mem, groups=2)}
+    model = fresh()
+    projections = []
+    real_call = dv.call
+
+    def counting(name, *a):
+        if re.fullmatch(r"dvid_\w+_memory_project\w*", name):
+            projections.append(name)
+        return real_call(name, *a)
+    dv.call = counting
+    try:
+        first = {k: runs[k](model) for k in ("video", "groups", "local")}
+        second = {k: runs[k](model) for k in ("local", "groups", "video")}
+        assert sorted(projections) == ["dvid_global_memory_project", "dvid_global_memory_project_groups", "dvid_local_memory_project"]
+    finally:
+        dv.call = real_call
+    for k in runs:
+        assert torch.equal(first[k], second[k]), (precision, k)
+        alone = fresh()
+        assert torch.equal(runs[k](alone), first[k]), (precision, k)
+        alone.close()
+    assert not torch.equal(first["video"], first["groups"]) and not torch.equal(first["groups"], first["local"])          # three different memories
+    model.close()
+
+
 # ---- 3.-5. end to end ---------------------------------------------------------------------------------------------------------------------
 def _model(dtype, sample_step):
     from diffusionvid_amd.config import get_cfg

@@ -592,6 +592,46 @@ def test_engine_builds_lookahead_from_unchanged_dataset(tmp_path):
         assert got == exp, idx
 
 
+def test_take_returns_views_inside_a_launch_and_concatenations_across():
+    """diffusion_det.take, the split of frame slots [a, b) that DiffusionDet._extract and StreamSet._extract share, over two launch
+    results of 3 and 2 frames."""
+    from diffusionvid_amd.modeling.detector.diffusion_det import take
+    g = torch.Generator().manual_seed(5)
+    keys = ("logits", "boxes", "obj", "k1", "k2")
+
+    def launch(n, levels=2):
+        res = {k: torch.randn(n, 4, 3 + i, generator=g) for i, k in enumerate(keys)}
+        res["feats"] = [torch.randn(n, 2 << lvl, 2 << lvl, 8, generator=g) for lvl in range(levels)]
+        return res
+    r0, r1 = launch(3), launch(2)
+    per_frame = [(r0, 0), (r0, 1), (r0, 2), (r1, 0), (r1, 1)]
+    # inside one launch: views, and the back-references that let neighbouring splits be re-joined
+    sp = take(per_frame, 1, 3)
+    assert set(sp) == set(keys) | {"feats", "_src", "_i0", "_i1"}
+    assert sp["_src"] is r0 and (sp["_i0"], sp["_i1"]) == (1, 3)
+    for k in keys:
+        assert sp[k].data_ptr() == r0[k][1:3].data_ptr() and sp[k].shape == r0[k][1:3].shape and torch.equal(sp[k], r0[k][1:3])
+    assert len(sp["feats"]) == 2 and all(f.data_ptr() == s[1:3].data_ptr() and f.shape[0] == 2 for f, s in zip(sp["feats"], r0["feats"]))
+    sp = take(per_frame, 3, 5)
+    assert sp["_src"] is r1 and (sp["_i0"], sp["_i1"]) == (0, 2) and sp["k1"].data_ptr() == r1["k1"].data_ptr()
+    # across both launches: the concatenation, per key and per level; nothing to re-join
+    sp = take(per_frame, 1, 5)
+    assert set(sp) == set(keys) | {"feats"}
+    for k in keys:
+        assert torch.equal(sp[k], torch.cat([r0[k][1:3], r1[k][0:2]]))
+    assert len(sp["feats"]) == 2
+    for lvl in range(2):
+        assert torch.equal(sp["feats"][lvl], torch.cat([r0["feats"][lvl][1:3], r1["feats"][lvl][0:2]]))
+    # the keyword form of the memory build: exactly those keys
+    sp = take(per_frame, 2, 4, keys=("k1", "k2"), with_feats=False)
+    assert set(sp) == {"k1", "k2"} and torch.equal(sp["k2"], torch.cat([r0["k2"][2:3], r1["k2"][0:1]]))
+    assert set(take(per_frame, 0, 2, keys=("k1", "k2"), with_feats=False)) == {"k1", "k2", "_src", "_i0", "_i1"}
+    # launches without feature maps: an empty list either way
+    e0, e1 = launch(3, levels=0), launch(2, levels=0)
+    empty = [(e0, 0), (e0, 1), (e0, 2), (e1, 0), (e1, 1)]
+    assert take(empty, 0, 3)["feats"] == [] and take(empty, 2, 5)["feats"] == []
+
+
 def test_gelu_erfc_form_matches_exact_gelu():
     """csrc/common.h gelu_erf: x * Phi(x) with Phi through erfc(z) = t exp(-z^2 + P(t)), restated here in float32 step by step (the
     coefficients are parsed from the header, so the test follows the kernel).  It must agree with nn.GELU's exact (erf) form -- the
