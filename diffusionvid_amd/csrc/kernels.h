@@ -215,6 +215,12 @@ int dvid_vid_eval_match_launch(const float* dets, const int* counts, int n_frame
                                int num_classes, signed char* match, double* weight, int* rank, double* n_pos, int* top_row, signed char* top_hit,
                                hipStream_t s);
 
+// cocoeval.hip: the COCO bbox evaluator's matching, a workgroup per image; iou_thrs / area_ranges are host tables (include/dvid_hip.h)
+int dvid_coco_eval_match_launch(const float* dets, const int* counts, int n_images, int cap, const double* gt_boxes, const double* gt_areas,
+                                const unsigned char* gt_crowd, const int* gt_labels, const int* gt_starts, const double* iou_thrs,
+                                const double* area_ranges, int num_classes, signed char* match, signed char* ignore, int* rank, int* npig,
+                                hipStream_t s);
+
 // fps.hip
 int dvid_cdist_launch(const float* x, int n, int d, float* dist, hipStream_t s);
 int dvid_fps_launch(const float* dist, int n, int m, int bs_emul, int* idx, hipStream_t s);

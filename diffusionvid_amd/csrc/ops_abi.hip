@@ -313,6 +313,33 @@ int dvid_vid_eval_match(const float* dets, const int* counts, int n_frames, int 
     return DVID_OK;
 }
 
+int dvid_coco_eval_match(const float* dets, const int* counts, int n_images, int cap, const double* gt_boxes, const double* gt_areas,
+                         const unsigned char* gt_crowd, const int* gt_labels, const int* gt_starts, const int* gt_starts_host,
+                         const double* iou_thrs, const double* area_ranges, int num_classes, signed char* match, signed char* ignore,
+                         int* rank, int* npig, void* stream) {
+    g_err[0] = 0;
+    if (!dets || !counts || !gt_starts || !gt_starts_host || !iou_thrs || !area_ranges || !match || !ignore || !rank || !npig)
+        FAIL(DVID_ERR_ARG, "COCO evaluation: null pointer");
+    if (n_images < 0 || cap < 1 || num_classes < 1)
+        FAIL(DVID_ERR_ARG, "COCO evaluation: bad sizes (%d images, %d rows per image, %d classes)", n_images, cap, num_classes);
+    if (cap > DVID_NMS_MAX_CANDIDATES)
+        FAIL(DVID_ERR_UNSUPPORTED, "COCO evaluation: %d rows per image exceed the limit of %d (DVID_NMS_MAX_CANDIDATES)", cap, DVID_NMS_MAX_CANDIDATES);
+    if (num_classes > DVID_MAX_CLASSES)
+        FAIL(DVID_ERR_UNSUPPORTED, "COCO evaluation: %d classes exceed the limit of %d (DVID_MAX_CLASSES)", num_classes, DVID_MAX_CLASSES);
+    if (gt_starts_host[0] != 0) FAIL(DVID_ERR_ARG, "COCO evaluation: gt_starts[0] is %d, not 0", gt_starts_host[0]);
+    for (int f = 0; f < n_images; ++f) {
+        const int g = gt_starts_host[f + 1] - gt_starts_host[f];
+        if (g < 0) FAIL(DVID_ERR_ARG, "COCO evaluation: gt_starts decreases at image %d", f);
+        if (g > DVID_COCO_EVAL_MAX_GT)
+            FAIL(DVID_ERR_UNSUPPORTED, "COCO evaluation: image %d holds %d ground-truth boxes, the limit is %d (DVID_COCO_EVAL_MAX_GT)", f, g,
+                 DVID_COCO_EVAL_MAX_GT);
+    }
+    if (gt_starts_host[n_images] > 0 && (!gt_boxes || !gt_areas || !gt_crowd || !gt_labels)) FAIL(DVID_ERR_ARG, "COCO evaluation: null ground truth");
+    TRY(dvid_coco_eval_match_launch(dets, counts, n_images, cap, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_starts, iou_thrs, area_ranges, num_classes,
+                                    match, ignore, rank, npig, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
 int dvid_cdist(const float* x, int n, int d, float* dist, void* stream) {
     g_err[0] = 0;
     TRY(dvid_cdist_launch(x, n, d, dist, reinterpret_cast<hipStream_t>(stream)));

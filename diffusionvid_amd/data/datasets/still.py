@@ -4,7 +4,8 @@ images apart.
 An item is `(image, image_id, (w, h))`: the image resized by its shortest edge with the video path's own transform (data/transforms.py:
 ResizeToTensor on the host, ResizeToTensorDevice = dvid_resize_u8_to_f32 on the GPU) as fp32 [3, oh, ow] in [0, 1], un-padded -- the
 batch's common canvas is made by the collate function -- and the ORIGINAL (w, h), to which engine.inference_images maps the detections
-back.  No annotations are read here: COCO evaluation is not part of this package."""
+back.  No annotations are read here: engine.inference_images scores the detections against a COCO annotation file
+(data/evaluation/coco_eval.py)."""
 import torch
 
 from ...structures.image_list import to_image_list

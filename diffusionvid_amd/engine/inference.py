@@ -408,13 +408,24 @@ def write_coco_results(predictions, path, label_map=None):
     return res
 
 
-def inference_images(model, loader, output_folder=None, label_map=None):
+def inference_images(model, loader, output_folder=None, label_map=None, annotations=None, eval_device=None):
     """Still images: `loader` yields (images, image_ids, original (w, h) per image) batches (data/datasets/still.py: batches, or a DataLoader
     over StillImageDataset with OrientationBatchSampler and collate_images); every batch goes through model.detect_images with its ids
     -- so an image's draws, and with them its detections, do not depend on its batch -- and every BoxList is mapped back to the image's
     original size (BoxList.resize).  -> {image_id: BoxList} on the host; with `output_folder` also `predictions.pth` (that dict) and
-    `coco_results.json` (coco_results with `label_map`).  Evaluation against COCO annotations is not part of this package."""
+    `coco_results.json` (coco_results with `label_map`).
+    annotations (a COCO annotation file, its dict or a coco_eval.CocoAnnotations): the predictions are scored with the COCO bbox
+    protocol (coco_eval.do_coco_evaluation; `coco_eval.txt` in `output_folder`) -> (predictions, the ordered dict of the twelve
+    numbers); `label_map` then defaults to the annotations' label -> category id map, and a prediction for an image that the
+    annotations do not list is an error that names the id.  eval_device: a torch.device runs the evaluator's matching there; None keeps
+    it in numpy."""
     import os
+    ann = None
+    if annotations is not None:
+        from ..data.evaluation import coco_eval
+        ann = annotations if isinstance(annotations, coco_eval.CocoAnnotations) else coco_eval.CocoAnnotations(annotations)
+        if label_map is None:
+            label_map = ann.category_of
     predictions = {}
     cpu = torch.device("cpu")
     with torch.no_grad():
@@ -423,9 +434,13 @@ def inference_images(model, loader, output_folder=None, label_map=None):
             for bl, image_id, size in zip(out, image_ids, sizes):
                 if int(image_id) in predictions:
                     raise ValueError("image id %d appears twice" % int(image_id))
+                if ann is not None and int(image_id) not in ann.images:
+                    raise ValueError("there is a prediction for image id %d, which the annotations do not list" % int(image_id))
                 predictions[int(image_id)] = bl.to(cpu).resize((int(size[0]), int(size[1])))
     if output_folder:
         os.makedirs(output_folder, exist_ok=True)
         torch.save(predictions, os.path.join(output_folder, "predictions.pth"))
         write_coco_results(predictions, os.path.join(output_folder, "coco_results.json"), label_map)
-    return predictions
+    if ann is None:
+        return predictions
+    return predictions, coco_eval.do_coco_evaluation(ann, predictions, output_folder, device=eval_device)

@@ -349,6 +349,36 @@ int dvid_vid_eval_match(const float* dets, const int* counts, int n_frames, int 
                         const int* gt_starts, const int* gt_starts_host, int label_min, int label_max, const double* motion,
                         const double* ranges, const double* empty_w, int n_ranges, float iou_thresh, int num_classes, signed char* match,
                         double* weight, int* rank, double* n_pos, int* top_row, signed char* top_hit, void* stream);
+/* The matching of the COCO bbox evaluator on the device (dvid_version >= 6; csrc/cocoeval.hip; data/evaluation/coco_eval.py:
+ * evaluate_numpy's loop), one workgroup per image, the ten IoU thresholds and the four area ranges in one launch.  No model handle,
+ * independent of DTYPE.
+ * in   dets [n_images, cap, 6] fp32 (xyxy box in annotation pixels, score, label as a float), counts [n_images] int32 (device), the
+ *      layout of engine.pack_predictions; the ragged ground truth gt_boxes [G, 4] float64 (x, y, w, h), gt_areas [G] float64 (the
+ *      annotation's own area), gt_crowd [G] uint8, gt_labels [G] int32, gt_starts [n_images + 1] int32 (device; image f owns boxes
+ *      [gt_starts[f], gt_starts[f + 1])) and, on the HOST, gt_starts_host (the same table), iou_thrs [DVID_COCO_EVAL_THRESHOLDS] and
+ *      area_ranges [DVID_COCO_EVAL_AREAS, 2] float64 (both ends inclusive).
+ * out  match and ignore [DVID_COCO_EVAL_AREAS, DVID_COCO_EVAL_THRESHOLDS, n_images, cap] int8, at the row's own place: 1 when the row took
+ *      a box / when it does not count (it took an ignored box, or took none and its own area w * h lies outside the range); rank
+ *      [n_images, cap] int32: the row's position in its (image, label) list in descending score, equal scores lower row first; -1, match
+ *      0 and ignore 0 behind counts[f], for a label outside 0 .. num_classes and past position DVID_COCO_EVAL_MAX_DETS; npig
+ *      [DVID_COCO_EVAL_AREAS, num_classes + 1] int32: the boxes per label that are neither crowd nor outside the range.
+ * A box is ignored in a range when it is crowd or its area lies outside.  A row walks the boxes of its label, the not ignored ones and
+ * then the ignored ones, each group in annotation order, starting from best = min(threshold, 1 - 1e-10): a box that an earlier row took
+ * is skipped unless it is crowd, a box with IoU < best is skipped, any other becomes the match and its IoU the new best (so equal IoU
+ * moves to the later box); a row matched to a not ignored box does not go on to the ignored ones.  The IoU is float64, one operation at
+ * a time: the overlap per axis min(dx + dw, gx + gw) - max(dx, gx) (<= 0 on either axis: IoU 0), i = w * h, u = dw * dh for a crowd box
+ * and (dw * dh + gw * gh) - i otherwise, one IEEE division; a row's w is x2 - x1 of its float32 corners, in float64.  Precondition: the
+ * scores are finite.
+ * Before anything is launched: cap <= DVID_NMS_MAX_CANDIDATES, num_classes <= DVID_MAX_CLASSES, at most DVID_COCO_EVAL_MAX_GT boxes
+ * per image (DVID_ERR_UNSUPPORTED beyond, with the limit and the value in the message; nothing is written). */
+#define DVID_COCO_EVAL_MAX_GT 256
+#define DVID_COCO_EVAL_THRESHOLDS 10
+#define DVID_COCO_EVAL_AREAS 4
+#define DVID_COCO_EVAL_MAX_DETS 100
+int dvid_coco_eval_match(const float* dets, const int* counts, int n_images, int cap, const double* gt_boxes, const double* gt_areas,
+                         const unsigned char* gt_crowd, const int* gt_labels, const int* gt_starts, const int* gt_starts_host,
+                         const double* iou_thrs, const double* area_ranges, int num_classes, signed char* match, signed char* ignore,
+                         int* rank, int* npig, void* stream);
 int dvid_cdist(const float* x, int n, int d, float* dist, void* stream);
 /* bs_emul: block size of the reference CUDA launch to emulate for tie-breaking (0 = fps.cu's own rule) */
 int dvid_fps_greedy(const float* dist, int n, int m, int bs_emul, int* idx, void* stream);
