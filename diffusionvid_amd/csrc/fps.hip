@@ -115,7 +115,8 @@ __global__ __launch_bounds__(1024) void fps_kernel(const float* __restrict__ dis
 // The same greedy sweep with the running distances in registers (EPT points per thread, 256 threads) and the winner's index decoded
 // from the winning key itself -- prio = bitrev(k % bs) * pmul + k / bs is invertible -- so a step is one row read, one wave
 // reduction, ONE barrier (winner slots double-buffered) instead of two barriers and an owner search through LDS.  Same keys, same
-// maximum: the same picks as fps_kernel (tests/test_gpu_kernels.py compares both with the thread-level emulation of fps.cu).
+// maximum: the same picks as fps_kernel.  tests/test_gpu_fps.py compares both with the thread-level emulation of fps.cu: this kernel
+// on both sides of every EPT threshold (test_fps_kernel_boundaries), fps_kernel beyond 4096 points (test_fps_lds_kernel).
 template <int EPT>
 __global__ __launch_bounds__(256) void fps_reg_kernel(const float* __restrict__ dist, int n, int m, int bs, int bs_bits,
                                                        int* __restrict__ idx) {

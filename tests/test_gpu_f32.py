@@ -153,6 +153,8 @@ def test_f32_roialign(dv):
 
 @pytest.mark.parametrize("B,lq,lk", [(2, 300, 300), (1, 777, 900), (1, 64, 37), (3, 17, 1)])
 def test_f32_mha(dv, B, lq, lk):
+    """fp32 attention on dense operands at the model's sizes.  Key and query counts around the 16 / 64-key chunks, the model's packed
+    pitches and wide score ranges: tests/test_gpu_mha.py."""
     g = torch.Generator().manual_seed(5)
     q, k, v = (torch.randn(B, L, 256, generator=g) for L in (lq, lk, lk))
     qh, kh, vh = (t.double().view(B, -1, 8, 32).transpose(1, 2) for t in (q, k, v))

@@ -143,7 +143,8 @@ def test_roialign_multilevel(dv):
 
 @pytest.mark.parametrize("B,lq,lk", [(2, 300, 300), (1, 777, 900), (1, 64, 37), (3, 17, 1)])
 def test_mha_mfma(dv, B, lq, lk):
-    """MFMA attention: fp16 operands (oracle gets the same rounded q/k/v), fp32 softmax, fp16 output."""
+    """MFMA attention: fp16 operands (oracle gets the same rounded q/k/v), fp32 softmax, fp16 output.  Key and query counts around the
+    16 / 32-key tiles, the model's packed pitches, wide score ranges and a stale V^T scratch: tests/test_gpu_mha.py."""
     g = torch.Generator().manual_seed(55)
     d, nh = 256, 8
     q, k, v = (h16(torch.randn(B, l, d, generator=g)) for l in (lq, lk, lk))
@@ -530,6 +531,8 @@ def test_postproc_on_reference_nms_vectors(dv):
 
 
 def test_cdist_fps_gather(dv):
+    """cdist -> greedy FPS -> gather at the model's sizes, all on the register kernel.  The thresholds between the FPS kernels, the LDS
+    form beyond 4096 points, emulated block sizes, tile edges of cdist and equal rows: tests/test_gpu_fps.py."""
     g = torch.Generator().manual_seed(13)
     x = torch.randn(1800, 256, generator=g)
     D = torch.cdist(x, x, p=2.0)
