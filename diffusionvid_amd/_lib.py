@@ -111,6 +111,9 @@ SIGNATURES = {
     "dvid_f32_to_f16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "dvid_resize_u8_to_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                       c_void_p, c_void_p, c_int, c_void_p]),
+    "dvid_resize_views_u8": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int,
+                                     c_int, c_void_p]),
+    "dvid_bbox_aug_merge": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p] * 5),
     "dvid_igemm_num_configs": (c_int, []),
     "dvid_igemm_set_config": (c_int, [c_int]),
     "dvid_igemm_set_tuning": (c_int, [c_int]),

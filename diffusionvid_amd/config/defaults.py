@@ -128,6 +128,13 @@ _C.TEST = CN()
 _C.TEST.IMS_PER_BATCH = 8
 _C.TEST.DETECTIONS_PER_IMG = 100
 _C.TEST.SEQ_NMS = False
+# test-time augmentation of still images (mega_core/config/defaults.py: TEST.BBOX_AUG, engine/bbox_aug.py): DiffusionDet.detect_images_aug
+_C.TEST.BBOX_AUG = CN()
+_C.TEST.BBOX_AUG.ENABLED = False
+_C.TEST.BBOX_AUG.H_FLIP = False
+_C.TEST.BBOX_AUG.SCALES = ()
+_C.TEST.BBOX_AUG.MAX_SIZE = 4000
+_C.TEST.BBOX_AUG.SCALE_H_FLIP = False
 
 _C.OUTPUT_DIR = "."
 _C.DTYPE = "float32"

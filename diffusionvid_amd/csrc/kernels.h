@@ -67,6 +67,12 @@ int dvid_add_layernorm_launch(const float* x, const float* r, const float* g, co
 int dvid_f32_to_f16_launch(const float* x, half_t* y, long n, hipStream_t s);
 int dvid_resize_u8_launch(const unsigned char* src, int h, int w, unsigned char* tmp, float* out, int oh, int ow, int ph, int pw,
                           const int* xbounds, const int* xk, int xksize, const int* ybounds, const int* yk, int yksize, hipStream_t s);
+// n images, each by its own row of `plan` (resize.hip), -> out [n * (1 + flip)][3][ph][pw]; max_h: the tallest source with an x pass (0: none)
+int dvid_resize_views_u8_launch(const unsigned char* const* srcs, int n, const long long* plan, const int* bounds, const int* kk,
+                                unsigned char* tmp, float* out, int ph, int pw, int flip, int max_h, int max_ow, hipStream_t s);
+// bboxaug.hip
+int dvid_bbox_aug_merge_launch(const float* boxes, const float* scores, const int* labels, const int* counts, const float* table, int n, int V,
+                               int cap, float* cand_boxes, float* cand_scores, int* cand_labels, int* live, hipStream_t s);
 // fc = x * (scale[frame] + 1) + shift  (shift per frame [B,D] or per row [R,D])
 int dvid_modulate_launch(const float* x, const float* scale, int scale_ld, const float* shift, int shift_per_row, int shift_ld,
                          half_t* y16, int rows, int rows_per_frame, int d, hipStream_t s);

@@ -528,4 +528,51 @@ int dvid_resize_u8_to_f32(const void* src_hwc, int h, int w, void* tmp, float* o
     if (rc != DVID_OK) FAIL(rc, "resize %dx%d -> %dx%d (padded %dx%d): bad sizes or missing tables / scratch", h, w, oh, ow, ph, pw);
     return DVID_OK;
 }
+
+int dvid_resize_views_u8(const void* const* srcs, int n, const long long* plan, const long long* plan_host, const int* bounds,
+                         int64_t n_bound_rows, const int* weights, int64_t n_weights, void* tmp, int64_t tmp_bytes, float* out, int ph, int pw,
+                         int flip, void* stream) {
+    g_err[0] = 0;
+    if (!srcs || !plan || !plan_host || !bounds || !weights || !tmp || !out) FAIL(DVID_ERR_ARG, "resize views: null pointer");
+    if (n < 1 || n > 65535 || ph < 1 || pw < 1 || ph > 65535) FAIL(DVID_ERR_ARG, "resize views: %d images on a %d x %d canvas", n, ph, pw);
+    int max_h = 0, max_ow = 0;
+    for (int i = 0; i < n; ++i) {          // every offset the kernels add is checked here, against the sizes of what they index
+        const long long* d = plan_host + (long)i * 11;
+        const long long h = d[0], w = d[1], oh = d[2], ow = d[3];
+        if (h < 1 || w < 1 || oh < 1 || ow < 1 || h > 65535 || oh > ph || ow > pw)
+            FAIL(DVID_ERR_ARG, "resize views: image %d is %lld x %lld -> %lld x %lld on a %d x %d canvas", i, h, w, oh, ow, ph, pw);
+        const long long axis[2][4] = {{d[4], d[5], d[6], ow}, {d[7], d[8], d[9], oh}};
+        for (int a = 0; a < 2; ++a) {
+            const long long row = axis[a][0], k0 = axis[a][1], ks = axis[a][2], len = axis[a][3];
+            if ((row < 0) != (a == 0 ? ow == w : oh == h))
+                FAIL(DVID_ERR_ARG, "resize views: image %d has %s tables for its %s pass", i, row < 0 ? "no" : "unexpected", a == 0 ? "x" : "y");
+            if (row >= 0 && (row + len > n_bound_rows || k0 < 0 || ks < 1 || k0 + len * ks > n_weights))
+                FAIL(DVID_ERR_ARG, "resize views: the %s tables of image %d lie outside the concatenated tables", a == 0 ? "x" : "y", i);
+        }
+        if (d[4] >= 0) {
+            if (d[10] < 0 || d[10] + h * ow * 3 > tmp_bytes) FAIL(DVID_ERR_ARG, "resize views: image %d's intermediate rows lie outside the %lld scratch bytes", i, (long long)tmp_bytes);
+            if (h > max_h) max_h = (int)h;
+        }
+        if (ow > max_ow) max_ow = (int)ow;
+    }
+    TRY(dvid_resize_views_u8_launch(reinterpret_cast<const unsigned char* const*>(srcs), n, plan, bounds, weights,
+                                    reinterpret_cast<unsigned char*>(tmp), out, ph, pw, flip, max_h, max_ow, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int dvid_bbox_aug_merge(const float* boxes, const float* scores, const int* labels, const int* counts, const float* table, int n, int views,
+                        int cap, float* cand_boxes, float* cand_scores, int* cand_labels, int* live, void* stream) {
+    g_err[0] = 0;
+    if (!boxes || !scores || !labels || !counts || !table || !cand_boxes || !cand_scores || !cand_labels || !live)
+        FAIL(DVID_ERR_ARG, "bbox aug merge: null pointer");
+    if (((uintptr_t)boxes | (uintptr_t)cand_boxes) & 15) FAIL(DVID_ERR_ARG, "bbox aug merge: the box arrays must be 16-byte aligned");
+    if (n < 1 || views < 1 || cap < 1) FAIL(DVID_ERR_ARG, "bbox aug merge: bad sizes (%d images, %d views, cap %d)", n, views, cap);
+    if (views > DVID_BBOX_AUG_MAX_VIEWS) FAIL(DVID_ERR_UNSUPPORTED, "bbox aug merge: %d views exceed the limit of %d", views, DVID_BBOX_AUG_MAX_VIEWS);
+    if ((long)views * cap > DVID_NMS_MAX_CANDIDATES)
+        FAIL(DVID_ERR_UNSUPPORTED, "bbox aug merge: %d views x %d rows = %ld candidates per image exceed the NMS's limit of %d", views, cap,
+             (long)views * cap, DVID_NMS_MAX_CANDIDATES);
+    TRY(dvid_bbox_aug_merge_launch(boxes, scores, labels, counts, table, n, views, cap, cand_boxes, cand_scores, cand_labels, live,
+                                   reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
 }  // extern "C"

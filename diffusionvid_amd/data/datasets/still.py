@@ -13,14 +13,17 @@ from ..transforms import ResizeToTensor, get_size
 
 
 class StillImageDataset:
-    def __init__(self, files, transform=None, loader=None, image_ids=None, min_size=800, max_size=1333):
-        """files: paths (or whatever `loader` takes); loader(path) -> uint8 HWC RGB (default: Pillow); transform(image, is_current=True)
+    def __init__(self, files, transform=None, loader=None, image_ids=None, min_size=800, max_size=1333, raw=False):
+        """raw: the item's image is the loader's uint8 HWC array at its native size, no transform (TEST.BBOX_AUG: the detector builds every
+        view itself, DiffusionDet.detect_images_aug); `resized_size`, and with it the orientation sampler, keep the plain transform's sizes.
+        files: paths (or whatever `loader` takes); loader(path) -> uint8 HWC RGB (default: Pillow); transform(image, is_current=True)
         -> fp32 [3, oh, ow] (or the device transform's padded [1, 3, ph, pw] with `.image_size`); image_ids default to 0 .. n-1."""
         self.files = list(files)
         self.image_ids = list(range(len(self.files))) if image_ids is None else [int(i) for i in image_ids]
         if len(self.image_ids) != len(self.files):
             raise ValueError("%d image_ids for %d files" % (len(self.image_ids), len(self.files)))
         self.min_size, self.max_size = min_size, max_size
+        self.raw = bool(raw)
         self.transform = transform or ResizeToTensor(min_size, max_size)
         self._default_loader = loader is None
         if loader is None:
@@ -52,6 +55,8 @@ class StillImageDataset:
         raw = self.loader(self.files[idx])
         h, w = raw.shape[:2]
         self._sizes[idx] = (int(w), int(h))
+        if self.raw:
+            return raw, self.image_ids[idx], (int(w), int(h))
         img = self.transform(raw, is_current=True)          # every still image chooses its own size
         size = getattr(img, "image_size", None)
         if size is not None:                                 # the device transform pads to a multiple of 32 of the image's own size
@@ -100,7 +105,15 @@ def collate_images(items, size_divisible=32):
     return to_image_list(images, size_divisible), [it[1] for it in items], [tuple(it[2]) for it in items]
 
 
-def batches(dataset, batch_size, size_divisible=32):
-    """the plain loader: collate_images over OrientationBatchSampler, one batch after the other"""
+def collate_raw(items):
+    """[(uint8 HWC image, id, (w, h))] of a raw dataset -> ([image], [id], [(w, h)]): the images stay as they are, each with its own size"""
+    return [it[0] for it in items], [it[1] for it in items], [tuple(it[2]) for it in items]
+
+
+def batches(dataset, batch_size, size_divisible=32, raw=False):
+    """the plain loader: collate_images (raw: collate_raw, over a dataset in raw mode) over OrientationBatchSampler, one batch after the other"""
+    if raw and not getattr(dataset, "raw", False):
+        raise ValueError("batches(raw=True) needs a StillImageDataset(raw=True)")
     for idx in OrientationBatchSampler(dataset, batch_size):
-        yield collate_images([dataset[i] for i in idx], size_divisible)
+        items = [dataset[i] for i in idx]
+        yield collate_raw(items) if raw else collate_images(items, size_divisible)

@@ -14,6 +14,7 @@ src/libImaging/Resample.c: precompute_coeffs, normalize_coeffs_8bpc, ImagingResa
 to Pillow's output, so that frames can travel to the GPU as uint8 at their native size (a 1280x720 JPEG frame is 2.8 MB
 instead of 7.5 MB of padded fp32) and be resized, scaled to [0,1] and zero-padded there.
 """
+import collections
 import math
 
 import numpy as np
@@ -86,6 +87,100 @@ def resize_u8_numpy(img_hwc, out_hw):
     if oh != h:
         out = _pass_numpy(out, *resample_tables(h, oh), axis=0)
     return out
+
+
+# ---- TEST.BBOX_AUG: the views of a still image (mega_core/engine/bbox_aug.py: im_detect_bbox_aug) --------------------------------------
+BBOX_AUG_MAX_VIEWS = 64          # the draw key's `image` slot holds the view index (utils/synthetic.py: 64 images per step)
+
+
+# one view: the (w, h) its `Resize` gives, whether it is mirrored behind it, and its scale group
+View = collections.namedtuple("View", ["w", "h", "flip", "group"])
+
+
+def bbox_aug_scales(cfg):
+    """[(min_size, max_size, n_views)] per scale group, in im_detect_bbox_aug's order: the identity scale (INPUT.MIN_SIZE_TEST,
+    INPUT.MAX_SIZE_TEST; two views with H_FLIP), then every TEST.BBOX_AUG.SCALES entry under BBOX_AUG.MAX_SIZE (two with SCALE_H_FLIP)"""
+    aug = cfg.TEST.BBOX_AUG
+    groups = [(int(cfg.INPUT.MIN_SIZE_TEST), int(cfg.INPUT.MAX_SIZE_TEST), 2 if aug.H_FLIP else 1)]
+    groups += [(int(s), int(aug.MAX_SIZE), 2 if aug.SCALE_H_FLIP else 1) for s in aug.SCALES]
+    return groups
+
+
+def bbox_aug_num_views(cfg):
+    return sum(g[2] for g in bbox_aug_scales(cfg))
+
+
+def bbox_aug_views(cfg, image_size_wh):
+    """The views of an image of (w, h), in the order im_detect_bbox_aug detects them -- view 0 is the plain test transform; a scale group
+    is one scale entry with its one or two views (the second one the mirror of the first, same size)."""
+    views = []
+    for g, (lo, hi, n) in enumerate(bbox_aug_scales(cfg)):
+        oh, ow = get_size(image_size_wh, lo, hi)
+        views += [View(int(ow), int(oh), k == 1, g) for k in range(n)]
+    return views
+
+
+def bbox_aug_check(cfg, num_proposals, sample_step, max_candidates):
+    """TEST.BBOX_AUG.ENABLED: refuses what the merge cannot take (NotImplementedError with the keys and the numbers)"""
+    n_views = bbox_aug_num_views(cfg)
+    aug = cfg.TEST.BBOX_AUG
+    what = "TEST.BBOX_AUG (H_FLIP %s, SCALES %s, SCALE_H_FLIP %s) gives %d views" % (aug.H_FLIP, tuple(aug.SCALES), aug.SCALE_H_FLIP, n_views)
+    if n_views > BBOX_AUG_MAX_VIEWS:
+        raise NotImplementedError("%s: the limit is %d (the view index is the `image` slot of the draw key)" % (what, BBOX_AUG_MAX_VIEWS))
+    per_view = max(1, int(sample_step) - 1) * int(num_proposals)
+    if n_views * per_view > max_candidates:
+        raise NotImplementedError(
+            "%s of max(1, SAMPLE_STEP - 1) * NUM_PROPOSALS = max(1, %d - 1) * %d = %d candidates each: the merging NMS gets %d per image, the limit is %d"
+            % (what, sample_step, num_proposals, per_view, n_views * per_view, max_candidates))
+    return n_views
+
+
+class ViewsPlan:
+    """What ops.resize_views_u8 reads for n images, each resized from its own (h, w) to its own (oh, ow): per image one descriptor row
+    (int64: h, w, oh, ow, first row of its x tables in `bounds` or -1 for a skipped pass, first weight, ksize, the same three for y, byte
+    offset of its share of the intermediate buffer) and the images' resample_tables concatenated -- bounds int32 [rows, 2], weights int32
+    flat, `ksize` per image.  Host arrays; `.to(device)` uploads them once."""
+    COLS = 11
+
+    def __init__(self, sizes_hw, out_hw, cache=None):
+        assert len(sizes_hw) == len(out_hw) and len(sizes_hw) > 0
+        cache = {} if cache is None else cache
+        desc = np.zeros((len(sizes_hw), self.COLS), dtype=np.int64)
+        bounds, weights, rows, nk, tmp = [], [], 0, 0, 0
+        for i, ((h, w), (oh, ow)) in enumerate(zip(sizes_hw, out_hw)):
+            h, w, oh, ow = int(h), int(w), int(oh), int(ow)
+            assert min(h, w, oh, ow) > 0
+            desc[i, :4] = (h, w, oh, ow)
+            for col, (a, b) in ((4, (w, ow)), (7, (h, oh))):
+                if a == b:
+                    desc[i, col:col + 3] = (-1, 0, 0)
+                    continue
+                if (a, b) not in cache:
+                    cache[(a, b)] = resample_tables(a, b)
+                bd, kk = cache[(a, b)]
+                assert bd[:, 0].min() >= 0 and bd[:, 1].min() >= 0 and (bd[:, 0] + bd[:, 1]).max() <= a and bd[:, 1].max() <= kk.shape[1]
+                desc[i, col:col + 3] = (rows, nk, kk.shape[1])
+                bounds.append(bd)
+                weights.append(kk.reshape(-1))
+                rows += bd.shape[0]
+                nk += kk.size
+            desc[i, 10] = tmp
+            if ow != w:
+                tmp += -(-h * ow * 3 // 16) * 16
+        self.n = len(sizes_hw)
+        self.desc = desc
+        self.bounds = np.concatenate(bounds) if bounds else np.zeros((1, 2), dtype=np.int32)
+        self.weights = np.concatenate(weights) if weights else np.zeros((1,), dtype=np.int32)
+        self.tmp_bytes = max(tmp, 16)
+        self.max_h = int(desc[desc[:, 4] >= 0, 0].max()) if (desc[:, 4] >= 0).any() else 0          # rows of the widest h-pass grid
+        self.max_ow = int(desc[:, 3].max())
+        self.max_oh = int(desc[:, 2].max())
+        self.dev = None
+
+    def to(self, device):
+        if self.dev is None or self.dev[0].device != torch.device(device):
+            self.dev = tuple(torch.from_numpy(a).to(device) for a in (self.desc, self.bounds, self.weights))
+        return self
 
 
 def _as_u8_hwc(image):

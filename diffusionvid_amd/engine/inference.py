@@ -408,7 +408,7 @@ def write_coco_results(predictions, path, label_map=None):
     return res
 
 
-def inference_images(model, loader, output_folder=None, label_map=None, annotations=None, eval_device=None):
+def inference_images(model, loader, output_folder=None, label_map=None, annotations=None, eval_device=None, bbox_aug=None):
     """Still images: `loader` yields (images, image_ids, original (w, h) per image) batches (data/datasets/still.py: batches, or a DataLoader
     over StillImageDataset with OrientationBatchSampler and collate_images); every batch goes through model.detect_images with its ids
     -- so an image's draws, and with them its detections, do not depend on its batch -- and every BoxList is mapped back to the image's
@@ -418,8 +418,14 @@ def inference_images(model, loader, output_folder=None, label_map=None, annotati
     protocol (coco_eval.do_coco_evaluation; `coco_eval.txt` in `output_folder`) -> (predictions, the ordered dict of the twelve
     numbers); `label_map` then defaults to the annotations' label -> category id map, and a prediction for an image that the
     annotations do not list is an error that names the id.  eval_device: a torch.device runs the evaluator's matching there; None keeps
-    it in numpy."""
+    it in numpy.
+    bbox_aug (None: the model's TEST.BBOX_AUG.ENABLED, as the reference's inference(bbox_aug=...) is called): the batches are lists of
+    uint8 images at their native size (still.batches(..., raw=True), collate_raw) and go to model.detect_images_aug, whose BoxLists are in
+    the plain test transform's size; everything behind it is the same."""
     import os
+    if bbox_aug is None:
+        bbox_aug = bool(getattr(getattr(getattr(getattr(model, "cfg", None), "TEST", None), "BBOX_AUG", None), "ENABLED", False))
+    detect = model.detect_images_aug if bbox_aug else model.detect_images
     ann = None
     if annotations is not None:
         from ..data.evaluation import coco_eval
@@ -430,7 +436,7 @@ def inference_images(model, loader, output_folder=None, label_map=None, annotati
     cpu = torch.device("cpu")
     with torch.no_grad():
         for images, image_ids, sizes in loader:
-            out = model.detect_images(images, image_ids)
+            out = detect(images, image_ids)
             for bl, image_id, size in zip(out, image_ids, sizes):
                 if int(image_id) in predictions:
                     raise ValueError("image id %d appears twice" % int(image_id))

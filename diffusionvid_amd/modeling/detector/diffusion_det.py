@@ -20,6 +20,7 @@ import os
 import time
 from collections import deque
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -202,6 +203,9 @@ class DiffusionDet(nn.Module):
             raise NotImplementedError(
                 "SAMPLE_STEP %d with NUM_PROPOSALS %d gives the NMS %d candidates per frame: the limit is %d = max(1, SAMPLE_STEP - 1) * NUM_PROPOSALS"
                 % (d.SAMPLE_STEP, d.NUM_PROPOSALS, candidates, ops.NMS_MAX_CANDIDATES))
+        if cfg.TEST.BBOX_AUG.ENABLED:          # the views' candidates all enter one NMS per image (detect_images_aug)
+            from ...data.transforms import bbox_aug_check
+            bbox_aug_check(cfg, d.NUM_PROPOSALS, d.SAMPLE_STEP, ops.NMS_MAX_CANDIDATES)
         if not 1 <= d.NUM_CLASSES <= ops.MAX_CLASSES:
             raise NotImplementedError("NUM_CLASSES %d: the limit is 1 <= NUM_CLASSES <= %d (DVID_MAX_CLASSES)" % (d.NUM_CLASSES, ops.MAX_CLASSES))
         self.ddim_sampling_eta = 1.0
@@ -406,31 +410,49 @@ class DiffusionDet(nn.Module):
                 return self._detect_images(imgs.tensors, sizes_wh, ids, result_cls)
         return self._detect_images(imgs.tensors, sizes_wh, ids, result_cls)
 
-    def _still_draws(self, kind, ids, step):
-        """[n, M, 4]: the draw of every image of the batch, keyed by its id; an injected noise_fn draws on the host and ONE tensor is uploaded"""
+    def _still_draws(self, kind, ids, step, views=(0,)):
+        """[n * len(views), M, 4]: the draw of every image of the batch, keyed by its id and -- in the key's `image` slot -- its view (0 for
+        a plain still image), image-major; an injected noise_fn draws on the host and ONE tensor is uploaded"""
         shape = (self.num_proposals, 4)
-        if getattr(self.noise_fn, "on_device", False):
-            return self.noise_fn.draw_ids(kind, ids, step, shape, self.device)          # one launch for consecutive ids
+        if getattr(self.noise_fn, "on_device", False):          # per view one launch for consecutive ids: keys a fixed stride apart
+            per_view = [self.noise_fn.draw_ids(kind, ids, step, shape, self.device, image=v) for v in views]
+            return per_view[0] if len(views) == 1 else torch.stack(per_view, dim=1).reshape((-1,) + shape)
         if self.noise_fn is not None:
-            return torch.stack([self.noise_fn(kind, i, step, 0, shape) for i in ids]).to(self.device, torch.float32)
-        return torch.randn((len(ids),) + shape, device=self.device)
+            return torch.stack([self.noise_fn(kind, i, step, v, shape) for i in ids for v in views]).to(self.device, torch.float32)
+        return torch.randn((len(ids) * len(views),) + shape, device=self.device)
+
+    def _still_uploads(self, sizes_wh, ids, views=(0,)):
+        """the size table and every draw of one launch sequence of still images (slots: image-major, then `views`), on the device"""
+        up = {"sizes": ops.FrameSizes(torch.tensor(sizes_wh, dtype=torch.float32), self.device), "ids": ids}
+        if self.sampling_timesteps == 1:
+            up["box_init"] = self._still_draws("box_init", ids, 0, views)
+        else:
+            up["draws"] = {"img": self._still_draws("img", ids, 0, views)}
+            for step, (_, time_next) in enumerate(self._time_pairs()):
+                if time_next >= 0:
+                    up["draws"][step] = (self._still_draws("ddim", ids, step, views), self._still_draws("renew", ids, step, views))
+        return up
 
     def _detect_images(self, canvas, sizes_wh, ids, result_cls):
+        # every upload of the call -- the size table, the frames of a host-side loader, the draws -- BEFORE any kernel is queued (the rule
+        # of _extract: a host->device copy from pageable memory blocks the host until the stream has drained)
+        up = self._still_uploads(sizes_wh, ids)
+        canvas = canvas.to(self.device, torch.float32).contiguous()
+        cap = max(1, int(self.still_chunk or self.infer_batch * self.lookahead))
+        outs = self._still_launches(canvas, up)
+        results = []          # the host reads the counts only behind the last chunk's launches
+        for k, out in enumerate(outs):
+            results += self._to_boxlists(*out, sizes_wh[k * cap:(k + 1) * cap], result_cls=result_cls)
+        return results
+
+    def _still_launches(self, canvas, up):
+        """the launch sequences of one canvas of still images: -> per chunk of `still_chunk` slots the detection buffers (boxes, scores,
+        labels, counts) of postproc_topk_nms.  Queues kernels only."""
         eng = self._get_engine()
         n, M = canvas.shape[0], self.num_proposals
         H, W = canvas.shape[-2:]
         pairs = self._time_pairs()
-        # every upload of the call -- the size table, the frames of a host-side loader, the draws -- BEFORE any kernel is queued (the rule
-        # of _extract: a host->device copy from pageable memory blocks the host until the stream has drained)
-        sizes = ops.FrameSizes(torch.tensor(sizes_wh, dtype=torch.float32), self.device)
-        canvas = canvas.to(self.device, torch.float32).contiguous()
-        if self.sampling_timesteps == 1:
-            box_init = self._still_draws("box_init", ids, 0)
-        else:
-            draws = {"img": self._still_draws("img", ids, 0)}
-            for step, (_, time_next) in enumerate(pairs):
-                if time_next >= 0:
-                    draws[step] = (self._still_draws("ddim", ids, step), self._still_draws("renew", ids, step))
+        sizes, ids, box_init, draws = up["sizes"], up["ids"], up.get("box_init"), up.get("draws")
         cap = max(1, int(self.still_chunk or self.infer_batch * self.lookahead))
         eng.reserve(min(cap, n), H, W, M)
         outs = []
@@ -446,11 +468,97 @@ class DiffusionDet(nn.Module):
                 outs.append(ops.postproc_topk_nms(logits, boxes, fs, None, 0.5, self.use_nms))
             else:
                 chunk = {k: (v[a:b] if k == "img" else (v[0][a:b], v[1][a:b])) for k, v in draws.items()}
-                outs.append(self._ddim_ensemble(feats, fs, b - a, ids[a], pairs, fs, None, chunk, skip_last=True))
-        results = []          # the host reads the counts only behind the last chunk's launches
-        for k, out in enumerate(outs):
-            results += self._to_boxlists(*out, sizes_wh[k * cap:(k + 1) * cap], result_cls=result_cls)
-        return results
+                outs.append(self._ddim_ensemble(feats, fs, b - a, ids[0], pairs, fs, None, chunk, skip_last=True))          # (the id is not read: the draws are made)
+        return outs
+
+    # ---- still images with TEST.BBOX_AUG -------------------------------------------------------------------------------------------------
+    def detect_images_aug(self, images, image_ids=None):
+        """TEST.BBOX_AUG (mega_core/engine/bbox_aug.py: im_detect_bbox_aug): every image detected in flipped and rescaled views, the views'
+        detections merged -> one BoxList per image in VIEW 0's (w, h) -- the size the plain test transform gives it -- with `scores` and
+        `labels` as detect_images returns them.
+
+        images: a list of uint8 [h, w, 3] RGB images at their native size (host or device tensors, numpy arrays, PIL images): what the
+        reference's BBoxAugCollator hands over.  The views (data/transforms.bbox_aug_views) are built on the device from the uint8 source,
+        per scale group in two launches (ops.resize_views_u8: Pillow's bits, the mirror one more store); every scale group is one launch
+        sequence of detect_images on a canvas of image 0's view(s), image 1's view(s), ... as large as the group's largest view rounded up
+        to 32; the per-view detections are mapped into view 0 with BoxList's arithmetic and packed (ops.bbox_aug_merge), and one class-aware
+        NMS at MODEL.ROI_HEADS.NMS, clipped to view 0, and the cut to MODEL.ROI_HEADS.DETECTIONS_PER_IMG finish (ops.bbox_aug_finish).
+        View v of image id i draws noise_fn(kind, i, step, v, (M, 4)): view 0 draws what detect_images draws.  filter_results' score threshold
+        is not applied (the detector's own post-processing has run), nothing is re-scored or box-voted.  Reads and writes no video state;
+        never replayed from a hipGraph."""
+        if self.training:
+            raise NotImplementedError("training is out of scope of the MI355X inference path")
+        vid = self.cfg.MODEL.VID
+        if vid.MEGA.GLOBAL.ENABLE:
+            raise NotImplementedError("detect_images_aug: MODEL.VID.MEGA.GLOBAL.ENABLE is True, and a still image has no global memory to condition on")
+        if vid.ROI_BOX_HEAD.ATTENTION.ENABLE:
+            raise NotImplementedError("detect_images_aug: MODEL.VID.ROI_BOX_HEAD.ATTENTION.ENABLE is True, and a still image has no local memory to condition on")
+        if self.num_heads_local > 0:
+            raise NotImplementedError("detect_images_aug: MODEL.DiffusionDet.NUM_HEADS_LOCAL is %d: the conditioned heads have nothing to be conditioned on "
+                                      "(still images need NUM_HEADS_LOCAL 0)" % self.num_heads_local)
+        if not self.cfg.TEST.BBOX_AUG.ENABLED:
+            raise NotImplementedError("detect_images_aug: TEST.BBOX_AUG.ENABLED is False (detect_images is the plain path)")
+        images = list(images)
+        ids = list(range(len(images))) if image_ids is None else [int(i) for i in image_ids]
+        if len(ids) != len(images):
+            raise ValueError("detect_images_aug: %d image_ids for %d images" % (len(ids), len(images)))
+        if not images:
+            return []
+        if self.device.type == "cuda" and self.device.index is not None:
+            with torch.cuda.device(self.device):
+                return self._detect_images_aug(images, ids)
+        return self._detect_images_aug(images, ids)
+
+    def _detect_images_aug(self, images, ids):
+        from ...data import transforms as T
+        result_cls = self.boxlist_cls or BoxList
+        n, div = len(images), self.size_divisibility
+        # every upload of the call first (the rule of _detect_images): the images, their pointer table, per scale group the resample plan,
+        # the size table and the draws, then the merge's table and view 0's sizes
+        dev_images = []
+        for im in images:
+            if not isinstance(im, (torch.Tensor, np.ndarray)):
+                im = np.array(im.convert("RGB"))          # a PIL image (a writable copy)
+            if im.dtype not in (torch.uint8, np.uint8) or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("detect_images_aug takes uint8 [h, w, 3] images, got %s %s" % (im.dtype, tuple(im.shape)))
+            if isinstance(im, np.ndarray):
+                im = torch.from_numpy(np.ascontiguousarray(im))
+            dev_images.append(im.to(self.device).contiguous())
+        srcs = ops.ImageTable(dev_images)
+        views = [T.bbox_aug_views(self.cfg, (w, h)) for h, w in srcs.sizes_hw]
+        V = len(views[0])
+        if not hasattr(self, "_aug_tables"):
+            self._aug_tables = {}          # resample tables by (in, out) size: a dataset repeats its sizes
+        groups, v0 = [], 0
+        for g, (_, _, nv) in enumerate(T.bbox_aug_scales(self.cfg)):
+            out_hw = [(vs[v0].h, vs[v0].w) for vs in views]
+            plan = T.ViewsPlan(srcs.sizes_hw, out_hw, cache=self._aug_tables).to(self.device)
+            PH, PW = -(-plan.max_oh // div) * div, -(-plan.max_ow // div) * div
+            sizes_wh = [(ow, oh) for oh, ow in out_hw for _ in range(nv)]
+            groups.append((plan, PH, PW, nv, self._still_uploads(sizes_wh, ids, tuple(range(v0, v0 + nv)))))
+            v0 += nv
+        if len(self._aug_tables) > 4096:
+            self._aug_tables.clear()
+        table = ops.bbox_aug_table(views).to(self.device)
+        sizes0_wh = [(vs[0].w, vs[0].h) for vs in views]
+        sizes0 = ops.FrameSizes(torch.tensor(sizes0_wh, dtype=torch.float32), self.device)
+        # launches only from here on
+        per_group = []
+        for plan, PH, PW, nv, up in groups:
+            canvas = ops.resize_views_u8(srcs, plan, PH, PW, nv == 2)
+            outs = self._still_launches(canvas, up)
+            ob, osc, ol, oc = (outs[0] if len(outs) == 1 else [torch.cat([o[k] for o in outs]) for k in range(4)])
+            cap = osc.shape[1]
+            per_group.append((ob.reshape(n, nv, cap, 4), osc.reshape(n, nv, cap), ol.reshape(n, nv, cap), oc.reshape(n, nv)))
+        if len(per_group) == 1:
+            ob, osc, ol, oc = per_group[0]
+        else:
+            ob, osc, ol, oc = (torch.cat([g[k] for g in per_group], dim=1) for k in range(4))
+        cap = osc.shape[2]
+        cand = ops.bbox_aug_merge(ob.reshape(n * V, cap, 4), osc.reshape(n * V, cap), ol.reshape(n * V, cap), oc.reshape(n * V), table, V)
+        heads = self.cfg.MODEL.ROI_HEADS
+        out = ops.bbox_aug_finish(*cand, sizes0, float(heads.NMS), int(heads.DETECTIONS_PER_IMG))
+        return self._to_boxlists(*out, sizes0_wh, result_cls=result_cls)
 
     def _reset_video(self):
         self._ahead = {}

@@ -319,6 +319,86 @@ def resize_u8_to_f32(src_hwc, oh, ow, ph, pw, xtab, ytab):
     return out
 
 
+class ImageTable:
+    """The pointer table of n uint8 [h_i, w_i, 3] device images (kept alive here), uploaded once: what resize_views_u8 reads its sources through"""
+
+    def __init__(self, images):
+        self.images = [_cuda(t, torch.uint8) for t in images]
+        if not self.images or any(t.dim() != 3 or t.shape[2] != 3 for t in self.images):
+            raise _lib.DvidError("ImageTable takes a non-empty list of uint8 [h, w, 3] images")
+        self.sizes_hw = [(int(t.shape[0]), int(t.shape[1])) for t in self.images]
+        self.dev = torch.tensor([t.data_ptr() for t in self.images], dtype=torch.int64).to(self.images[0].device)
+
+    def __len__(self):
+        return len(self.images)
+
+
+def resize_views_u8(srcs, plan, PH, PW, flip):
+    """n uint8 [h_i, w_i, 3] device images (a list, or an ImageTable made before the call) -> fp32 [n * (1 + flip), 3, PH, PW] in [0, 1]:
+    slot i * (1 + flip) is image i resized Pillow-identically to its (oh_i, ow_i) of `plan` (data/transforms.ViewsPlan), zero outside; with
+    `flip` the next slot is its mirror inside its own ow_i columns.  Two launches however many images (dvid_resize_views_u8)."""
+    table = srcs if isinstance(srcs, ImageTable) else ImageTable(srcs)
+    if len(table) != plan.n or any(hw != (int(d[0]), int(d[1])) for hw, d in zip(table.sizes_hw, plan.desc)):
+        raise _lib.DvidError(f"resize_views_u8: the plan describes {plan.n} images of other sizes than the {len(table)} sources")
+    dev = table.dev.device
+    desc, bounds, weights = plan.to(dev).dev
+    flip = 1 if flip else 0
+    out = torch.empty((plan.n * (1 + flip), 3, int(PH), int(PW)), dtype=torch.float32, device=dev)
+    tmp = torch.empty((plan.tmp_bytes,), dtype=torch.uint8, device=dev)
+    host = torch.from_numpy(plan.desc)
+    call("dvid_resize_views_u8", ptr(table.dev), plan.n, ptr(desc), ptr(host), ptr(bounds), bounds.shape[0], ptr(weights), weights.numel(), ptr(tmp),
+         tmp.numel(), ptr(out), int(PH), int(PW), flip, stream_ptr())
+    return out
+
+
+def bbox_aug_table(views_per_image):
+    """fp32 [n * V, 5] rows (w_v, h_v, flip, rw, rh) of bbox_aug_merge from every image's data/transforms.bbox_aug_views: the multipliers
+    are the Python doubles w_0 / w_v and h_0 / h_v rounded to fp32, as BoxList.resize's scalar multiplication rounds them"""
+    rows = []
+    for views in views_per_image:
+        w0, h0 = views[0].w, views[0].h
+        rows += [(v.w, v.h, 1.0 if v.flip else 0.0, float(w0) / float(v.w), float(h0) / float(v.h)) for v in views]
+    return torch.tensor(rows, dtype=torch.float64).to(torch.float32)
+
+
+def bbox_aug_merge(boxes, scores, labels, counts, table, views):
+    """The per-view detections of n images -- boxes [n * V, cap, 4], scores, labels int32 [n * V, cap], counts int32 [n * V], slot
+    i * V + v -- mapped into view 0's frame (BoxList.transpose / resize in fp32) -> (cand_boxes [n, V * cap, 4], cand_scores, cand_labels
+    int32, live int32 [n]): what nms_frames_tiled takes, live rows first, the padding rows of engine.inference.seq_nms_boxlists behind."""
+    boxes, scores = _cuda(boxes, torch.float32), _cuda(scores, torch.float32)
+    labels, counts, table = _cuda(labels, torch.int32), _cuda(counts, torch.int32), _cuda(table, torch.float32)
+    V = int(views)
+    slots, cap = scores.shape
+    if V < 1 or slots % V or slots == 0 or cap == 0:
+        raise _lib.DvidError(f"bbox_aug_merge: {slots} slots of {cap} rows do not split into images of {V} views")
+    n = slots // V
+    if boxes.shape != (slots, cap, 4) or labels.shape != (slots, cap) or counts.shape != (slots,) or table.shape != (slots, 5):
+        raise _lib.DvidError("bbox_aug_merge: boxes [n * V, cap, 4], scores / labels [n * V, cap], counts [n * V] and table [n * V, 5] must agree")
+    dev = boxes.device
+    cb = torch.empty((n, V * cap, 4), dtype=torch.float32, device=dev)
+    cs = torch.empty((n, V * cap), dtype=torch.float32, device=dev)
+    cl = torch.empty((n, V * cap), dtype=torch.int32, device=dev)
+    live = torch.empty((n,), dtype=torch.int32, device=dev)
+    call("dvid_bbox_aug_merge", ptr(boxes), ptr(scores), ptr(labels), ptr(counts), ptr(table), n, V, cap, ptr(cb), ptr(cs), ptr(cl), ptr(live),
+         stream_ptr())
+    return cb, cs, cl, live
+
+
+def bbox_aug_finish(cand_boxes, cand_scores, cand_labels, live, sizes, iou, max_det):
+    """Behind bbox_aug_merge: the class-aware NMS at `iou`, clipped to view 0 (`sizes`), minus the padding rows, cut as filter_results
+    cuts (more than max_det > 0 survivors: those scoring >= the max_det-th; survivors are in score order, so a prefix) -> (boxes, scores,
+    labels, counts) as postproc_topk_nms returns them, the counts rewritten in place."""
+    N = cand_scores.shape[1]
+    ob, osc, ol, oc = nms_frames_tiled(cand_boxes, cand_scores, cand_labels, sizes, None, iou, True)
+    kept = oc - (N - live)
+    K = int(max_det)
+    if 0 < K < N:
+        cut = ((osc >= osc[:, K - 1:K]) & (torch.arange(N, device=osc.device)[None, :] < kept[:, None])).sum(dim=1).to(torch.int32)
+        kept = torch.where(kept > K, cut, kept)
+    oc.copy_(kept)
+    return ob, osc, ol, oc
+
+
 class FrameSizes:
     """The per-frame size table of the `_sizes` entry points, checked once on the host and uploaded once: rows (w, h) fp32 [n, 2], every
     entry positive and finite.  `fs[a:b]` is the table of frames a..b (views of both copies, nothing checked or uploaded again)."""

@@ -259,8 +259,9 @@ class DeviceNoise:
         from .. import ops
         return ops.counter_normal(self.key(kind, frame_id, step, first_image), n_images, shape, device)
 
-    def draw_ids(self, kind, ids, step, shape, device=None):
-        """[len(ids), *shape]: the draws keyed (kind, id, step, image 0) of a batch of still images -- ONE launch when the ids are
+    def draw_ids(self, kind, ids, step, shape, device=None, image=0):
+        """[len(ids), *shape]: the draws keyed (kind, id, step, `image`) of a batch of still images (`image`: the view index under
+        TEST.BBOX_AUG, 0 for the plain image) -- ONE launch when the ids are
         consecutive (their keys lie a fixed stride apart), else one per run of consecutive ids"""
         import torch
         from .. import ops
@@ -269,7 +270,7 @@ class DeviceNoise:
         runs, a = [], 0
         for b in range(1, len(ids) + 1):
             if b == len(ids) or ids[b] != ids[b - 1] + 1:
-                runs.append(ops.counter_normal(self.key(kind, ids[a], step, 0), b - a, shape, device, key_stride=stride))
+                runs.append(ops.counter_normal(self.key(kind, ids[a], step, image), b - a, shape, device, key_stride=stride))
                 a = b
         return runs[0] if len(runs) == 1 else torch.cat(runs)
 

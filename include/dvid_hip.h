@@ -464,6 +464,29 @@ int dvid_f32_to_f16(const float* x, void* y, int64_t n, void* stream);
 int dvid_resize_u8_to_f32(const void* src_hwc, int h, int w, void* tmp, float* out_chw, int oh, int ow, int ph, int pw,
                           const int* xbounds, const int* xk, int xksize, const int* ybounds, const int* yk, int yksize, void* stream);
 
+/* The views of TEST.BBOX_AUG (dvid_version >= 7; csrc/resize.hip): n uint8 images, each with its own size, resized as
+ * dvid_resize_u8_to_f32 resizes one -- the same two integer passes, the same bits -- onto one canvas in two launches however many images.
+ * srcs: DEVICE table of n pointers to uint8 [h_i][w_i][3]; plan (device) and plan_host (the same rows on the host, checked before
+ * anything is launched): int64 [n][11] = h, w, oh, ow, then for x and for y the first row of the image's tables in `bounds`
+ * (-1 exactly when that axis keeps its size), its first entry in `weights` and its ksize, and the byte offset of its h * ow * 3
+ * intermediate bytes in `tmp`; bounds int32 [n_bound_rows][2] and weights int32 [n_weights]: the images' resample tables concatenated.
+ * -> out fp32 [n * (1 + flip)][3][ph][pw] in [0, 1]: slot i * (1 + flip) holds image i, zero outside [oh_i, ow_i]; with flip the next
+ * slot holds its mirror inside its own ow_i columns, out[y][x] = resized[y][ow_i - 1 - x] (Resize, then RandomHorizontalFlip(1.0)). */
+int dvid_resize_views_u8(const void* const* srcs, int n, const long long* plan, const long long* plan_host, const int* bounds,
+                         int64_t n_bound_rows, const int* weights, int64_t n_weights, void* tmp, int64_t tmp_bytes, float* out, int ph, int pw,
+                         int flip, void* stream);
+/* The merge of TEST.BBOX_AUG (dvid_version >= 7; csrc/bboxaug.hip; mega_core/engine/bbox_aug.py): the detections of `views` views of
+ * each of n images -- boxes [n * views][cap][4], scores, labels (int32) [n * views][cap], counts [n * views], slot i * views + v, as
+ * dvid_postproc_topk_nms leaves them -- mapped into view 0's frame and packed as the candidates of dvid_nms_frames_tiled_sizes:
+ * cand_* [n][views * cap], live rows first in (view, row) order, behind them padding rows (a zero-area box at the origin, score
+ * FLT_MIN, label 1), live [n] the number of live rows.  table fp32 [n * views][5] = w_v, h_v, flip (0 / 1), rw, rh: a mirrored view
+ * takes x1' = w_v - x2 - 1, x2' = w_v - x1 - 1, then x is multiplied by rw = fp32(w_0 / w_v) and y by rh, one fp32 operation at a time
+ * (BoxList.transpose / resize); view 0 is copied.  views <= DVID_BBOX_AUG_MAX_VIEWS, views * cap <= DVID_NMS_MAX_CANDIDATES
+ * (DVID_ERR_UNSUPPORTED beyond); the box arrays 16-byte aligned. */
+#define DVID_BBOX_AUG_MAX_VIEWS 64
+int dvid_bbox_aug_merge(const float* boxes, const float* scores, const int* labels, const int* counts, const float* table, int n, int views,
+                        int cap, float* cand_boxes, float* cand_scores, int* cand_labels, int* live, void* stream);
+
 /* ---- options ------------------------------------------------------------------------------
  * The library's behaviour switches are ONE table set through this ABI, never through the environment (csrc/options.h; the defaults
  * are the benchmarked configuration).  Names: conv3x3, wstat, bneck_fuse (0 off / 1 by the layer's shape rule / 2 wherever the layer
