@@ -88,6 +88,7 @@ SIGNATURES = {
     "dvid_vid_eval_match": (c_int, [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 4 + [c_int, c_int] + [c_void_p] * 3 + [c_int, c_float, c_int] +
                             [c_void_p] * 7),
     "dvid_coco_eval_match": (c_int, [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 8 + [c_int] + [c_void_p] * 5),
+    "dvid_lvis_eval_match": (c_int, [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 14 + [c_int] + [c_void_p] * 5),
     "dvid_cdist":(c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "dvid_fps_greedy": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dvid_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

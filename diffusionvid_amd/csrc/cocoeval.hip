@@ -16,8 +16,7 @@
 // as the protocol writes them (`iou < best` skips), so a NaN takes the same branch.  Precondition: the scores are finite.
 #include "../../include/dvid_hip.h"
 #include "kernels.h"
-
-typedef unsigned long long u64;
+#include "evalkey.h"          // u64, ce_score_desc, coco_iou: shared with lviseval.hip
 
 #define CE_THREADS 256
 #define CE_PAD (~(u64)0)
@@ -32,27 +31,8 @@ struct CocoEvalParams {
 };
 
 // key: label (bits 44..), the score's bits mapped so that a greater score is a smaller number (bits 12..43), the row (bits 0..11)
-__device__ __forceinline__ unsigned ce_score_desc(float s) {
-    if (s == 0.f) s = 0.f;          // -0 and +0 are one score
-    const unsigned b = __float_as_uint(s);
-    return ~(b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u));
-}
 __device__ __forceinline__ int ce_label(u64 key) { return (int)(key >> 44); }
 __device__ __forceinline__ int ce_row(u64 key) { return (int)(key & 0xfff); }
-
-// d, g: x, y, w, h
-__device__ __forceinline__ double coco_iou(const double dx, const double dy, const double dw, const double dh, const double* __restrict__ g,
-                                           const bool crowd) {
-#pragma clang fp contract(off)
-    const double w = fmin(dx + dw, g[0] + g[2]) - fmax(dx, g[0]);
-    if (w <= 0.0) return 0.0;
-    const double h = fmin(dy + dh, g[1] + g[3]) - fmax(dy, g[1]);
-    if (h <= 0.0) return 0.0;
-    const double i = w * h;
-    const double da = dw * dh, ga = g[2] * g[3];
-    const double u = crowd ? da : (da + ga) - i;
-    return __ddiv_rn(i, u);
-}
 
 __global__ __launch_bounds__(CE_THREADS) void coco_eval_match_kernel(const float* __restrict__ dets, const int* __restrict__ counts, int N, int cap, int P,
                                                                      const double* __restrict__ gt_boxes, const double* __restrict__ gt_areas,

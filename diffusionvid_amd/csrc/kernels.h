@@ -227,6 +227,14 @@ int dvid_coco_eval_match_launch(const float* dets, const int* counts, int n_imag
                                 const double* area_ranges, int num_classes, signed char* match, signed char* ignore, int* rank, int* npig,
                                 hipStream_t s);
 
+// lviseval.hip: the LVIS (federated) bbox evaluator's matching, a workgroup per image; max_gt is the greatest box count of one image, read
+// from the host's gt_starts; iou_thrs / area_ranges are host tables (include/dvid_hip.h)
+int dvid_lvis_eval_match_launch(const float* dets, const int* counts, int n_images, int cap, const double* gt_boxes, const double* gt_areas,
+                                const unsigned char* gt_ignore, const int* gt_labels, const int* gt_starts, int max_gt, const int* neg_starts,
+                                const int* neg_labels, const int* nex_starts, const int* nex_labels, const double* iou_thrs,
+                                const double* area_ranges, int num_classes, signed char* match, signed char* ignore, int* rank, int* npig,
+                                hipStream_t s);
+
 // fps.hip
 int dvid_cdist_launch(const float* x, int n, int d, float* dist, hipStream_t s);
 int dvid_fps_launch(const float* dist, int n, int m, int bs_emul, int* idx, hipStream_t s);

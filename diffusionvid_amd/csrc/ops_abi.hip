@@ -340,6 +340,51 @@ int dvid_coco_eval_match(const float* dets, const int* counts, int n_images, int
     return DVID_OK;
 }
 
+// a CSR table of per-image label lists: starts at 0 and never decreases
+static const char* lvis_list_fault(const int* starts, int n_images, int* at) {
+    if (starts[0] != 0) return *at = 0, "does not start at 0";
+    for (int f = 0; f < n_images; ++f)
+        if (starts[f + 1] < starts[f]) return *at = f, "decreases";
+    return nullptr;
+}
+
+int dvid_lvis_eval_match(const float* dets, const int* counts, int n_images, int cap, const double* gt_boxes, const double* gt_areas,
+                         const unsigned char* gt_ignore, const int* gt_labels, const int* gt_starts, const int* gt_starts_host,
+                         const int* neg_starts, const int* neg_labels, const int* neg_starts_host, const int* nex_starts, const int* nex_labels,
+                         const int* nex_starts_host, const double* iou_thrs, const double* area_ranges, int num_classes, signed char* match,
+                         signed char* ignore, int* rank, int* npig, void* stream) {
+    g_err[0] = 0;
+    if (!dets || !counts || !gt_starts || !gt_starts_host || !neg_starts || !neg_starts_host || !nex_starts || !nex_starts_host || !iou_thrs ||
+        !area_ranges || !match || !ignore || !rank || !npig)
+        FAIL(DVID_ERR_ARG, "LVIS evaluation: null pointer");
+    if (n_images < 0 || cap < 1 || num_classes < 1)
+        FAIL(DVID_ERR_ARG, "LVIS evaluation: bad sizes (%d images, %d rows per image, %d classes)", n_images, cap, num_classes);
+    if (cap > DVID_NMS_MAX_CANDIDATES)
+        FAIL(DVID_ERR_UNSUPPORTED, "LVIS evaluation: %d rows per image exceed the limit of %d (DVID_NMS_MAX_CANDIDATES)", cap, DVID_NMS_MAX_CANDIDATES);
+    if (num_classes > DVID_MAX_CLASSES)
+        FAIL(DVID_ERR_UNSUPPORTED, "LVIS evaluation: %d classes exceed the limit of %d (DVID_MAX_CLASSES)", num_classes, DVID_MAX_CLASSES);
+    if (gt_starts_host[0] != 0) FAIL(DVID_ERR_ARG, "LVIS evaluation: gt_starts[0] is %d, not 0", gt_starts_host[0]);
+    int max_gt = 0;
+    for (int f = 0; f < n_images; ++f) {
+        const int g = gt_starts_host[f + 1] - gt_starts_host[f];
+        if (g < 0) FAIL(DVID_ERR_ARG, "LVIS evaluation: gt_starts decreases at image %d", f);
+        if (g > DVID_LVIS_EVAL_MAX_GT)
+            FAIL(DVID_ERR_UNSUPPORTED, "LVIS evaluation: image %d holds %d ground-truth boxes, the limit is %d (DVID_LVIS_EVAL_MAX_GT)", f, g,
+                 DVID_LVIS_EVAL_MAX_GT);
+        max_gt = g > max_gt ? g : max_gt;
+    }
+    int at = 0;
+    if (const char* what = lvis_list_fault(neg_starts_host, n_images, &at)) FAIL(DVID_ERR_ARG, "LVIS evaluation: neg_starts %s (image %d)", what, at);
+    if (const char* what = lvis_list_fault(nex_starts_host, n_images, &at)) FAIL(DVID_ERR_ARG, "LVIS evaluation: nex_starts %s (image %d)", what, at);
+    if (gt_starts_host[n_images] > 0 && (!gt_boxes || !gt_areas || !gt_ignore || !gt_labels)) FAIL(DVID_ERR_ARG, "LVIS evaluation: null ground truth");
+    if ((neg_starts_host[n_images] > 0 && !neg_labels) || (nex_starts_host[n_images] > 0 && !nex_labels))
+        FAIL(DVID_ERR_ARG, "LVIS evaluation: null negative or not-exhaustive labels");
+    TRY(dvid_lvis_eval_match_launch(dets, counts, n_images, cap, gt_boxes, gt_areas, gt_ignore, gt_labels, gt_starts, max_gt, neg_starts, neg_labels,
+                                    nex_starts, nex_labels, iou_thrs, area_ranges, num_classes, match, ignore, rank, npig,
+                                    reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
 int dvid_cdist(const float* x, int n, int d, float* dist, void* stream) {
     g_err[0] = 0;
     TRY(dvid_cdist_launch(x, n, d, dist, reinterpret_cast<hipStream_t>(stream)));

@@ -20,7 +20,7 @@ itself, from its published definition:
   summarize    means over the entries > -1
 
 Both paths produce (match, ignore, rank, npig) in one layout and share accumulate_from_matches, so their results are equal, not close.
-Not here: segmentation and keypoint evaluation, LVIS' federated protocol, proposal recall, evaluation spread over ranks."""
+Not here: segmentation and keypoint evaluation, proposal recall, evaluation spread over ranks; LVIS' federated protocol is lvis_eval.py."""
 import json
 import os
 from collections import OrderedDict
@@ -186,10 +186,17 @@ def accumulate_from_matches(scores, labels, counts, rank, match, ignore, npig):
     """accumulate + summarize on the matching's arrays: scores / labels / rank [N, cap] (images in ascending id), counts [N], match and
     ignore [4, 10, N, cap], npig [4, K + 1] -> {"precision" [10, 101, K, 4, 3], "recall" [10, K, 4, 3], "stats": the twelve numbers};
     category k is label k + 1.  float64 throughout."""
+    precision, recall = accumulate_arrays(scores, labels, counts, rank, match, ignore, npig, MAX_DETS)
+    return {"precision": precision, "recall": recall, "stats": summarize(precision, recall)}
+
+
+def accumulate_arrays(scores, labels, counts, rank, match, ignore, npig, max_dets):
+    """accumulate alone, for the protocol's own list of detection limits (lvis_eval has one, 300) -> (precision [10, 101, K, 4, M],
+    recall [10, K, 4, M]), M = len(max_dets)"""
     scores, labels, rank = _np(scores), _np(labels, np.int64), _np(rank)
     match, ignore, npig = _np(match), _np(ignore), _np(npig)
     A, T, N, cap = match.shape
-    K, R, M = npig.shape[1] - 1, len(REC_THRS), len(MAX_DETS)
+    K, R, M = npig.shape[1] - 1, len(REC_THRS), len(max_dets)
     precision, recall = -np.ones((T, R, K, A, M)), -np.ones((T, K, A, M))
     live = (np.arange(cap)[None, :] < _np(counts, np.int64).reshape(-1, 1)) & (rank >= 0)
     fi, ri = np.nonzero(live)
@@ -209,7 +216,7 @@ def accumulate_from_matches(scores, labels, counts, rank, match, ignore, npig):
         if len(counted) == 0:
             continue
         n_gt = np.where(npig[:, k + 1] > 0, npig[:, k + 1], 1).astype(np.float64)[:, None, None]
-        for mi, max_det in enumerate(MAX_DETS):
+        for mi, max_det in enumerate(max_dets):
             sel = b0 + np.nonzero(rk[b0:b1] < max_det)[0]
             sel = sel[np.argsort(-s_all[sel], kind="mergesort")]
             nd = len(sel)
@@ -226,7 +233,7 @@ def accumulate_from_matches(scores, labels, counts, rank, match, ignore, npig):
                 for t in range(T):
                     inds = np.searchsorted(rc[a, t], REC_THRS, side="left")
                     precision[t, :, k, a, mi] = np.where(inds < nd, pr[a, t, np.minimum(inds, nd - 1)], 0.0)
-    return {"precision": precision, "recall": recall, "stats": summarize(precision, recall)}
+    return precision, recall
 
 
 def _mean(s):

@@ -408,7 +408,27 @@ def write_coco_results(predictions, path, label_map=None):
     return res
 
 
-def inference_images(model, loader, output_folder=None, label_map=None, annotations=None, eval_device=None, bbox_aug=None):
+def _still_annotations(annotations, protocol):
+    """-> ("coco" or "lvis", that evaluator's annotations object).  protocol None: LVIS exactly when the file's images carry `neg_category_ids`."""
+    import json
+
+    from ..data.evaluation import coco_eval, lvis_eval
+    if protocol not in (None, "coco", "lvis"):
+        raise ValueError("protocol is 'coco', 'lvis' or None, not %r" % (protocol,))
+    if isinstance(annotations, coco_eval.CocoAnnotations):
+        lvis = isinstance(annotations, lvis_eval.LvisAnnotations)
+        if protocol is not None and lvis != (protocol == "lvis"):
+            raise ValueError("protocol %r with annotations loaded as %s" % (protocol, type(annotations).__name__))
+        return ("lvis" if lvis else "coco"), annotations
+    if not isinstance(annotations, dict):
+        with open(annotations) as f:
+            annotations = json.load(f)
+    if protocol == "lvis" or (protocol is None and lvis_eval.is_lvis(annotations)):
+        return "lvis", lvis_eval.LvisAnnotations(annotations)
+    return "coco", coco_eval.CocoAnnotations(annotations)
+
+
+def inference_images(model, loader, output_folder=None, label_map=None, annotations=None, eval_device=None, bbox_aug=None, protocol=None):
     """Still images: `loader` yields (images, image_ids, original (w, h) per image) batches (data/datasets/still.py: batches, or a DataLoader
     over StillImageDataset with OrientationBatchSampler and collate_images); every batch goes through model.detect_images with its ids
     -- so an image's draws, and with them its detections, do not depend on its batch -- and every BoxList is mapped back to the image's
@@ -419,6 +439,9 @@ def inference_images(model, loader, output_folder=None, label_map=None, annotati
     numbers); `label_map` then defaults to the annotations' label -> category id map, and a prediction for an image that the
     annotations do not list is an error that names the id.  eval_device: a torch.device runs the evaluator's matching there; None keeps
     it in numpy.
+    protocol ("coco", "lvis" or None): None takes the LVIS bbox protocol (lvis_eval.do_lvis_evaluation: the federated protocol, thirteen
+    numbers, `lvis_eval.txt`, and `lvis_results.json` with at most 300 rows per image) exactly when the file's images carry
+    `neg_category_ids`, which a COCO file's never do.
     bbox_aug (None: the model's TEST.BBOX_AUG.ENABLED, as the reference's inference(bbox_aug=...) is called): the batches are lists of
     uint8 images at their native size (still.batches(..., raw=True), collate_raw) and go to model.detect_images_aug, whose BoxLists are in
     the plain test transform's size; everything behind it is the same."""
@@ -428,8 +451,7 @@ def inference_images(model, loader, output_folder=None, label_map=None, annotati
     detect = model.detect_images_aug if bbox_aug else model.detect_images
     ann = None
     if annotations is not None:
-        from ..data.evaluation import coco_eval
-        ann = annotations if isinstance(annotations, coco_eval.CocoAnnotations) else coco_eval.CocoAnnotations(annotations)
+        protocol, ann = _still_annotations(annotations, protocol)
         if label_map is None:
             label_map = ann.category_of
     predictions = {}
@@ -449,4 +471,11 @@ def inference_images(model, loader, output_folder=None, label_map=None, annotati
         write_coco_results(predictions, os.path.join(output_folder, "coco_results.json"), label_map)
     if ann is None:
         return predictions
+    from ..data.evaluation import coco_eval, lvis_eval
+    if protocol == "lvis":
+        if output_folder:
+            import json
+            with open(os.path.join(output_folder, "lvis_results.json"), "w") as f:
+                json.dump(lvis_eval.lvis_results(predictions, label_map), f)
+        return predictions, lvis_eval.do_lvis_evaluation(ann, predictions, output_folder, device=eval_device)
     return predictions, coco_eval.do_coco_evaluation(ann, predictions, output_folder, device=eval_device)

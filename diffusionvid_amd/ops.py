@@ -712,6 +712,51 @@ def coco_eval_match(dets, counts, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_st
     return out
 
 
+LVIS_EVAL_MAX_GT, LVIS_EVAL_MAX_DETS = 1024, 300          # include/dvid_hip.h
+
+
+def lvis_eval_match(dets, counts, gt_boxes, gt_areas, gt_ignore, gt_labels, gt_starts, neg_starts, neg_labels, nex_starts, nex_labels,
+                    num_classes, iou_thrs, area_ranges, out=None):
+    """The LVIS bbox evaluator's matching (lvis_eval.match_numpy, the federated protocol) for the ten IoU thresholds and the four area
+    ranges in one launch (csrc/lviseval.hip).  dets, counts, gt_boxes, gt_areas, gt_labels, gt_starts, iou_thrs, area_ranges and the
+    returned (match, ignore, rank, npig) are coco_eval_match's; gt_ignore [G] uint8 is the annotation's `ignore`; neg_starts [N + 1] int32
+    with neg_labels and nex_starts [N + 1] int32 with nex_labels are the images' negative and not-exhaustive label lists as CSR tables
+    (lvis_eval.pack_groundtruth).  All tensors on the device.  The scores must be finite."""
+    dets, counts = _cuda(dets, torch.float32), _cuda(counts, torch.int32)
+    N, cap = counts.shape[0], dets.shape[1] if dets.dim() == 3 else -1
+    assert dets.shape == (N, cap, 6), "dets is [images, cap, 6]"
+    dev = dets.device
+    A, T = COCO_EVAL_AREAS, COCO_EVAL_THRESHOLDS
+    thr = torch.tensor([float(t) for t in iou_thrs], dtype=torch.float64)
+    rng = torch.tensor([[float(lo), float(hi)] for lo, hi in area_ranges], dtype=torch.float64).reshape(-1, 2)
+    assert thr.shape == (T,) and rng.shape == (A, 2) and num_classes >= 1, "ten thresholds and four area ranges"
+    if out is None:
+        out = (torch.empty((A, T, N, cap), dtype=torch.int8, device=dev), torch.empty((A, T, N, cap), dtype=torch.int8, device=dev),
+               torch.empty((N, cap), dtype=torch.int32, device=dev), torch.zeros((A, num_classes + 1), dtype=torch.int32, device=dev))
+    match, ignore, rank, npig = out
+    assert match.shape == ignore.shape == (A, T, N, cap) and rank.shape == (N, cap) and npig.shape == (A, num_classes + 1), "output shapes"
+    assert (match.dtype, ignore.dtype, rank.dtype, npig.dtype) == (torch.int8, torch.int8, torch.int32, torch.int32), "output dtypes"
+    if N == 0 or cap == 0:
+        npig.zero_()
+        return out
+    gt_boxes, gt_areas = _cuda(gt_boxes, torch.float64).reshape(-1, 4), _cuda(gt_areas, torch.float64)
+    gt_ignore, gt_labels, gt_starts = _cuda(gt_ignore, torch.uint8), _cuda(gt_labels, torch.int32), _cuda(gt_starts, torch.int32)
+    G = gt_boxes.shape[0]
+    assert gt_starts.shape == (N + 1,) and gt_areas.shape == gt_ignore.shape == gt_labels.shape == (G,), "gt_starts is [images + 1]"
+    starts_host = gt_starts.cpu()
+    assert int(starts_host[-1]) == G, "gt_starts ends at the box count"
+    lists = []
+    for name, starts, labels in (("neg", neg_starts, neg_labels), ("nex", nex_starts, nex_labels)):
+        starts, labels = _cuda(starts, torch.int32), _cuda(labels, torch.int32).reshape(-1)
+        assert starts.shape == (N + 1,), "%s_starts is [images + 1]" % name
+        host = starts.cpu()
+        assert int(host[-1]) == labels.shape[0], "%s_starts ends at the length of %s_labels" % (name, name)
+        lists += [starts, labels, host]
+    call("dvid_lvis_eval_match", ptr(dets), ptr(counts), N, cap, ptr(gt_boxes), ptr(gt_areas), ptr(gt_ignore), ptr(gt_labels), ptr(gt_starts),
+         ptr(starts_host), *(ptr(t) for t in lists), ptr(thr), ptr(rng), int(num_classes), *(ptr(_cuda(o)) for o in out), stream_ptr())
+    return out
+
+
 def split_detection_buffer(buf, n, cap):
     """The four post-processing outputs are views of ONE flat fp32 buffer [boxes | scores | labels(int32) |
     counts(int32)], so a caller can bring a whole batch to the host with a single D2H copy

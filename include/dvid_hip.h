@@ -379,6 +379,31 @@ int dvid_coco_eval_match(const float* dets, const int* counts, int n_images, int
                          const unsigned char* gt_crowd, const int* gt_labels, const int* gt_starts, const int* gt_starts_host,
                          const double* iou_thrs, const double* area_ranges, int num_classes, signed char* match, signed char* ignore,
                          int* rank, int* npig, void* stream);
+/* The matching of the LVIS bbox evaluator on the device, the federated protocol (dvid_version >= 8; csrc/lviseval.hip;
+ * data/evaluation/lvis_eval.py: match_numpy), one workgroup per image, the ten IoU thresholds and the four area ranges in one launch.  No
+ * model handle, independent of DTYPE.
+ * in   dets, counts, gt_boxes, gt_areas, gt_labels, gt_starts, gt_starts_host, iou_thrs, area_ranges: as dvid_coco_eval_match; gt_ignore
+ *      [G] uint8 (the annotation's `ignore`) where that entry has gt_crowd; the image's negative and not-exhaustive label lists as two CSR
+ *      tables on the device, neg_starts [n_images + 1] int32 with neg_labels, nex_starts [n_images + 1] int32 with nex_labels (image f owns
+ *      neg_labels[neg_starts[f] .. neg_starts[f + 1]); a label outside 0 .. num_classes is skipped), and the two start tables on the HOST.
+ * out  match, ignore, rank, npig: the layout of dvid_coco_eval_match.  rank -1, match 0 and ignore 0 also for every row that is not among
+ *      the image's DVID_LVIS_EVAL_MAX_DETS rows of highest score (all labels together; equal scores: the lower row first; a row whose
+ *      label is outside 0 .. num_classes takes no place) and for every row among them whose label is neither a label of one of the
+ *      image's boxes nor in its negative list.  There is no further cut per label.
+ * A box is ignored in a range when gt_ignore is set or its area lies outside.  The walk is dvid_coco_eval_match's without the crowd case:
+ * a taken box is never taken again.  A row that takes no box does not count when its own area lies outside the range or its label is in
+ * the image's not-exhaustive list; a row that takes a box counts as that box does.  Precondition: the scores are finite.
+ * Before anything is launched: cap <= DVID_NMS_MAX_CANDIDATES, num_classes <= DVID_MAX_CLASSES, at most DVID_LVIS_EVAL_MAX_GT boxes
+ * per image (DVID_ERR_UNSUPPORTED beyond, with the limit and the value in the message; nothing is written); the three start tables begin
+ * at 0 and do not decrease (DVID_ERR_ARG).  DVID_LVIS_EVAL_MAX_GT is what the workgroup's LDS holds beside 4096 row keys: 115784 bytes
+ * of 160 KiB (csrc/lviseval.hip has the sum). */
+#define DVID_LVIS_EVAL_MAX_GT 1024
+#define DVID_LVIS_EVAL_MAX_DETS 300
+int dvid_lvis_eval_match(const float* dets, const int* counts, int n_images, int cap, const double* gt_boxes, const double* gt_areas,
+                         const unsigned char* gt_ignore, const int* gt_labels, const int* gt_starts, const int* gt_starts_host,
+                         const int* neg_starts, const int* neg_labels, const int* neg_starts_host, const int* nex_starts, const int* nex_labels,
+                         const int* nex_starts_host, const double* iou_thrs, const double* area_ranges, int num_classes, signed char* match,
+                         signed char* ignore, int* rank, int* npig, void* stream);
 int dvid_cdist(const float* x, int n, int d, float* dist, void* stream);
 /* bs_emul: block size of the reference CUDA launch to emulate for tie-breaking (0 = fps.cu's own rule) */
 int dvid_fps_greedy(const float* dist, int n, int m, int bs_emul, int* idx, void* stream);

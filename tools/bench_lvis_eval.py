@@ -1,0 +1,158 @@
+"""Time the LVIS bbox evaluator (the federated protocol) on an LVIS-val-shaped synthetic set: the numpy path
+(lvis_eval.do_lvis_evaluation, device=None) and the device path (device=cuda: ops.lvis_eval_match, csrc/lviseval.hip).
+
+    python tools/bench_lvis_eval.py [--images 19809] [--dets 300] [--cpu-images 250] [--repeats 3] [--warmup 1] [--out FILE]
+
+The set: `--images` images of 640 x 480 (LVIS v1 val has 19809), 1203 categories (337 rare, 461 common, 405 frequent, as v1), per image
+1 .. 23 ground-truth boxes (12 on average; v1 val has 12.3) of one to five categories, sides 6 .. 400 pixels drawn log-uniformly so that
+all three area ranges are met, the annotation's area 0.5 .. 1 of w * h, 2 % of the boxes with `ignore`.  Lists, at a stated rate: every
+image's `neg_category_ids` holds `--neg` (8) categories that none of its boxes has, and every category of its boxes is in
+`not_exhaustive_category_ids` with probability `--nex` (0.1).  `--dets` detections per image (300 = DETECTIONS_PER_IMG of
+configs/still_R_101_DiffusionDet_lvis.yaml): three jittered copies of every box with detector-like scores, and clutter of low score in the
+other rows, half of it of the image's listed categories and half of any category (most of which nobody looked for: those rows vanish).
+Seeded.
+What is timed
+  numpy   do_lvis_evaluation(device=None) on the FIRST `--cpu-images` images only, median of `--repeats` runs, and that time SCALED
+          linearly by images to the whole set -- the matching loops are linear in images, the final sorts slightly worse.  It is a scaled
+          figure, not a measurement of the whole set.
+  device  the WHOLE set, median of `--repeats` runs after `--warmup`, in parts: pack (pack_detections + pack_groundtruth on the host),
+          copy (host to device, and the results back), kernel (the matching launch, to the device synchronise) and tail (numpy:
+          accumulate_from_matches and summarize); their sum is the total.
+On the subset both paths' lvis_eval.txt texts are compared.  There is no speed gate: the figures are a record."""
+import argparse
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+STAGES = ("pack", "copy_in", "kernel", "copy_out", "tail")
+W, H, CLASSES, RARE, COMMON = 640, 480, 1203, 337, 461
+
+
+def make_set(images, dets, seed, n_neg, p_nex):
+    """-> (an LVIS annotation dict, {image id: BoxList})"""
+    from diffusionvid_amd.structures.bounding_box import BoxList
+    rng = np.random.RandomState(seed)
+    ann = {"images": [], "annotations": [],
+           "categories": [{"id": c + 1, "name": "c%d" % (c + 1), "frequency": "r" if c < RARE else ("c" if c < RARE + COMMON else "f")}
+                          for c in range(CLASSES)]}
+    preds = {}
+    for i in range(images):
+        g = int(rng.randint(1, 24))
+        cats = np.unique(rng.randint(1, CLASSES + 1, size=int(rng.randint(1, 6))))
+        neg = [int(c) for c in rng.randint(1, CLASSES + 1, size=n_neg) if c not in cats]
+        ann["images"].append({"id": i + 1, "width": W, "height": H, "neg_category_ids": sorted(set(neg)),
+                              "not_exhaustive_category_ids": [int(c) for c in cats if rng.rand() < p_nex]})
+        wh = np.exp(rng.uniform(np.log(6), np.log(400), size=(g, 2)))
+        xy = rng.uniform(0, 1, size=(g, 2)) * np.maximum((W, H) - wh, 1)
+        gl = cats[rng.randint(0, len(cats), size=g)]
+        for k in range(g):
+            a = {"id": len(ann["annotations"]) + 1, "image_id": i + 1, "category_id": int(gl[k]),
+                 "bbox": [float(xy[k, 0]), float(xy[k, 1]), float(wh[k, 0]), float(wh[k, 1])],
+                 "area": float(wh[k, 0] * wh[k, 1] * rng.uniform(0.5, 1.0))}
+            if rng.rand() < 0.02:
+                a["ignore"] = 1
+            ann["annotations"].append(a)
+        out = np.zeros((dets, 6), dtype=np.float32)
+        dxy = rng.uniform(0, 1, size=(dets, 2)) * (W - 40, H - 40)
+        out[:, :4] = np.concatenate((dxy, dxy + np.exp(rng.uniform(np.log(6), np.log(300), size=(dets, 2)))), axis=1)
+        out[:, 4] = rng.beta(1, 12, size=dets)
+        listed = np.concatenate((cats, np.asarray(neg, dtype=cats.dtype)))
+        out[:, 5] = np.where(rng.rand(dets) < 0.5, listed[rng.randint(0, len(listed), size=dets)], rng.randint(1, CLASSES + 1, size=dets))
+        for j in range(min(3 * g, dets)):
+            k, tier = j % g, j // g
+            box = np.concatenate((xy[k], xy[k] + wh[k])) + rng.uniform(-0.08, 0.08, size=4) * (1 + tier) * np.tile(wh[k], 2)
+            out[j, :4] = box
+            out[j, 4] = np.clip(rng.normal(0.75 - 0.2 * tier, 0.12), 0.02, 0.99)
+            out[j, 5] = gl[k]
+        t = torch.from_numpy(out)
+        bl = BoxList(t[:, :4], (W, H))
+        bl.add_field("scores", t[:, 4])
+        bl.add_field("labels", t[:, 5].long())
+        preds[i + 1] = bl
+    return ann, preds
+
+
+def subset(ann, preds, k):
+    ids = set(im["id"] for im in ann["images"][:k])
+    part = dict(ann, images=ann["images"][:k], annotations=[a for a in ann["annotations"] if a["image_id"] in ids])
+    return part, {i: preds[i] for i in ids}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=19809)
+    ap.add_argument("--dets", type=int, default=300)
+    ap.add_argument("--neg", type=int, default=8, help="categories drawn for every image's neg_category_ids")
+    ap.add_argument("--nex", type=float, default=0.1, help="probability that a category of the image's boxes is not exhaustively annotated")
+    ap.add_argument("--cpu-images", type=int, default=250, help="the numpy path is timed on the first K images and scaled")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--seed", type=int, default=2019)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lvis_eval_bench.txt"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_lvis_eval needs the GPU: nothing is timed without one")
+    from diffusionvid_amd.data.evaluation import lvis_eval
+    t0 = time.perf_counter()
+    ann, preds = make_set(args.images, args.dets, args.seed, args.neg, args.nex)
+    N, K = args.images, min(args.cpu_images, args.images)
+    per_image = np.bincount([a["image_id"] for a in ann["annotations"]])
+    lines = ["LVIS evaluator: %d images, %d detections per image, %d categories, %d ground-truth boxes, at most %d on one image (set built in %.1f s)" % (
+        N, args.dets, CLASSES, len(ann["annotations"]), int(per_image.max()), time.perf_counter() - t0),
+        "lists: %d categories drawn per image for neg_category_ids (%.1f kept on average), a box's category not exhaustive with probability %.2f "
+        "(%.2f per image on average)" % (args.neg, np.mean([len(im["neg_category_ids"]) for im in ann["images"]]), args.nex,
+                                        np.mean([len(im["not_exhaustive_category_ids"]) for im in ann["images"]])),
+        "torch %s, %s; the host parts (pack, tail, numpy) run on one thread" % (torch.__version__, torch.cuda.get_device_name(0))]
+    print("\n".join(lines), flush=True)
+    device = torch.device("cuda")
+    whole = lvis_eval.LvisAnnotations(ann)
+    part_ann, part_preds = subset(ann, preds, K)
+    part = lvis_eval.LvisAnnotations(part_ann)
+    with tempfile.TemporaryDirectory() as tmp:
+        cpu = []
+        for _ in range(args.repeats):
+            t0 = time.perf_counter()
+            lvis_eval.do_lvis_evaluation(part, part_preds, tmp)
+            cpu.append(time.perf_counter() - t0)
+        want = open(os.path.join(tmp, "lvis_eval.txt"), "rb").read()
+        lvis_eval.do_lvis_evaluation(part, part_preds, tmp, device=device)
+        same = want == open(os.path.join(tmp, "lvis_eval.txt"), "rb").read()
+    cpu_s = statistics.median(cpu)
+    print("  numpy on %d images: %.3f s; texts %s" % (K, cpu_s, "identical" if same else "DIFFERENT"), flush=True)
+    runs, stats = [], None
+    for i in range(args.warmup + args.repeats):
+        times = {}
+        stats = lvis_eval.do_lvis_evaluation(whole, preds, None, device=device, times=times)
+        if i >= args.warmup:
+            runs.append(times)
+        print("  device run %d: %s" % (i, " ".join("%s %.2f" % (k, times[k]) for k in STAGES)), flush=True)
+    med = {k: statistics.median(r[k] for r in runs) for k in STAGES}
+    totals = [sum(r[k] for k in STAGES) for r in runs]
+    total = statistics.median(totals)
+    block = ["",
+             "  numpy, MEASURED on the first %d images: %.3f s (median of %d, min %.3f max %.3f)" % (K, cpu_s, len(cpu), min(cpu), max(cpu)),
+             "  numpy, SCALED by images to %d images (not measured): %.1f s" % (N, cpu_s * N / K),
+             "  device, measured on all %d images, median of %d after %d warm-up: total %.2f s" % (N, len(runs), args.warmup, total),
+             "    pack %.2f s | copy %.2f s (in %.2f + out %.2f) | kernel %.3f s | tail %.2f s" % (
+                 med["pack"], med["copy_in"] + med["copy_out"], med["copy_in"], med["copy_out"], med["kernel"], med["tail"]),
+             "    spread of the total over the runs: min %.2f max %.2f s" % (min(totals), max(totals)),
+             "  lvis_eval.txt of both paths on the first %d images: %s" % (K, "identical" if same else "DIFFERENT"),
+             "  the scaled numpy figure is %.1fx the device total; largest device part: %s" % (cpu_s * N / K / total, max(med, key=med.get)),
+             "  whole set on the device: " + " ".join("%s %.3f" % kv for kv in stats.items())]
+    lines += block
+    print("\n".join(block), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
