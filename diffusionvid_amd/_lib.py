@@ -89,6 +89,8 @@ SIGNATURES = {
                             [c_void_p] * 7),
     "dvid_coco_eval_match": (c_int, [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 8 + [c_int] + [c_void_p] * 5),
     "dvid_lvis_eval_match": (c_int, [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 14 + [c_int] + [c_void_p] * 5),
+    "dvid_eval_accumulate": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 3 + [c_int64, c_void_p]),
+    "dvid_eval_accumulate_scratch_bytes": (c_int64, [c_int, c_int, c_int]),
     "dvid_cdist":(c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "dvid_fps_greedy": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dvid_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -235,6 +235,13 @@ int dvid_lvis_eval_match_launch(const float* dets, const int* counts, int n_imag
                                 const double* area_ranges, int num_classes, signed char* match, signed char* ignore, int* rank, int* npig,
                                 hipStream_t s);
 
+// evalaccum.hip: the COCO / LVIS evaluators' accumulation (precision and recall with numpy's bits); max_dets / rec_thrs are host tables,
+// the scratch is dvid_eval_accumulate_scratch_size(...) bytes (-1: bad sizes); every argument is checked by the caller (ops_abi.hip)
+long long dvid_eval_accumulate_scratch_size(int n_images, int cap, int max_dets_count);
+int dvid_eval_accumulate_launch(const float* dets, const int* counts, const int* rank, const signed char* match, const signed char* ignore,
+                                const int* npig, int n_images, int cap, int num_classes, const int* max_dets, int max_dets_count,
+                                const double* rec_thrs, double* precision, double* recall, void* scratch, hipStream_t s);
+
 // fps.hip
 int dvid_cdist_launch(const float* x, int n, int d, float* dist, hipStream_t s);
 int dvid_fps_launch(const float* dist, int n, int m, int bs_emul, int* idx, hipStream_t s);

@@ -385,6 +385,50 @@ int dvid_lvis_eval_match(const float* dets, const int* counts, int n_images, int
     return DVID_OK;
 }
 
+long long dvid_eval_accumulate_scratch_bytes(int n_images, int cap, int max_dets_count) {
+    return dvid_eval_accumulate_scratch_size(n_images, cap, max_dets_count);
+}
+
+int dvid_eval_accumulate(const float* dets, const int* counts, const int* rank, const signed char* match, const signed char* ignore,
+                         const int* npig, int n_images, int cap, int num_classes, int n_areas, int n_thresholds, const int* max_dets,
+                         int max_dets_count, const double* rec_thrs, int n_rec_thrs, double* precision, double* recall, void* scratch,
+                         long long scratch_bytes, void* stream) {
+    g_err[0] = 0;
+    if (n_images < 0 || cap < 1 || num_classes < 1)
+        FAIL(DVID_ERR_ARG, "evaluation accumulate: bad sizes (%d images, %d rows per image, %d classes)", n_images, cap, num_classes);
+    if (n_areas != DVID_COCO_EVAL_AREAS || n_thresholds != DVID_COCO_EVAL_THRESHOLDS || n_rec_thrs != DVID_EVAL_ACCUMULATE_RECALLS)
+        FAIL(DVID_ERR_ARG, "evaluation accumulate: %d area ranges, %d IoU thresholds and %d recall thresholds; the kernels are built for %d, %d and %d "
+             "(DVID_COCO_EVAL_AREAS, DVID_COCO_EVAL_THRESHOLDS, DVID_EVAL_ACCUMULATE_RECALLS)", n_areas, n_thresholds, n_rec_thrs, DVID_COCO_EVAL_AREAS,
+             DVID_COCO_EVAL_THRESHOLDS, DVID_EVAL_ACCUMULATE_RECALLS);
+    if (max_dets_count < 1 || max_dets_count > DVID_EVAL_ACCUMULATE_MAX_LIMITS)
+        FAIL(DVID_ERR_ARG, "evaluation accumulate: %d detection limits, 1 .. %d are taken (DVID_EVAL_ACCUMULATE_MAX_LIMITS)", max_dets_count,
+             DVID_EVAL_ACCUMULATE_MAX_LIMITS);
+    if (!max_dets || !rec_thrs || !npig || !precision || !recall) FAIL(DVID_ERR_ARG, "evaluation accumulate: null pointer");
+    for (int m = 0; m < max_dets_count; ++m)
+        if (max_dets[m] < 1 || (m && max_dets[m] <= max_dets[m - 1]))
+            FAIL(DVID_ERR_ARG, "evaluation accumulate: max_dets must be positive and ascending (entry %d is %d)", m, max_dets[m]);
+    for (int r = 1; r < n_rec_thrs; ++r)
+        if (!(rec_thrs[r] >= rec_thrs[r - 1])) FAIL(DVID_ERR_ARG, "evaluation accumulate: rec_thrs decreases at entry %d", r);
+    if (cap > DVID_NMS_MAX_CANDIDATES)
+        FAIL(DVID_ERR_UNSUPPORTED, "evaluation accumulate: %d rows per image exceed the limit of %d (DVID_NMS_MAX_CANDIDATES)", cap, DVID_NMS_MAX_CANDIDATES);
+    if (num_classes > DVID_MAX_CLASSES)
+        FAIL(DVID_ERR_UNSUPPORTED, "evaluation accumulate: %d classes exceed the limit of %d (DVID_MAX_CLASSES)", num_classes, DVID_MAX_CLASSES);
+    const long long rows = (long long)n_images * cap;
+    if (rows >= (1ll << 31))
+        FAIL(DVID_ERR_UNSUPPORTED, "evaluation accumulate: %d images x %d rows are %lld rows, the limit is %lld (rows are indexed with int32)", n_images, cap,
+             rows, (1ll << 31) - 1);
+    const long long need = dvid_eval_accumulate_scratch_size(n_images, cap, max_dets_count);
+    if (need > DVID_EVAL_ACCUMULATE_MAX_SCRATCH_BYTES)
+        FAIL(DVID_ERR_UNSUPPORTED, "evaluation accumulate: %lld bytes of sort buffers for %lld rows (56 bytes per row) exceed the limit of %lld "
+             "(DVID_EVAL_ACCUMULATE_MAX_SCRATCH_BYTES): evaluate fewer images per call", need, rows, (long long)DVID_EVAL_ACCUMULATE_MAX_SCRATCH_BYTES);
+    if (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 15))
+        FAIL(DVID_ERR_ARG, "evaluation accumulate: the scratch holds %lld bytes, %lld are needed (16-byte aligned)", scratch_bytes, need);
+    if (rows > 0 && (!dets || !counts || !rank || !match || !ignore)) FAIL(DVID_ERR_ARG, "evaluation accumulate: null pointer");
+    TRY(dvid_eval_accumulate_launch(dets, counts, rank, match, ignore, npig, n_images, cap, num_classes, max_dets, max_dets_count, rec_thrs, precision,
+                                    recall, scratch, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
 int dvid_cdist(const float* x, int n, int d, float* dist, void* stream) {
     g_err[0] = 0;
     TRY(dvid_cdist_launch(x, n, d, dist, reinterpret_cast<hipStream_t>(stream)));

@@ -20,6 +20,8 @@ itself, from its published definition:
   summarize    means over the entries > -1
 
 Both paths produce (match, ignore, rank, npig) in one layout and share accumulate_from_matches, so their results are equal, not close.
+accumulate="device" runs accumulate_arrays as kernels on those arrays (ops.eval_accumulate, csrc/evalaccum.hip): its order of the rows is
+total -- label, score descending, image, rank -- and the rest is integer counts and single float64 divisions, so that result is equal too.
 Not here: segmentation and keypoint evaluation, proposal recall, evaluation spread over ranks; LVIS' federated protocol is lvis_eval.py."""
 import json
 import os
@@ -236,6 +238,25 @@ def accumulate_arrays(scores, labels, counts, rank, match, ignore, npig, max_det
     return precision, recall
 
 
+ACCUMULATE_MODES = ("numpy", "device")
+
+
+def check_accumulate(accumulate, device, keyword="accumulate", device_keyword="device"):
+    """the evaluators' `accumulate` keyword: "numpy", or "device", which needs a device for the matching as well"""
+    if accumulate not in ACCUMULATE_MODES:
+        raise ValueError("%s is 'numpy' or 'device', not %r" % (keyword, accumulate))
+    if accumulate == "device" and device is None:
+        raise ValueError("%s='device' needs %s: the accumulation runs where the matching leaves its arrays" % (keyword, device_keyword))
+
+
+def accumulate_arrays_device(dets, counts, rank, match, ignore, npig, max_dets):
+    """accumulate_arrays as kernels (ops.eval_accumulate, csrc/evalaccum.hip) on the arrays the matching left on the device (dets
+    [N, cap, 6] supplies the scores and the labels) -> (precision, recall) on the host, equal to accumulate_arrays' bit for bit"""
+    from ... import ops
+    precision, recall = ops.eval_accumulate(dets, counts, rank, match, ignore, npig, max_dets, REC_THRS)
+    return precision.cpu().numpy(), recall.cpu().numpy()
+
+
 def _mean(s):
     s = s[s > -1]
     return float(np.mean(s)) if len(s) else -1.0
@@ -266,10 +287,14 @@ def evaluate_numpy(dets, counts, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_sta
     return _tail(dets, counts, got[2], got[0], got[1], got[3])
 
 
-def evaluate_device(dets, counts, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_starts, num_classes, device=None, times=None):
+def evaluate_device(dets, counts, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_starts, num_classes, device=None, times=None, accumulate="numpy"):
     """evaluate_numpy with the matching as one kernel call on `device` (default: where dets is); the accumulation is the same numpy
-    code on the same arrays, so the result is equal.  times: see vid_eval._Laps (copy_in, kernel, copy_out, tail)."""
+    code on the same arrays, so the result is equal.  times: see vid_eval._Laps (copy_in, kernel, copy_out, tail).
+    accumulate "device": match, ignore and rank stay on the device, ops.eval_accumulate runs there and only precision and recall
+    come back (equal again: csrc/evalaccum.hip); the laps are then copy_in, kernel, accumulate, copy_out, tail (summarize)."""
     from ... import ops
+    if accumulate not in ACCUMULATE_MODES:
+        raise ValueError("accumulate is 'numpy' or 'device', not %r" % (accumulate,))
     dets = torch.as_tensor(dets)
     device = torch.device(device) if device is not None else dets.device
     lap = _Laps(times, device)
@@ -282,6 +307,15 @@ def evaluate_device(dets, counts, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_st
     lap("copy_in")
     got = ops.coco_eval_match(dets, counts, *gt, num_classes, IOU_THRS, AREA_RANGES)
     lap("kernel")
+    if accumulate == "device":
+        match, ignore, rank, npig = got
+        pr, rc = ops.eval_accumulate(dets, counts, rank, match, ignore, npig, MAX_DETS, REC_THRS)
+        lap("accumulate")
+        precision, recall = pr.cpu().numpy(), rc.cpu().numpy()
+        lap("copy_out")
+        out = {"precision": precision, "recall": recall, "stats": summarize(precision, recall)}
+        lap("tail")
+        return out
     match, ignore, rank, npig = (t.cpu().numpy() for t in got)
     host, counts = dets.cpu(), counts.cpu().numpy()
     lap("copy_out")
@@ -304,12 +338,14 @@ def result_string(stats):
     return text
 
 
-def do_coco_evaluation(annotations, predictions, output_folder=None, device=None, logger=None, times=None):
+def do_coco_evaluation(annotations, predictions, output_folder=None, device=None, logger=None, times=None, accumulate="numpy"):
     """annotations: a CocoAnnotations, a path or a dict; predictions: {image id: BoxList} as engine.inference_images returns them (boxes
     xyxy in the original image's pixels, `scores`, `labels` 1 .. K in CocoAnnotations' order).  Every image of the annotations is
     evaluated, one without a prediction as an image without detections; a prediction for an image the annotations do not list, or a
     label outside 1 .. K, is an error.  -> an ordered dict of the twelve numbers (STAT_NAMES); the text goes to the logger and to
-    `output_folder/coco_eval.txt`.  device: a torch.device runs the matching there and writes the same text; None is the numpy path."""
+    `output_folder/coco_eval.txt`.  device: a torch.device runs the matching there and writes the same text; None is the numpy path.
+    accumulate: "device" runs the accumulation on `device` too (evaluate_device) and writes the same text again."""
+    check_accumulate(accumulate, device)
     ann = annotations if isinstance(annotations, CocoAnnotations) else CocoAnnotations(annotations)
     lap = _Laps(times, torch.device(device) if device is not None else torch.device("cpu"))
     counts, dets = pack_detections(predictions, ann.image_ids)
@@ -323,7 +359,7 @@ def do_coco_evaluation(annotations, predictions, output_folder=None, device=None
     if device is None:
         res = evaluate_numpy(dets, counts, *gt, max(1, ann.num_classes))
     else:
-        res = evaluate_device(dets, counts, *gt, max(1, ann.num_classes), device=device, times=times)
+        res = evaluate_device(dets, counts, *gt, max(1, ann.num_classes), device=device, times=times, accumulate=accumulate)
     text = result_string(res["stats"])
     if logger is not None:
         logger.info("\n" + text)

@@ -208,10 +208,13 @@ def evaluate_numpy(dets, counts, gt_boxes, gt_areas, gt_ignore, gt_labels, gt_st
 
 
 def evaluate_device(dets, counts, gt_boxes, gt_areas, gt_ignore, gt_labels, gt_starts, neg_starts, neg_labels, nex_starts, nex_labels, frequency,
-                    num_classes, device=None, times=None):
+                    num_classes, device=None, times=None, accumulate="numpy"):
     """evaluate_numpy with the matching as one kernel call on `device` (default: where dets is); the accumulation is the same numpy
-    code on the same arrays, so the result is equal.  times: see vid_eval._Laps (copy_in, kernel, copy_out, tail)."""
+    code on the same arrays, so the result is equal.  times: see vid_eval._Laps (copy_in, kernel, copy_out, tail).
+    accumulate "device": as coco_eval.evaluate_device, with the one limit 300 (laps copy_in, kernel, accumulate, copy_out, tail)."""
     from ... import ops
+    if accumulate not in coco_eval.ACCUMULATE_MODES:
+        raise ValueError("accumulate is 'numpy' or 'device', not %r" % (accumulate,))
     dets = torch.as_tensor(dets)
     device = torch.device(device) if device is not None else dets.device
     lap = _Laps(times, device)
@@ -225,6 +228,15 @@ def evaluate_device(dets, counts, gt_boxes, gt_areas, gt_ignore, gt_labels, gt_s
     lap("copy_in")
     got = ops.lvis_eval_match(dets, counts, *gt, num_classes, IOU_THRS, AREA_RANGES)
     lap("kernel")
+    if accumulate == "device":
+        match, ignore, rank, npig = got
+        pr, rc = ops.eval_accumulate(dets, counts, rank, match, ignore, npig, (MAX_DETS,), coco_eval.REC_THRS)
+        lap("accumulate")
+        precision, recall = pr.cpu().numpy(), rc.cpu().numpy()
+        lap("copy_out")
+        out = {"precision": precision, "recall": recall, "stats": summarize(precision, recall, _frequency(frequency, num_classes))}
+        lap("tail")
+        return out
     match, ignore, rank, npig = (t.cpu().numpy() for t in got)
     host, counts = dets.cpu(), counts.cpu().numpy()
     lap("copy_out")
@@ -261,12 +273,14 @@ def lvis_results(predictions, label_map=None):
     return coco_results(top, label_map)
 
 
-def do_lvis_evaluation(annotations, predictions, output_folder=None, device=None, logger=None, times=None):
+def do_lvis_evaluation(annotations, predictions, output_folder=None, device=None, logger=None, times=None, accumulate="numpy"):
     """annotations: an LvisAnnotations, a path or a dict; predictions: {image id: BoxList} as engine.inference_images returns them (boxes
     xyxy in the original image's pixels, `scores`, `labels` 1 .. K in the annotations' order).  Every image of the annotations is
     evaluated, one without a prediction as an image without detections; a prediction for an image the annotations do not list, or a
     label outside 1 .. K, is an error.  -> an ordered dict of the thirteen numbers (STAT_NAMES); the text goes to the logger and to
-    `output_folder/lvis_eval.txt`.  device: a torch.device runs the matching there and writes the same text; None is the numpy path."""
+    `output_folder/lvis_eval.txt`.  device: a torch.device runs the matching there and writes the same text; None is the numpy path.
+    accumulate: "device" runs the accumulation on `device` too (evaluate_device) and writes the same text again."""
+    coco_eval.check_accumulate(accumulate, device)
     ann = annotations if isinstance(annotations, LvisAnnotations) else LvisAnnotations(annotations)
     lap = _Laps(times, torch.device(device) if device is not None else torch.device("cpu"))
     counts, dets = pack_detections(predictions, ann.image_ids)
@@ -280,7 +294,7 @@ def do_lvis_evaluation(annotations, predictions, output_folder=None, device=None
     if device is None:
         res = evaluate_numpy(dets, counts, *gt, max(1, ann.num_classes))
     else:
-        res = evaluate_device(dets, counts, *gt, max(1, ann.num_classes), device=device, times=times)
+        res = evaluate_device(dets, counts, *gt, max(1, ann.num_classes), device=device, times=times, accumulate=accumulate)
     text = result_string(res["stats"])
     if logger is not None:
         logger.info("\n" + text)

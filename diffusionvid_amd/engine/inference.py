@@ -428,7 +428,8 @@ def _still_annotations(annotations, protocol):
     return "coco", coco_eval.CocoAnnotations(annotations)
 
 
-def inference_images(model, loader, output_folder=None, label_map=None, annotations=None, eval_device=None, bbox_aug=None, protocol=None):
+def inference_images(model, loader, output_folder=None, label_map=None, annotations=None, eval_device=None, bbox_aug=None, protocol=None,
+                     eval_accumulate="numpy"):
     """Still images: `loader` yields (images, image_ids, original (w, h) per image) batches (data/datasets/still.py: batches, or a DataLoader
     over StillImageDataset with OrientationBatchSampler and collate_images); every batch goes through model.detect_images with its ids
     -- so an image's draws, and with them its detections, do not depend on its batch -- and every BoxList is mapped back to the image's
@@ -438,7 +439,8 @@ def inference_images(model, loader, output_folder=None, label_map=None, annotati
     protocol (coco_eval.do_coco_evaluation; `coco_eval.txt` in `output_folder`) -> (predictions, the ordered dict of the twelve
     numbers); `label_map` then defaults to the annotations' label -> category id map, and a prediction for an image that the
     annotations do not list is an error that names the id.  eval_device: a torch.device runs the evaluator's matching there; None keeps
-    it in numpy.
+    it in numpy.  eval_accumulate: "device" runs the evaluator's accumulation on `eval_device` as well (the same numbers and files);
+    "numpy" keeps it on the host.
     protocol ("coco", "lvis" or None): None takes the LVIS bbox protocol (lvis_eval.do_lvis_evaluation: the federated protocol, thirteen
     numbers, `lvis_eval.txt`, and `lvis_results.json` with at most 300 rows per image) exactly when the file's images carry
     `neg_category_ids`, which a COCO file's never do.
@@ -446,6 +448,8 @@ def inference_images(model, loader, output_folder=None, label_map=None, annotati
     uint8 images at their native size (still.batches(..., raw=True), collate_raw) and go to model.detect_images_aug, whose BoxLists are in
     the plain test transform's size; everything behind it is the same."""
     import os
+    from ..data.evaluation.coco_eval import check_accumulate
+    check_accumulate(eval_accumulate, eval_device, "eval_accumulate", "eval_device")
     if bbox_aug is None:
         bbox_aug = bool(getattr(getattr(getattr(getattr(model, "cfg", None), "TEST", None), "BBOX_AUG", None), "ENABLED", False))
     detect = model.detect_images_aug if bbox_aug else model.detect_images
@@ -477,5 +481,5 @@ def inference_images(model, loader, output_folder=None, label_map=None, annotati
             import json
             with open(os.path.join(output_folder, "lvis_results.json"), "w") as f:
                 json.dump(lvis_eval.lvis_results(predictions, label_map), f)
-        return predictions, lvis_eval.do_lvis_evaluation(ann, predictions, output_folder, device=eval_device)
-    return predictions, coco_eval.do_coco_evaluation(ann, predictions, output_folder, device=eval_device)
+        return predictions, lvis_eval.do_lvis_evaluation(ann, predictions, output_folder, device=eval_device, accumulate=eval_accumulate)
+    return predictions, coco_eval.do_coco_evaluation(ann, predictions, output_folder, device=eval_device, accumulate=eval_accumulate)

@@ -757,6 +757,41 @@ def lvis_eval_match(dets, counts, gt_boxes, gt_areas, gt_ignore, gt_labels, gt_s
     return out
 
 
+EVAL_ACCUMULATE_RECALLS, EVAL_ACCUMULATE_MAX_LIMITS, EVAL_ACCUMULATE_MAX_SCRATCH_BYTES = 101, 3, 1 << 30          # include/dvid_hip.h
+
+
+def eval_accumulate(dets, counts, rank, match, ignore, npig, max_dets, rec_thrs, out=None):
+    """The COCO / LVIS evaluators' accumulation (coco_eval.accumulate_arrays) on the device, with that function's bits
+    (csrc/evalaccum.hip).  dets [N, cap, 6] fp32 and counts [N] int32 as the matching read them, (match [4, 10, N, cap] int8, ignore
+    [4, 10, N, cap] int8, rank [N, cap] int32, npig [4, K + 1] int32) as coco_eval_match / lvis_eval_match return them, all on the
+    device; max_dets: 1 .. 3 ascending limits; rec_thrs: 101 floats, taken as float64.  Returns (precision [10, 101, K, 4, M] float64,
+    recall [10, K, 4, M] float64) on the device; `out`: such a pair to write into.  The scores must be finite."""
+    dets, counts, rank = _cuda(dets, torch.float32), _cuda(counts, torch.int32), _cuda(rank, torch.int32)
+    match, ignore, npig = _cuda(match, torch.int8), _cuda(ignore, torch.int8), _cuda(npig, torch.int32)
+    N, cap = counts.shape[0], dets.shape[1] if dets.dim() == 3 else -1
+    assert dets.shape == (N, cap, 6) and rank.shape == (N, cap), "dets is [images, cap, 6], rank [images, cap]"
+    assert match.dim() == 4 and match.shape == ignore.shape and match.shape[2:] == (N, cap), "match and ignore are [areas, thresholds, images, cap]"
+    A, T = match.shape[:2]
+    assert npig.dim() == 2 and npig.shape[0] == A and npig.shape[1] >= 2, "npig is [areas, classes + 1]"
+    K = npig.shape[1] - 1
+    lim = torch.tensor([int(m) for m in max_dets], dtype=torch.int32)
+    thr = torch.tensor([float(r) for r in rec_thrs], dtype=torch.float64)
+    M, R = lim.numel(), thr.numel()
+    dev = dets.device
+    if out is None:
+        out = (torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev), torch.empty((T, K, A, M), dtype=torch.float64, device=dev))
+    precision, recall = out
+    assert precision.shape == (T, R, K, A, M) and recall.shape == (T, K, A, M), "output shapes"
+    assert precision.dtype == recall.dtype == torch.float64 and precision.is_contiguous() and recall.is_contiguous(), "outputs are contiguous float64"
+    if N == 0 or cap == 0:
+        N, cap = 0, 1          # no row at all: the counted categories get 0
+    need = int(_lib.load().dvid_eval_accumulate_scratch_bytes(N, cap, M))
+    scratch = torch.empty((max(16, need),), dtype=torch.uint8, device=dev) if 0 <= need <= EVAL_ACCUMULATE_MAX_SCRATCH_BYTES else None
+    call("dvid_eval_accumulate", ptr(dets), ptr(counts), ptr(rank), ptr(match), ptr(ignore), ptr(npig), N, cap, K, A, T, ptr(lim), M, ptr(thr), R,
+         ptr(_cuda(precision)), ptr(_cuda(recall)), ptr(scratch), need if scratch is not None else 0, stream_ptr())
+    return out
+
+
 def split_detection_buffer(buf, n, cap):
     """The four post-processing outputs are views of ONE flat fp32 buffer [boxes | scores | labels(int32) |
     counts(int32)], so a caller can bring a whole batch to the host with a single D2H copy

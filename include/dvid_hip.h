@@ -404,6 +404,33 @@ int dvid_lvis_eval_match(const float* dets, const int* counts, int n_images, int
                          const int* neg_starts, const int* neg_labels, const int* neg_starts_host, const int* nex_starts, const int* nex_labels,
                          const int* nex_starts_host, const double* iou_thrs, const double* area_ranges, int num_classes, signed char* match,
                          signed char* ignore, int* rank, int* npig, void* stream);
+/* The accumulation of the COCO and the LVIS bbox evaluators on the device (dvid_version >= 9; csrc/evalaccum.hip;
+ * data/evaluation/coco_eval.py: accumulate_arrays), with that function's bits: its order of the rows is total (label, score descending
+ * with -0 == +0, image, rank), and everything behind the sort is integer counting, one correctly rounded float64 division, a maximum and
+ * a comparison.  No host synchronise.
+ * in   on the device, as dvid_coco_eval_match / dvid_lvis_eval_match read and leave them: dets [n_images, cap, 6] float32 (columns 4 and
+ *      5 are read), counts [n_images] int32, rank [n_images, cap] int32, match and ignore [n_areas, n_thresholds, n_images, cap] int8, npig
+ *      [n_areas, num_classes + 1] int32.  On the HOST: max_dets [max_dets_count] int32, ascending and positive ((1, 10, 100) for COCO,
+ *      (300) for LVIS), and rec_thrs [n_rec_thrs] float64, which do not decrease.
+ * out  precision [n_thresholds, n_rec_thrs, num_classes, n_areas, max_dets_count] and recall [n_thresholds, num_classes, n_areas,
+ *      max_dets_count] float64, every entry: -1 for a (category, range) without counted ground truth, as accumulate_arrays leaves it.
+ * A row is live when it lies in front of counts[image], its rank is >= 0 and its label is 1 .. num_classes; the scores must be finite.
+ * scratch: >= dvid_eval_accumulate_scratch_bytes(n_images, cap, max_dets_count) bytes, 16-byte aligned: 56 bytes per row of
+ * n_images * cap (two 64-bit keys and two 32-bit indices for the sort's two sides, two 64-bit flag masks in the layout's order and two in
+ * the sorted order), a 1 KiB histogram per 4096 rows, one int32 per image and 5 KiB of tables.
+ * Before anything is launched or written: n_areas == DVID_COCO_EVAL_AREAS, n_thresholds == DVID_COCO_EVAL_THRESHOLDS, n_rec_thrs ==
+ * DVID_EVAL_ACCUMULATE_RECALLS, 1 <= max_dets_count <= DVID_EVAL_ACCUMULATE_MAX_LIMITS, max_dets ascending and positive, rec_thrs not
+ * decreasing (DVID_ERR_ARG); cap <= DVID_NMS_MAX_CANDIDATES, num_classes <= DVID_MAX_CLASSES, n_images * cap < 2^31 and the scratch at
+ * most DVID_EVAL_ACCUMULATE_MAX_SCRATCH_BYTES, that is about 19 million rows (DVID_ERR_UNSUPPORTED, with the limit and the value in
+ * the message).  dvid_eval_accumulate_scratch_bytes is -1 for sizes that are no sizes. */
+#define DVID_EVAL_ACCUMULATE_RECALLS 101
+#define DVID_EVAL_ACCUMULATE_MAX_LIMITS 3
+#define DVID_EVAL_ACCUMULATE_MAX_SCRATCH_BYTES (1ll << 30)
+int dvid_eval_accumulate(const float* dets, const int* counts, const int* rank, const signed char* match, const signed char* ignore,
+                         const int* npig, int n_images, int cap, int num_classes, int n_areas, int n_thresholds, const int* max_dets,
+                         int max_dets_count, const double* rec_thrs, int n_rec_thrs, double* precision, double* recall, void* scratch,
+                         long long scratch_bytes, void* stream);
+long long dvid_eval_accumulate_scratch_bytes(int n_images, int cap, int max_dets_count);
 int dvid_cdist(const float* x, int n, int d, float* dist, void* stream);
 /* bs_emul: block size of the reference CUDA launch to emulate for tie-breaking (0 = fps.cu's own rule) */
 int dvid_fps_greedy(const float* dist, int n, int m, int bs_emul, int* idx, void* stream);

@@ -2,6 +2,7 @@
 (lvis_eval.do_lvis_evaluation, device=None) and the device path (device=cuda: ops.lvis_eval_match, csrc/lviseval.hip).
 
     python tools/bench_lvis_eval.py [--images 19809] [--dets 300] [--cpu-images 250] [--repeats 3] [--warmup 1] [--out FILE]
+        [--accumulate {numpy,device,both}] [--accumulate-out FILE]
 
 The set: `--images` images of 640 x 480 (LVIS v1 val has 19809), 1203 categories (337 rare, 461 common, 405 frequent, as v1), per image
 1 .. 23 ground-truth boxes (12 on average; v1 val has 12.3) of one to five categories, sides 6 .. 400 pixels drawn log-uniformly so that
@@ -18,7 +19,12 @@ What is timed
   device  the WHOLE set, median of `--repeats` runs after `--warmup`, in parts: pack (pack_detections + pack_groundtruth on the host),
           copy (host to device, and the results back), kernel (the matching launch, to the device synchronise) and tail (numpy:
           accumulate_from_matches and summarize); their sum is the total.
-On the subset both paths' lvis_eval.txt texts are compared.  There is no speed gate: the figures are a record."""
+On the subset both paths' lvis_eval.txt texts are compared.
+--accumulate  numpy (default): the run above.  device: the same run with the accumulation on the device as well
+              (accumulate="device", csrc/evalaccum.hip): a lap `accumulate` appears and the tail is summarize alone.  both: ONLY the two
+              accumulations side by side on the whole set, packed once, in one run (tools/_accumulate_bench.py): the numpy tail is the
+              yardstick of the device tail, and precision, recall, the numbers and the text of the two are compared at full size.  The
+              block is appended to `--accumulate-out` (profiles/eval_accumulate_bench.txt).  There is no speed gate: the figures are a record."""
 import argparse
 import os
 import statistics
@@ -97,6 +103,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--seed", type=int, default=2019)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lvis_eval_bench.txt"))
+    ap.add_argument("--accumulate", choices=("numpy", "device", "both"), default="numpy")
+    ap.add_argument("--accumulate-out", default=os.path.join(ROOT, "profiles", "eval_accumulate_bench.txt"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_lvis_eval needs the GPU: nothing is timed without one")
@@ -114,6 +122,18 @@ def main():
     print("\n".join(lines), flush=True)
     device = torch.device("cuda")
     whole = lvis_eval.LvisAnnotations(ann)
+    if args.accumulate == "both":
+        from _accumulate_bench import compare
+        counts, dets = lvis_eval.pack_detections(preds, whole.image_ids)
+        packed = (dets, counts) + tuple(lvis_eval.pack_groundtruth(whole))
+        block = compare(lvis_eval, packed, CLASSES, device, args.repeats, args.warmup, lines[0].split(" (set built")[0])
+        print("\n".join(block), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.accumulate_out)), exist_ok=True)
+        with open(args.accumulate_out, "a") as f:
+            f.write("\n".join(lines[-1:] + block) + "\n")
+        return
+    mode = args.accumulate
+    stages = STAGES if mode == "numpy" else STAGES[:3] + ("accumulate",) + STAGES[3:]
     part_ann, part_preds = subset(ann, preds, K)
     part = lvis_eval.LvisAnnotations(part_ann)
     with tempfile.TemporaryDirectory() as tmp:
@@ -123,26 +143,27 @@ def main():
             lvis_eval.do_lvis_evaluation(part, part_preds, tmp)
             cpu.append(time.perf_counter() - t0)
         want = open(os.path.join(tmp, "lvis_eval.txt"), "rb").read()
-        lvis_eval.do_lvis_evaluation(part, part_preds, tmp, device=device)
+        lvis_eval.do_lvis_evaluation(part, part_preds, tmp, device=device, accumulate=mode)
         same = want == open(os.path.join(tmp, "lvis_eval.txt"), "rb").read()
     cpu_s = statistics.median(cpu)
     print("  numpy on %d images: %.3f s; texts %s" % (K, cpu_s, "identical" if same else "DIFFERENT"), flush=True)
     runs, stats = [], None
     for i in range(args.warmup + args.repeats):
         times = {}
-        stats = lvis_eval.do_lvis_evaluation(whole, preds, None, device=device, times=times)
+        stats = lvis_eval.do_lvis_evaluation(whole, preds, None, device=device, times=times, accumulate=mode)
         if i >= args.warmup:
             runs.append(times)
-        print("  device run %d: %s" % (i, " ".join("%s %.2f" % (k, times[k]) for k in STAGES)), flush=True)
-    med = {k: statistics.median(r[k] for r in runs) for k in STAGES}
-    totals = [sum(r[k] for k in STAGES) for r in runs]
+        print("  device run %d: %s" % (i, " ".join("%s %.2f" % (k, times[k]) for k in stages)), flush=True)
+    med = {k: statistics.median(r[k] for r in runs) for k in stages}
+    totals = [sum(r[k] for k in stages) for r in runs]
     total = statistics.median(totals)
     block = ["",
              "  numpy, MEASURED on the first %d images: %.3f s (median of %d, min %.3f max %.3f)" % (K, cpu_s, len(cpu), min(cpu), max(cpu)),
              "  numpy, SCALED by images to %d images (not measured): %.1f s" % (N, cpu_s * N / K),
              "  device, measured on all %d images, median of %d after %d warm-up: total %.2f s" % (N, len(runs), args.warmup, total),
              "    pack %.2f s | copy %.2f s (in %.2f + out %.2f) | kernel %.3f s | tail %.2f s" % (
-                 med["pack"], med["copy_in"] + med["copy_out"], med["copy_in"], med["copy_out"], med["kernel"], med["tail"]),
+                 med["pack"], med["copy_in"] + med["copy_out"], med["copy_in"], med["copy_out"], med["kernel"], med["tail"]) +
+             (" | accumulate (device) %.3f s" % med["accumulate"] if mode == "device" else ""),
              "    spread of the total over the runs: min %.2f max %.2f s" % (min(totals), max(totals)),
              "  lvis_eval.txt of both paths on the first %d images: %s" % (K, "identical" if same else "DIFFERENT"),
              "  the scaled numpy figure is %.1fx the device total; largest device part: %s" % (cpu_s * N / K / total, max(med, key=med.get)),
