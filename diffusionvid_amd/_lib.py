@@ -117,6 +117,10 @@ SIGNATURES = {
     "dvid_resize_views_u8": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int,
                                      c_int, c_void_p]),
     "dvid_bbox_aug_merge": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p] * 5),
+    "dvid_overlay_detections": (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
+                                        c_float, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "dvid_overlay_scratch_bytes": (c_int64, [c_int, c_int]),
+    "dvid_overlay_tile": (c_int, [C.POINTER(c_int), C.POINTER(c_int)]),
     "dvid_igemm_num_configs": (c_int, []),
     "dvid_igemm_set_config": (c_int, [c_int]),
     "dvid_igemm_set_tuning": (c_int, [c_int]),

@@ -73,6 +73,13 @@ int dvid_resize_views_u8_launch(const unsigned char* const* srcs, int n, const l
 // bboxaug.hip
 int dvid_bbox_aug_merge_launch(const float* boxes, const float* scores, const int* labels, const int* counts, const float* table, int n, int V,
                                int cap, float* cand_boxes, float* cand_scores, int* cand_labels, int* live, hipStream_t s);
+// overlay.hip: overlay_prepare_kernel (one workgroup per frame: select, sort, map, colour, text -> the frame's draw list in `lists`) and
+// overlay_draw_kernel (one workgroup per tile and frame: cull, resolve, store); lists holds dvid_overlay_scratch_bytes_for(n) bytes
+int dvid_overlay_launch(unsigned char* const* frames, const int* sizes, int n, int max_h, int max_w, const float* dets, const int* counts, int cap,
+                        const float* ratios, const unsigned char* names, int num_classes, const unsigned char* atlas, int gh, int gw,
+                        float threshold, int thickness, int text_scale, int* lists, hipStream_t s);
+long long dvid_overlay_scratch_bytes_for(int n);
+void dvid_overlay_tile_size(int* tw, int* th);
 // fc = x * (scale[frame] + 1) + shift  (shift per frame [B,D] or per row [R,D])
 int dvid_modulate_launch(const float* x, const float* scale, int scale_ld, const float* shift, int shift_per_row, int shift_ld,
                          half_t* y16, int rows, int rows_per_frame, int d, hipStream_t s);

@@ -664,4 +664,47 @@ int dvid_bbox_aug_merge(const float* boxes, const float* scores, const int* labe
                                    reinterpret_cast<hipStream_t>(stream)));
     return DVID_OK;
 }
+
+int64_t dvid_overlay_scratch_bytes(int n, int cap) {
+    (void)cap;          // the rows are sorted in LDS: the draw lists are all the scratch there is
+    return n < 0 ? 0 : dvid_overlay_scratch_bytes_for(n);
+}
+
+int dvid_overlay_tile(int* tile_w, int* tile_h) {
+    g_err[0] = 0;
+    if (!tile_w || !tile_h) FAIL(DVID_ERR_ARG, "overlay tile: null pointer");
+    dvid_overlay_tile_size(tile_w, tile_h);
+    return DVID_OK;
+}
+
+int dvid_overlay_detections(void* const* frames, const int* sizes, const int* sizes_host, int n, const float* dets, const int* counts, int cap,
+                            const float* ratios, const unsigned char* names, int num_classes, const unsigned char* atlas, int gh, int gw,
+                            float threshold, int thickness, int text_scale, void* scratch, int64_t scratch_bytes, void* stream) {
+    g_err[0] = 0;
+    if (!frames || !sizes || !sizes_host || !dets || !counts || !ratios || !names || !atlas || !scratch) FAIL(DVID_ERR_ARG, "overlay: null pointer");
+    if (n < 1 || n > 65535 || cap < 1 || num_classes < 1 || gh < 1 || gw < 1)
+        FAIL(DVID_ERR_ARG, "overlay: bad sizes (%d frames, cap %d, %d classes, glyph cell %d x %d)", n, cap, num_classes, gw, gh);
+    if (!(threshold == threshold)) FAIL(DVID_ERR_ARG, "overlay: the threshold is NaN");
+    if (cap > DVID_NMS_MAX_CANDIDATES)
+        FAIL(DVID_ERR_UNSUPPORTED, "overlay: %d rows per frame exceed the limit of %d (DVID_NMS_MAX_CANDIDATES)", cap, DVID_NMS_MAX_CANDIDATES);
+    if (num_classes > DVID_MAX_CLASSES)
+        FAIL(DVID_ERR_UNSUPPORTED, "overlay: %d classes exceed the limit of %d (DVID_MAX_CLASSES)", num_classes, DVID_MAX_CLASSES);
+    if (gh > 32 || gw > 32) FAIL(DVID_ERR_UNSUPPORTED, "overlay: a glyph cell of %d x %d exceeds the limit of 32 x 32", gw, gh);
+    if (thickness < 1 || thickness > 16) FAIL(DVID_ERR_UNSUPPORTED, "overlay: thickness %d, the limits are 1 .. 16", thickness);
+    if (text_scale < 1 || text_scale > 4) FAIL(DVID_ERR_UNSUPPORTED, "overlay: text_scale %d, the limits are 1 .. 4", text_scale);
+    const long long need = dvid_overlay_scratch_bytes_for(n);
+    if (scratch_bytes < need)
+        FAIL(DVID_ERR_UNSUPPORTED, "overlay: %lld bytes of scratch, %d frames need %lld (dvid_overlay_scratch_bytes)", (long long)scratch_bytes, n, need);
+    if ((uintptr_t)scratch & 3) FAIL(DVID_ERR_ARG, "overlay: the scratch must be 4-byte aligned");
+    int max_h = 0, max_w = 0;
+    for (int i = 0; i < n; ++i) {          // the grid comes from the host's copy of the sizes
+        const int h = sizes_host[2 * i], w = sizes_host[2 * i + 1];
+        if (h < 1 || w < 1 || h > 65535 || w > 65535) FAIL(DVID_ERR_ARG, "overlay: frame %d is %d x %d, the limits are 1 .. 65535", i, h, w);
+        if (h > max_h) max_h = h;
+        if (w > max_w) max_w = w;
+    }
+    TRY(dvid_overlay_launch(reinterpret_cast<unsigned char* const*>(frames), sizes, n, max_h, max_w, dets, counts, cap, ratios, names, num_classes,
+                            atlas, gh, gw, threshold, thickness, text_scale, reinterpret_cast<int*>(scratch), reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
 }  // extern "C"

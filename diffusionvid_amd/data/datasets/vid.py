@@ -45,6 +45,27 @@ class VIDFrameList:
         self.frame_seg_id = [int(r[2]) for r in rows]
         self.frame_seg_len = [int(r[3]) for r in rows]
 
+    @classmethod
+    def from_lengths(cls, lengths):
+        """the frame list of videos given as {video name: n_frames}, in the mapping's order, without an index file: what the lines
+        "name frame_no seg_id n_frames" (frame_no counting from 1 over the whole list, seg_id from 0 within the video) would give"""
+        self = cls.__new__(cls)
+        self.video_format = True
+        self.image_set_index, self.pattern, self.frame_id, self.frame_seg_id, self.frame_seg_len = [], [], [], [], []
+        for name, n in lengths.items():
+            name, n = str(name), int(n)
+            if n < 1 or " " in name:
+                raise ValueError("video %r with %d frames: names carry no blank and a video has a frame" % (name, n))
+            for f in range(n):
+                self.image_set_index.append("%s/%06d" % (name, f))
+                self.pattern.append(name + "/%06d")
+                self.frame_id.append(len(self.frame_id) + 1)
+                self.frame_seg_id.append(f)
+                self.frame_seg_len.append(n)
+        if not self.image_set_index:
+            raise ValueError("an empty frame list")
+        return self
+
     def __len__(self):
         return len(self.image_set_index)
 
@@ -117,7 +138,7 @@ class VIDMEGATestDataset:
 
     def __init__(self, cfg, img_dir, img_index, transform=None, loader=None, rng=None, size_divisible=None, anno_path=None,
                  anno_cache=None):
-        self.frames = VIDFrameList(img_index)
+        self.frames = img_index if isinstance(img_index, VIDFrameList) else VIDFrameList(img_index)          # a path, or a list made elsewhere
         self.annotations = VIDAnnotations(self.frames, anno_path, anno_cache) if (anno_path or anno_cache) else None
         if not self.frames.video_format:
             raise ValueError("%s is not a video frame list (4 columns expected)" % img_index)

@@ -399,6 +399,53 @@ def bbox_aug_finish(cand_boxes, cand_scores, cand_labels, live, sizes, iou, max_
     return ob, osc, ol, oc
 
 
+# ---- the demo surface (csrc/overlay.hip; engine/demo.py) -----------------------------------------------------------------------------------
+OVERLAY_MAX_DRAWN = 256          # DVID_OVERLAY_MAX_DRAWN of include/dvid_hip.h: rows drawn per frame, the latest in draw order
+OVERLAY_NAME_MAX = 24            # DVID_OVERLAY_NAME_MAX: bytes of a class name on a plate
+OVERLAY_TILE = (64, 16)          # (tw, th): the pixels one workgroup of the draw kernel resolves (dvid_overlay_tile)
+
+
+def overlay_scratch_bytes(n, cap):
+    """bytes of scratch dvid_overlay_detections needs for n frames of `cap` rows: the frames' draw lists"""
+    return int(_lib.load().dvid_overlay_scratch_bytes(int(n), int(cap)))
+
+
+def overlay_detections(frames, dets, counts, ratios, names, atlas, threshold=0.7, thickness=2, text_scale=1):
+    """Paint detections onto uint8 RGB frames on the device, in place (the contract: include/dvid_hip.h, dvid_overlay_detections).
+    frames: one CUDA uint8 tensor [n, H, W, 3] or a list of n [h_i, w_i, 3] CUDA tensors; dets fp32 [n, cap, 6] = box, score, label in the
+    model's frame, counts int32 [n]; ratios fp32 [n, 2] = (rw, rh), native / model size; names uint8 [num_classes + 1, 24]
+    (engine.demo.name_table); atlas uint8 [95, gh, gw] of 0 / 1 (engine.demo.glyph_atlas).  Returns `frames`.  Scores stay on the device:
+    two launches on the current stream, no synchronisation."""
+    batch = isinstance(frames, torch.Tensor)
+    images = list(frames.unbind(0)) if batch and frames.dim() == 4 else ([frames] if batch else list(frames))
+    if batch and frames.dim() != 4:
+        raise _lib.DvidError(f"overlay_detections: frames are [n, H, W, 3] or a list of [h, w, 3], got {tuple(frames.shape)}")
+    for t in images:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3 and t.is_contiguous()):
+            raise _lib.DvidError("overlay_detections: every frame is a contiguous CUDA uint8 [h, w, 3] tensor (drawn in place)")
+    n = len(images)
+    dev = images[0].device if n else None
+    dets, counts, ratios = _cuda(dets, torch.float32), _cuda(counts, torch.int32), _cuda(ratios, torch.float32)
+    names, atlas = _cuda(names, torch.uint8), _cuda(atlas, torch.uint8)
+    if n == 0 or dets.dim() != 3 or dets.shape[0] != n or dets.shape[2] != 6 or counts.shape != (n,) or ratios.shape != (n, 2):
+        raise _lib.DvidError(f"overlay_detections: {n} frames take dets [n, cap, 6], counts [n] and ratios [n, 2], got {tuple(dets.shape)}, "
+                             f"{tuple(counts.shape)}, {tuple(ratios.shape)}")
+    if names.dim() != 2 or names.shape[0] < 2 or names.shape[1] != OVERLAY_NAME_MAX or atlas.dim() != 3 or atlas.shape[0] != 95:
+        raise _lib.DvidError(f"overlay_detections: names are [num_classes + 1, {OVERLAY_NAME_MAX}] and the atlas [95, gh, gw], got "
+                             f"{tuple(names.shape)}, {tuple(atlas.shape)}")
+    cap = dets.shape[1]
+    if cap == 0:
+        return frames
+    host_sizes = torch.tensor([(t.shape[0], t.shape[1]) for t in images], dtype=torch.int32)
+    table = torch.tensor([t.data_ptr() for t in images], dtype=torch.int64).to(dev)
+    sizes = host_sizes.to(dev)
+    scratch = torch.empty((overlay_scratch_bytes(n, cap) // 4,), dtype=torch.int32, device=dev)
+    call("dvid_overlay_detections", ptr(table), ptr(sizes), ptr(host_sizes), n, ptr(dets), ptr(counts), cap, ptr(ratios), ptr(names),
+         names.shape[0] - 1, ptr(atlas), atlas.shape[1], atlas.shape[2], float(threshold), int(thickness), int(text_scale), ptr(scratch),
+         scratch.numel() * 4, stream_ptr())
+    return frames
+
+
 class FrameSizes:
     """The per-frame size table of the `_sizes` entry points, checked once on the host and uploaded once: rows (w, h) fp32 [n, 2], every
     entry positive and finite.  `fs[a:b]` is the table of frames a..b (views of both copies, nothing checked or uploaded again)."""

@@ -539,6 +539,34 @@ int dvid_resize_views_u8(const void* const* srcs, int n, const long long* plan, 
 int dvid_bbox_aug_merge(const float* boxes, const float* scores, const int* labels, const int* counts, const float* table, int n, int views,
                         int cap, float* cand_boxes, float* cand_scores, int* cand_labels, int* live, void* stream);
 
+/* The demo surface (dvid_version >= 10; csrc/overlay.hip; the reference's demo/predictor.py: select_top_predictions, overlay_boxes,
+ * overlay_class_names): the detections of n frames painted onto them in place, two launches however many frames.
+ * frames: DEVICE table of n pointers to uint8 RGB [h_i][w_i][3] at the image's native size (row pitch w_i * 3 bytes, no alignment asked);
+ * sizes (device) and sizes_host (the same rows on the host: the grid, checked before anything is launched): int32 [n][2] = (h, w),
+ * each 1 .. 65535.  dets fp32 [n][cap][6] = x1, y1, x2, y2, score, label in the model's frame, counts int32 [n]: rows at and beyond
+ * counts[i] are never read for meaning.  ratios fp32 [n][2] = (rw, rh), native / model size.
+ * A row is drawn iff its corners and score are finite and score > threshold (fp32, strict); draw order is ascending score, then
+ * ascending row; the last DVID_OVERLAY_MAX_DRAWN in that order are kept.  Each corner is one fp32 product with its axis' ratio,
+ * truncated toward zero and clamped to int32; corners are inclusive; a kept row with x2 < x1 or y2 < y1 is skipped.  Colour: with L the
+ * truncated label, c_k = (L * (2^25 - 1, 2^15 - 1, 2^21 - 1)_k) mod 255 (non-negative), shown as R = c_2, G = c_1, B = c_0.
+ * Ring of `thickness` t (1 .. 16), o = t / 2, i = t - o: [x1 - o, x2 + o] x [y1 - o, y2 + o] minus [x1 + i, x2 - i] x [y1 + i, y2 - i].
+ * Text: names[L] (uint8 [num_classes + 1][DVID_OVERLAY_NAME_MAX], zero-padded, bytes 32 .. 126; a label outside 0 .. num_classes has
+ * none) + ": " + the score as "%.2f" prints it (correctly rounded, ties to even; hundredths clamped to 999), the score alone without a
+ * name.  Plate: with n characters, s = text_scale (1 .. 4) and pad = s, [x1, x1 + n * gw * s + 2 * pad - 1] x [y1, y1 + gh * s + 2 * pad - 1]
+ * in the colour, white (255) where atlas (uint8 [95][gh][gw] of 0 / 1 for the characters 32 .. 126, gh, gw <= 32) holds 1 at the
+ * pixel's cell, each atlas pixel s x s frame pixels.  Layers: a pixel takes the latest plate that covers it, else the latest ring,
+ * else it is not written.  Everything is clipped to the frame.
+ * DVID_ERR_UNSUPPORTED, with the numbers, before anything is launched: cap > DVID_NMS_MAX_CANDIDATES, num_classes > DVID_MAX_CLASSES,
+ * a glyph cell beyond 32, thickness or text_scale out of range, scratch_bytes < dvid_overlay_scratch_bytes(n, cap). */
+#define DVID_OVERLAY_MAX_DRAWN 256
+#define DVID_OVERLAY_NAME_MAX 24
+int dvid_overlay_detections(void* const* frames, const int* sizes, const int* sizes_host, int n, const float* dets, const int* counts, int cap,
+                            const float* ratios, const unsigned char* names, int num_classes, const unsigned char* atlas, int gh, int gw,
+                            float threshold, int thickness, int text_scale, void* scratch, int64_t scratch_bytes, void* stream);
+int64_t dvid_overlay_scratch_bytes(int n, int cap);
+/* the pixel tile one workgroup of the draw kernel resolves (the tests place boxes on its edges) */
+int dvid_overlay_tile(int* tile_w, int* tile_h);
+
 /* ---- options ------------------------------------------------------------------------------
  * The library's behaviour switches are ONE table set through this ABI, never through the environment (csrc/options.h; the defaults
  * are the benchmarked configuration).  Names: conv3x3, wstat, bneck_fuse (0 off / 1 by the layer's shape rule / 2 wherever the layer
