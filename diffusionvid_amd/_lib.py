@@ -121,6 +121,10 @@ SIGNATURES = {
                                         c_float, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "dvid_overlay_scratch_bytes": (c_int64, [c_int, c_int]),
     "dvid_overlay_tile": (c_int, [C.POINTER(c_int), C.POINTER(c_int)]),
+    "dvid_jpeg_parse": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int]),
+    "dvid_jpeg_entropy_decode": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int]),
+    "dvid_jpeg_reconstruct_u8": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64,
+                                         c_void_p]),
     "dvid_igemm_num_configs": (c_int, []),
     "dvid_igemm_set_config": (c_int, [c_int]),
     "dvid_igemm_set_tuning": (c_int, [c_int]),

@@ -80,6 +80,10 @@ int dvid_overlay_launch(unsigned char* const* frames, const int* sizes, int n, i
                         float threshold, int thickness, int text_scale, int* lists, hipStream_t s);
 long long dvid_overlay_scratch_bytes_for(int n);
 void dvid_overlay_tile_size(int* tw, int* th);
+// jpeg.hip: jpeg_idct_kernel (8 lanes per 8x8 block -> uint8 component planes) and jpeg_colour_kernel (upsample + YCbCr -> RGB), n frames by
+// the rows of `plan`; max_blocks: the most blocks any frame has over its components, max_w / max_h: the widest / tallest frame
+int dvid_jpeg_reconstruct_launch(const short* coef, const unsigned short* quant, const long long* plan, int n, int max_blocks, int max_w, int max_h,
+                                 unsigned char* planes, unsigned char* out, hipStream_t s);
 // fc = x * (scale[frame] + 1) + shift  (shift per frame [B,D] or per row [R,D])
 int dvid_modulate_launch(const float* x, const float* scale, int scale_ld, const float* shift, int shift_per_row, int shift_ld,
                          half_t* y16, int rows, int rows_per_frame, int d, hipStream_t s);

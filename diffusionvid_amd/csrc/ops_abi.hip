@@ -665,6 +665,49 @@ int dvid_bbox_aug_merge(const float* boxes, const float* scores, const int* labe
     return DVID_OK;
 }
 
+int dvid_jpeg_reconstruct_u8(const int16_t* coef, int64_t n_coef, const uint16_t* quant, int64_t n_quant, const long long* plan,
+                             const long long* plan_host, int n, void* planes, int64_t planes_bytes, void* out, int64_t out_bytes, void* stream) {
+    g_err[0] = 0;
+    if (!coef || !quant || !plan || !plan_host || !planes || !out) FAIL(DVID_ERR_ARG, "jpeg reconstruct: null pointer");
+    if (n < 1 || n_coef < 1 || n_quant < 1 || out_bytes < 1) FAIL(DVID_ERR_ARG, "jpeg reconstruct: %d frames, %lld coefficients, %lld table entries, %lld output bytes", n, (long long)n_coef, (long long)n_quant, (long long)out_bytes);
+    if (n > 65535) FAIL(DVID_ERR_UNSUPPORTED, "jpeg reconstruct: %d frames exceed the limit of 65535 per call", n);
+    if (n_coef > DVID_JPEG_MAX_COEFS)
+        FAIL(DVID_ERR_UNSUPPORTED, "jpeg reconstruct: %lld coefficients exceed the limit of %lld (DVID_JPEG_MAX_COEFS: int32 indices)", (long long)n_coef, DVID_JPEG_MAX_COEFS);
+    if (planes_bytes < n_coef) FAIL(DVID_ERR_ARG, "jpeg reconstruct: the planes hold %lld bytes, %lld coefficients need as many", (long long)planes_bytes, (long long)n_coef);
+    if (((uintptr_t)coef | (uintptr_t)quant) & 15 || (uintptr_t)planes & 7) FAIL(DVID_ERR_ARG, "jpeg reconstruct: coef and quant must be 16-byte aligned, planes 8-byte aligned");
+    long long coef_end = 0, out_end = 0;
+    int max_blocks = 0, max_w = 0, max_h = 0;
+    for (int i = 0; i < n; ++i) {          // every offset the kernels add is checked here, against the sizes of what they index
+        const long long* d = plan_host + (long)i * DVID_JPEG_PLAN_COLS;
+        const long long w = d[0], h = d[1], nc = d[2], hs = d[3], vs = d[4];
+        if (w < 1 || h < 1 || w > 65535 || h > 65535) FAIL(DVID_ERR_ARG, "jpeg reconstruct: frame %d is %lld x %lld (1 .. 65535 each)", i, w, h);
+        if ((nc != 1 && nc != 3) || !((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2)) || (nc == 1 && hs * vs != 1))
+            FAIL(DVID_ERR_ARG, "jpeg reconstruct: frame %d has %lld components with luma sampling %lld x %lld (1 component at 1x1, or 3 at 1x1, 2x1, 2x2)", i, nc, hs, vs);
+        const long long mw = (w + 8 * hs - 1) / (8 * hs), mh = (h + 8 * vs - 1) / (8 * vs);
+        const long long blocks[3] = {mw * hs * mh * vs, nc == 3 ? mw * mh : 0, nc == 3 ? mw * mh : 0};
+        for (int c = 0; c < nc; ++c) {
+            const long long off = d[5 + c];
+            if (off < coef_end || off % 64)
+                FAIL(DVID_ERR_ARG, "jpeg reconstruct: component %d of frame %d starts at coefficient %lld: offsets are multiples of 64 and ascend without overlap (the one before ends at %lld)", c, i, off, coef_end);
+            coef_end = off + blocks[c] * 64;
+            if (coef_end > n_coef)
+                FAIL(DVID_ERR_ARG, "jpeg reconstruct: component %d of frame %d ends at coefficient %lld, the buffer holds %lld", c, i, coef_end, (long long)n_coef);
+        }
+        if (d[8] < 0 || d[8] % 64 || d[8] + 64 * nc > n_quant)
+            FAIL(DVID_ERR_ARG, "jpeg reconstruct: the tables of frame %d start at entry %lld of %lld (a multiple of 64, %lld entries)", i, d[8], (long long)n_quant, 64 * nc);
+        if (d[9] < out_end) FAIL(DVID_ERR_ARG, "jpeg reconstruct: frame %d's pixels start at byte %lld and overlap the frame before, which ends at %lld", i, d[9], out_end);
+        out_end = d[9] + h * w * 3;
+        if (out_end > out_bytes) FAIL(DVID_ERR_ARG, "jpeg reconstruct: frame %d's pixels end at byte %lld, the output holds %lld", i, out_end, (long long)out_bytes);
+        const long long nb = blocks[0] + blocks[1] + blocks[2];
+        if (nb > max_blocks) max_blocks = (int)nb;
+        if (w > max_w) max_w = (int)w;
+        if (h > max_h) max_h = (int)h;
+    }
+    TRY(dvid_jpeg_reconstruct_launch(coef, quant, plan, n, max_blocks, max_w, max_h, reinterpret_cast<unsigned char*>(planes),
+                                     reinterpret_cast<unsigned char*>(out), reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
 int64_t dvid_overlay_scratch_bytes(int n, int cap) {
     (void)cap;          // the rows are sorted in LDS: the draw lists are all the scratch there is
     return n < 0 ? 0 : dvid_overlay_scratch_bytes_for(n);

@@ -41,6 +41,9 @@ class StillImageDataset:
                 from PIL import Image
                 with Image.open(self.files[idx]) as im:
                     self._sizes[idx] = (int(im.size[0]), int(im.size[1]))
+            elif hasattr(self.loader, "size"):          # a loader that reads headers (data/jpeg.py: DeviceJpegLoader): no decode for a size
+                w, h = self.loader.size(self.files[idx])
+                self._sizes[idx] = (int(w), int(h))
             else:
                 h, w = self.loader(self.files[idx]).shape[:2]
                 self._sizes[idx] = (int(w), int(h))

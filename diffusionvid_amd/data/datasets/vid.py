@@ -12,9 +12,11 @@
                       `get_img_info` / `get_groundtruth` -- what `do_vid_evaluation` asks a dataset for.  Not on the hot
                       path: items still carry None as target, exactly as the reference's test items are not read there.
 
-Frames: `loader(path) -> uint8 HWC RGB` (default: Pillow decode on the host -- JPEG decode stays a CPU job, as the
-reference's 16 DataLoader workers do it); `transform(image, is_current)` = data/transforms.ResizeToTensor (host, Pillow:
-the reference's path) or ResizeToTensorDevice (uint8 upload, resize + /255 + padding in HIP kernels).
+Frames: `loader(path) -> uint8 HWC RGB` (default: Pillow decode on the host, as the reference's 16 DataLoader workers do
+it; data/jpeg.py's DeviceJpegLoader instead keeps only the Huffman stage of a baseline JPEG on the host and returns the
+frame as a CUDA tensor with Pillow's bits, Pillow's numpy array for a file outside the split); `transform(image, is_current)`
+= data/transforms.ResizeToTensor (host, Pillow: the reference's path) or ResizeToTensorDevice (a uint8 upload, or the
+loader's CUDA tensor as it is; resize + /255 + padding in HIP kernels).
 """
 import os
 

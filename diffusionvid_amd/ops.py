@@ -446,6 +446,36 @@ def overlay_detections(frames, dets, counts, ratios, names, atlas, threshold=0.7
     return frames
 
 
+JPEG_PLAN_COLS = 10          # DVID_JPEG_PLAN_COLS
+
+
+def jpeg_reconstruct_u8(coef, quant, plan_host, plan=None):
+    """The device half of the split JPEG decode (the contract: include/dvid_hip.h, dvid_jpeg_reconstruct_u8): dequantise, ISLOW IDCT,
+    fancy upsampling, YCbCr -> RGB, equal to libjpeg's (Pillow's) decode bit for bit.  coef: CUDA int16 [n_coef], the coefficients of n
+    frames as data.jpeg.entropy_decode leaves them; quant: CUDA int16 holding the uint16 tables' bits, 192 per frame; plan_host: int64
+    [n, JPEG_PLAN_COLS] on the host (data.jpeg.plan_rows), checked by the library before anything is launched; plan: the same rows on
+    the device (uploaded here when None).  -> a list of n CUDA uint8 [h_i, w_i, 3] tensors, views of one buffer.  Two launches on the
+    current stream however many frames, no synchronisation."""
+    coef, quant = _cuda(coef, torch.int16), _cuda(quant, torch.int16)
+    plan_host = torch.as_tensor(plan_host)
+    if plan_host.is_cuda or plan_host.dtype != torch.int64 or plan_host.dim() != 2 or plan_host.shape[1] != JPEG_PLAN_COLS or plan_host.shape[0] < 1:
+        raise _lib.DvidError(f"jpeg_reconstruct_u8: the plan is a host int64 [n, {JPEG_PLAN_COLS}] tensor, got {plan_host.dtype} {tuple(plan_host.shape)}")
+    plan_host = plan_host.contiguous()
+    n = plan_host.shape[0]
+    dev = coef.device
+    plan = plan_host.to(dev) if plan is None else _cuda(plan, torch.int64)
+    if plan.shape != plan_host.shape:
+        raise _lib.DvidError("jpeg_reconstruct_u8: the device plan and the host plan differ in shape")
+    w, h, off = plan_host[:, 0], plan_host[:, 1], plan_host[:, 9]
+    sane = bool(((w >= 1) & (w <= 65535) & (h >= 1) & (h <= 65535) & (off >= 0) & (off < 2 ** 44)).all())
+    out_bytes = int((off + h * w * 3).max()) if sane else 1          # a plan the library is about to refuse: nothing to size the output by
+    out = torch.empty((out_bytes,), dtype=torch.uint8, device=dev)
+    planes = torch.empty((coef.numel(),), dtype=torch.uint8, device=dev)
+    call("dvid_jpeg_reconstruct_u8", ptr(coef), coef.numel(), ptr(quant), quant.numel(), ptr(plan), ptr(plan_host), n, ptr(planes), planes.numel(),
+         ptr(out), out_bytes, stream_ptr())
+    return [out[int(o):int(o) + int(hh) * int(ww) * 3].view(int(hh), int(ww), 3) for ww, hh, o in zip(w.tolist(), h.tolist(), off.tolist())]
+
+
 class FrameSizes:
     """The per-frame size table of the `_sizes` entry points, checked once on the host and uploaded once: rows (w, h) fp32 [n, 2], every
     entry positive and finite.  `fs[a:b]` is the table of frames a..b (views of both copies, nothing checked or uploaded again)."""

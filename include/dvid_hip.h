@@ -567,6 +567,50 @@ int64_t dvid_overlay_scratch_bytes(int n, int cap);
 /* the pixel tile one workgroup of the draw kernel resolves (the tests place boxes on its edges) */
 int dvid_overlay_tile(int* tile_w, int* tile_h);
 
+/* ---- split JPEG decode (dvid_version >= 11) --------------------------------------------------
+ * The entropy (Huffman) stage runs on the host (csrc/jpeg_host.cpp, plain C++), everything behind it on the device (csrc/jpeg.hip), and
+ * the result equals libjpeg's default decode bit for bit: ISLOW integer IDCT, "fancy" triangle upsampling, 16-bit fixed-point colour.
+ *
+ * Accepted files: SOF0 (baseline, 8-bit, Huffman), one interleaved scan, one component or three in YCbCr (a JFIF APP0 marker, or Adobe
+ * APP14 with transform 1, or neither and component ids 1, 2, 3), luma sampling 1x1, 2x1 or 2x2 with chroma 1x1, 8-bit quantisation
+ * tables; any Huffman tables, DRI / RSTn, stuffed FF 00.  DVID_ERR_UNSUPPORTED from dvid_jpeg_parse, the reason in the message:
+ * progressive, arithmetic coding, 12-bit, SOF1, several scans, four components, Adobe transform 0 or 2, other sampling factors, 16-bit
+ * quantisation tables, DNL or zero height.  Malformed data is DVID_ERR_ARG; no byte outside [data, data + size) is read.
+ *
+ * The two host entries call no HIP function and initialise no GPU (worker processes call them), keep no state and write their message
+ * into the caller's `err` (err_cap bytes, may be NULL): they are re-entrant, and dvid_last_error does not speak for them.
+ * dvid_jpeg_info holds no pointers.  Component c has a padded grid of blocks_w[c] x blocks_h[c] 8x8 blocks, blocks_w = ceil(width /
+ * (8 * hmax)) * hsamp[c] and likewise down; its coefficients start at element coef_offset[c], blocks in raster order of that grid, 64
+ * int16 per block in natural (de-zigzagged) order, NOT dequantised; coef_count is the total.  quant[c] is component c's table in natural
+ * order.  A single component always reports sampling 1x1. */
+typedef struct dvid_jpeg_info {
+    int32_t width, height, ncomp;
+    int32_t hsamp[3], vsamp[3];
+    int32_t blocks_w[3], blocks_h[3];
+    int32_t reserved;
+    int64_t coef_offset[3];
+    int64_t coef_count;
+    uint16_t quant[3][64];
+} dvid_jpeg_info;
+int dvid_jpeg_parse(const void* data, int64_t size, dvid_jpeg_info* info, char* err, int err_cap);
+/* parse + Huffman decode into coef[0 .. coef_count) (coef_cap: elements the buffer holds; zeroed first); info may be NULL */
+int dvid_jpeg_entropy_decode(const void* data, int64_t size, int16_t* coef, int64_t coef_cap, dvid_jpeg_info* info, char* err, int err_cap);
+/* The device half: n frames, each with its own size and sampling, in two launches however many frames (IDCT into uint8 component planes,
+ * then upsample + colour into packed RGB).  coef: int16 [n_coef], the frames' coefficients one after the other; quant: uint16 [n_quant],
+ * 192 entries (quant[3][64]) per frame; planes: >= n_coef bytes of scratch, 8-byte aligned (component samples, at the coefficients' own
+ * offsets); out: uint8 [out_bytes], frame i as [h_i][w_i][3] RGB at byte out_off_i, a one-component frame with R = G = B.
+ * plan (device) and plan_host (the same rows on the host, checked before anything is launched): int64 [n][DVID_JPEG_PLAN_COLS] = width,
+ * height, ncomp, luma hsamp, luma vsamp, coef_offset[0..2] (elements into coef), the first entry of its tables in quant, out_off.
+ * No address in either kernel depends on a coefficient's value: a corrupt file gives wrong pixels inside its own image.
+ * DVID_ERR_ARG, with the numbers: a null pointer, a sampling outside 1x1 / 2x1 / 2x2, offsets that are not 64-element aligned, do not
+ * ascend (overlap) or leave their buffers.  DVID_ERR_UNSUPPORTED: n > 65535 or n_coef > DVID_JPEG_MAX_COEFS -- the kernels index
+ * coefficients and plane samples with int32, and 2^31 - 1 coefficients are 1.4 gigapixels of 4:2:0 per call; pixel offsets are 64-bit
+ * (one 65535 x 65535 frame alone would be 12.9 GB of RGB). */
+#define DVID_JPEG_PLAN_COLS 10
+#define DVID_JPEG_MAX_COEFS 2147483647LL
+int dvid_jpeg_reconstruct_u8(const int16_t* coef, int64_t n_coef, const uint16_t* quant, int64_t n_quant, const long long* plan,
+                             const long long* plan_host, int n, void* planes, int64_t planes_bytes, void* out, int64_t out_bytes, void* stream);
+
 /* ---- options ------------------------------------------------------------------------------
  * The library's behaviour switches are ONE table set through this ABI, never through the environment (csrc/options.h; the defaults
  * are the benchmarked configuration).  Names: conv3x3, wstat, bneck_fuse (0 off / 1 by the layer's shape rule / 2 wherever the layer
