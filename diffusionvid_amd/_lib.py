@@ -91,6 +91,10 @@ SIGNATURES = {
     "dvid_lvis_eval_match": (c_int, [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 14 + [c_int] + [c_void_p] * 5),
     "dvid_eval_accumulate": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 3 + [c_int64, c_void_p]),
     "dvid_eval_accumulate_scratch_bytes": (c_int64, [c_int, c_int, c_int]),
+    "dvid_q_sample_boxes": (c_int, [c_void_p] * 3 + [c_int, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_float] + [c_void_p] * 3),
+    "dvid_set_criterion": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 5 + [c_float, c_float, c_int] + [c_float] * 3 +
+                           [c_void_p, c_void_p, c_int] + [c_void_p] * 3 + [c_int64, c_void_p]),
+    "dvid_set_criterion_scratch_bytes": (c_int64, [c_int] * 4),
     "dvid_cdist":(c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "dvid_fps_greedy": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dvid_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

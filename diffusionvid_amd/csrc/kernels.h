@@ -197,6 +197,14 @@ int dvid_ddim_renew_launch(const float* logits, const float* boxes, const float*
                            float* out, int n_img, int m, int c, float w, float h, float scale, float sra, float srm1, float sqrt_an,
                            float cc, float sigma, float thr, hipStream_t s);
 
+// criterion.hip
+int dvid_q_sample_boxes_launch(const float* gt, const int* gt_starts, int n, int m, const int* t, const float* sqrt_ac, const float* sqrt_omac,
+                               int timesteps, const float* noise, const float* placeholder, float scale, const float* sizes, float* out, hipStream_t s);
+long long dvid_set_criterion_scratch_bytes_host(int n_sets, int n, int m, int gmax);
+int dvid_set_criterion_launch(const float* logits, const float* boxes, int n_sets, int n, int m, int c, const float* gt_boxes, const int* gt_labels,
+                              const int* gt_starts, const float* sizes, float alpha, float gamma, int ota_k, float cost_class, float cost_bbox,
+                              float cost_giou, int* assign, int* matched_query, int gmax, double* sums, int* status, void* scratch, hipStream_t s);
+
 // postproc.hip
 int dvid_topk_candidates_launch(const float* logits, const float* boxes, int n_img, int nsets, int m, int c, float* cand_boxes,
                                 float* cand_scores, int* cand_labels, hipStream_t s);

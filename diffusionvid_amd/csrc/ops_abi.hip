@@ -313,6 +313,65 @@ int dvid_vid_eval_match(const float* dets, const int* counts, int n_frames, int 
     return DVID_OK;
 }
 
+int dvid_q_sample_boxes(const float* gt_cxcywh, const int* gt_starts, const int* gt_starts_host, int n, int m, const int* t, const int* t_host,
+                        const float* sqrt_ac, const float* sqrt_omac, int timesteps, const float* noise, const float* placeholder, float snr_scale,
+                        const float* sizes, float* boxes, void* stream) {
+    g_err[0] = 0;
+    if (n < 0 || m < 1 || timesteps < 1) FAIL(DVID_ERR_ARG, "q_sample_boxes: bad sizes (%d images, %d proposals, %d time steps)", n, m, timesteps);
+    if (n == 0) return DVID_OK;
+    if (!gt_starts || !gt_starts_host || !t || !t_host || !sqrt_ac || !sqrt_omac || !noise || !placeholder || !sizes || !boxes)
+        FAIL(DVID_ERR_ARG, "q_sample_boxes: null pointer");
+    if (gt_starts_host[0] != 0) FAIL(DVID_ERR_ARG, "q_sample_boxes: gt_starts[0] is %d, not 0", gt_starts_host[0]);
+    for (int i = 0; i < n; ++i) {
+        const int g = gt_starts_host[i + 1] - gt_starts_host[i];
+        if (g < 0) FAIL(DVID_ERR_ARG, "q_sample_boxes: gt_starts decreases at image %d", i);
+        if (g > m)
+            FAIL(DVID_ERR_UNSUPPORTED, "q_sample_boxes: image %d holds %d ground-truth boxes, NUM_PROPOSALS is %d (the reference's random subset is not built)",
+                 i, g, m);
+        if (t_host[i] < 0 || t_host[i] >= timesteps) FAIL(DVID_ERR_ARG, "q_sample_boxes: t[%d] is %d, outside 0 .. %d", i, t_host[i], timesteps - 1);
+    }
+    if (gt_starts_host[n] > 0 && !gt_cxcywh) FAIL(DVID_ERR_ARG, "q_sample_boxes: null ground truth");
+    TRY(dvid_q_sample_boxes_launch(gt_cxcywh, gt_starts, n, m, t, sqrt_ac, sqrt_omac, timesteps, noise, placeholder, snr_scale, sizes, boxes,
+                                   reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
+int64_t dvid_set_criterion_scratch_bytes(int n_sets, int n, int m, int gmax) { return dvid_set_criterion_scratch_bytes_host(n_sets, n, m, gmax); }
+
+int dvid_set_criterion(const float* logits, const float* boxes, int n_sets, int n, int m, int c, const float* gt_boxes, const int* gt_labels,
+                       const int* gt_starts, const int* gt_starts_host, const float* sizes, float alpha, float gamma, int ota_k, float cost_class,
+                       float cost_bbox, float cost_giou, int* assign, int* matched_query, int gmax, double* sums, int* status, void* scratch,
+                       int64_t scratch_bytes, void* stream) {
+    g_err[0] = 0;
+    if (n_sets < 0 || n < 0 || m < 1 || c < 1 || gmax < 0) FAIL(DVID_ERR_ARG, "set criterion: bad sizes (%d head outputs, %d images, %d queries, %d classes)", n_sets, n, m, c);
+    if (ota_k < 1 || ota_k > DVID_CRITERION_MAX_OTA_K)
+        FAIL(DVID_ERR_UNSUPPORTED, "set criterion: OTA_K %d, the limit is 1 .. %d (DVID_CRITERION_MAX_OTA_K)", ota_k, DVID_CRITERION_MAX_OTA_K);
+    if (m < ota_k || m > DVID_CRITERION_MAX_ROWS)
+        FAIL(DVID_ERR_UNSUPPORTED, "set criterion: %d queries per image, the limit is OTA_K = %d <= queries <= %d (DVID_CRITERION_MAX_ROWS)", m, ota_k,
+             DVID_CRITERION_MAX_ROWS);
+    if (c > DVID_MAX_CLASSES) FAIL(DVID_ERR_UNSUPPORTED, "set criterion: %d classes exceed the limit of %d (DVID_MAX_CLASSES)", c, DVID_MAX_CLASSES);
+    if (gmax > DVID_CRITERION_MAX_GT)
+        FAIL(DVID_ERR_UNSUPPORTED, "set criterion: gmax %d exceeds the limit of %d (DVID_CRITERION_MAX_GT)", gmax, DVID_CRITERION_MAX_GT);
+    if ((long long)n_sets * n > 65535) FAIL(DVID_ERR_UNSUPPORTED, "set criterion: %d head outputs x %d images exceed 65535 sets per call", n_sets, n);
+    if (n_sets == 0 || n == 0) return DVID_OK;
+    if (!logits || !boxes || !gt_starts || !gt_starts_host || !sizes || !assign || !matched_query || !sums || !status) FAIL(DVID_ERR_ARG, "set criterion: null pointer");
+    if (gt_starts_host[0] != 0) FAIL(DVID_ERR_ARG, "set criterion: gt_starts[0] is %d, not 0", gt_starts_host[0]);
+    for (int i = 0; i < n; ++i) {
+        const int g = gt_starts_host[i + 1] - gt_starts_host[i];
+        if (g < 0) FAIL(DVID_ERR_ARG, "set criterion: gt_starts decreases at image %d", i);
+        if (g > DVID_CRITERION_MAX_GT)
+            FAIL(DVID_ERR_UNSUPPORTED, "set criterion: image %d holds %d ground-truth boxes, the limit is %d (DVID_CRITERION_MAX_GT)", i, g, DVID_CRITERION_MAX_GT);
+        if (g > gmax) FAIL(DVID_ERR_ARG, "set criterion: image %d holds %d ground-truth boxes, gmax is %d", i, g, gmax);
+    }
+    if (gt_starts_host[n] > 0 && (!gt_boxes || !gt_labels)) FAIL(DVID_ERR_ARG, "set criterion: null ground truth");
+    const long long need = dvid_set_criterion_scratch_bytes_host(n_sets, n, m, gmax);
+    if (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 15))
+        FAIL(DVID_ERR_ARG, "set criterion: the scratch holds %lld bytes, %lld are needed (16-byte aligned)", (long long)scratch_bytes, need);
+    TRY(dvid_set_criterion_launch(logits, boxes, n_sets, n, m, c, gt_boxes, gt_labels, gt_starts, sizes, alpha, gamma, ota_k, cost_class, cost_bbox, cost_giou,
+                                  assign, matched_query, gmax, sums, status, scratch, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
 int dvid_coco_eval_match(const float* dets, const int* counts, int n_images, int cap, const double* gt_boxes, const double* gt_areas,
                          const unsigned char* gt_crowd, const int* gt_labels, const int* gt_starts, const int* gt_starts_host,
                          const double* iou_thrs, const double* area_ranges, int num_classes, signed char* match, signed char* ignore,

@@ -483,3 +483,36 @@ def inference_images(model, loader, output_folder=None, label_map=None, annotati
                 json.dump(lvis_eval.lvis_results(predictions, label_map), f)
         return predictions, lvis_eval.do_lvis_evaluation(ann, predictions, output_folder, device=eval_device, accumulate=eval_accumulate)
     return predictions, coco_eval.do_coco_evaluation(ann, predictions, output_folder, device=eval_device, accumulate=eval_accumulate)
+
+
+def validation_losses(model, loader, output_folder=None):
+    """The weighted training losses of a labelled data set of still images, forward only: `loader` yields (images, targets, image_ids)
+    batches -- what model.compute_losses takes -- and every batch goes through model.loss_sums.  The set's losses are formed with the
+    reference's normalisation over the WHOLE set: the focal, L1 and 1 - GIoU sums and the matched counts of all batches are added (float64)
+    and divided once, per head output; per-batch ratios are not averaged, so the result does not depend on the batching.  -> an ordered
+    dict {loss_ce, loss_bbox, loss_giou, then `_0 .. _{S-2}`, and `total_loss`, their sum} of Python floats, times CLASS_WEIGHT / L1_WEIGHT /
+    GIOU_WEIGHT; with `output_folder` also written to `losses.txt`, one `name value` line each."""
+    import os
+    from collections import OrderedDict
+
+    from ..modeling.roi_heads.box_head.loss import losses_from_sums
+    total, seen = None, set()
+    for images, targets, image_ids in loader:
+        for i in image_ids:
+            if int(i) in seen:
+                raise ValueError("image id %d appears twice" % int(i))
+            seen.add(int(i))
+        sums, _ = model.loss_sums(images, targets, image_ids)
+        sums = sums.sum(1, keepdim=True)
+        total = sums if total is None else total + sums
+    if total is None:
+        raise ValueError("validation_losses: the loader yielded no batch")
+    weights = model._get_criterion().weight_dict
+    out = OrderedDict((k, v * weights.get(k, 1.0)) for k, v in losses_from_sums(total).items())
+    out["total_loss"] = sum(out.values())
+    if output_folder:
+        os.makedirs(output_folder, exist_ok=True)
+        with open(os.path.join(output_folder, "losses.txt"), "w") as f:
+            for k, v in out.items():
+                f.write("%s %.9g\n" % (k, v))
+    return out

@@ -472,6 +472,134 @@ class DiffusionDet(nn.Module):
         return outs
 
     # ---- still images with TEST.BBOX_AUG -------------------------------------------------------------------------------------------------
+    # ---- the forward of the training objective (diffusion_det.py:338-375, still batches) -------------------------------------------------
+    def _get_criterion(self):
+        """SetCriterionDynamicK over HungarianMatcherDynamicK with the weights of diffusion_det.py:275-299, built on first use: a config the
+        criterion refuses (USE_FED_LOSS) still detects"""
+        if getattr(self, "_criterion", None) is None:
+            from ..roi_heads.box_head.loss import HungarianMatcherDynamicK, SetCriterionDynamicK
+            d = self.cfg.MODEL.DiffusionDet
+            matcher = HungarianMatcherDynamicK(cfg=self.cfg, cost_class=d.CLASS_WEIGHT, cost_bbox=d.L1_WEIGHT, cost_giou=d.GIOU_WEIGHT, use_focal=self.use_focal)
+            weights = {"loss_ce": d.CLASS_WEIGHT, "loss_bbox": d.L1_WEIGHT, "loss_giou": d.GIOU_WEIGHT}
+            if d.DEEP_SUPERVISION:
+                for i in range(self.num_heads + self.num_heads_local - 1):
+                    weights.update({k + "_%d" % i: v for k, v in list(weights.items())[:3]})
+            object.__setattr__(self, "_criterion", SetCriterionDynamicK(cfg=self.cfg, num_classes=self.num_classes, matcher=matcher, weight_dict=weights,
+                                                                        eos_coef=d.NO_OBJECT_WEIGHT, losses=["labels", "boxes"], use_focal=self.use_focal))
+        return self._criterion
+
+    def _train_step(self, image_id):
+        """The diffusion step of an image's loss, a uniform integer in [0, num_timesteps): the reference draws torch.randint per image
+        (diffusion_det.py:695).  With a noise_fn it is derived from the image's key on the host: z = the one N(0, 1) draw of kind
+        "train_t" keyed (image_id, step 0, image 0), u = Phi(z) = (1 + erf(z / sqrt 2)) / 2 in float64, t = min(floor(u * num_timesteps),
+        num_timesteps - 1) -- a pure function of the id, uniform because Phi(z) is.  Without a noise_fn: torch.randint."""
+        if self.noise_fn is None:
+            return int(torch.randint(0, self.num_timesteps, (1,)))
+        z = float(self.noise_fn("train_t", int(image_id), 0, 0, (1,)).reshape(-1)[0])
+        u = 0.5 * (1.0 + math.erf(z / math.sqrt(2.0)))
+        return min(int(u * self.num_timesteps), self.num_timesteps - 1)
+
+    def loss_sums(self, images, targets, image_ids=None):
+        """What compute_losses forms its dict from: (sums [S, n, 4] float64 on the host -- per head output (the final one last) and image the
+        focal sum, the L1 sum, the 1 - GIoU sum and the matched count -- and the device tuple (assign, matched_query, sums, status) of
+        ops.set_criterion).  engine.inference.validation_losses adds the sums of a data set's batches."""
+        if self.training:
+            raise NotImplementedError("training is out of scope of the MI355X inference path")
+        if isinstance(images, dict):
+            raise NotImplementedError("compute_losses: the video item dict (cur / ref_l / ref_g) of the training protocol is not built; "
+                                      "hand over a batch of still images")
+        vid = self.cfg.MODEL.VID
+        if vid.ROI_BOX_HEAD.ATTENTION.ENABLE:
+            raise NotImplementedError("compute_losses: MODEL.VID.ROI_BOX_HEAD.ATTENTION.ENABLE True is not built (local-attention training batches)")
+        if vid.MEGA.GLOBAL.ENABLE or self.num_heads_local > 0:
+            raise NotImplementedError("compute_losses: still batches need MODEL.VID.MEGA.GLOBAL.ENABLE False and NUM_HEADS_LOCAL 0 (got %s, %d): the "
+                                      "conditioned heads have nothing to be conditioned on" % (vid.MEGA.GLOBAL.ENABLE, self.num_heads_local))
+        criterion = self._get_criterion()          # refuses USE_FED_LOSS by key
+        if isinstance(images, torch.Tensor):
+            images = list(images) if images.dim() == 4 else [images]
+        imgs = to_image_list(images, self.size_divisibility)
+        n, ch, H, W = imgs.tensors.shape
+        if ch != 3 or H % self.size_divisibility or W % self.size_divisibility:
+            raise ValueError("compute_losses: the canvas must be [n, 3, H, W] with H and W multiples of %d, got %s"
+                             % (self.size_divisibility, tuple(imgs.tensors.shape)))
+        sizes_wh = [(int(s[1]), int(s[0])) for s in imgs.image_sizes]
+        if len(sizes_wh) != n or any(not (0 < w <= W and 0 < h <= H) for w, h in sizes_wh):
+            raise ValueError("compute_losses: image_sizes must hold one (h, w) inside the %d x %d canvas per image, got %s" % (H, W, list(imgs.image_sizes)))
+        ids = list(range(n)) if image_ids is None else [int(i) for i in image_ids]
+        if len(ids) != n or len(targets) != n:
+            raise ValueError("compute_losses: %d image_ids and %d targets for %d images" % (len(ids), len(targets), n))
+        if n == 0:
+            raise ValueError("compute_losses: an empty batch has no loss")
+        M = self.num_proposals
+        # the ground truth, ragged, on the host: absolute xyxy in the image's own size, labels 1-based; normalised (cx, cy, w, h) for q_sample
+        gt_abs, gt_norm, labels, starts = [], [], [], [0]
+        for i, (t, (w, h)) in enumerate(zip(targets, sizes_wh)):
+            if tuple(int(v) for v in t.size) != (w, h):
+                raise ValueError("compute_losses: target %d is for a %s image, the image is %s" % (i, tuple(t.size), (w, h)))
+            if not t.has_field("labels"):
+                raise ValueError("compute_losses: target %d carries no `labels` field" % i)
+            b = t.convert("xyxy").bbox.detach().to("cpu", torch.float32).reshape(-1, 4)
+            if b.shape[0] > M:
+                raise NotImplementedError("compute_losses: image %d holds %d ground-truth boxes, MODEL.DiffusionDet.NUM_PROPOSALS is %d (the reference's "
+                                          "random subset is not built)" % (i, b.shape[0], M))
+            nb = b / torch.tensor([w, h, w, h], dtype=torch.float32)
+            gt_abs.append(b), labels.append(t.get_field("labels").detach().to("cpu", torch.int32).reshape(-1))
+            gt_norm.append(torch.stack(((nb[:, 0] + nb[:, 2]) / 2, (nb[:, 1] + nb[:, 3]) / 2, nb[:, 2] - nb[:, 0], nb[:, 3] - nb[:, 1]), dim=1))
+            starts.append(starts[-1] + b.shape[0])
+        from ..roi_heads.box_head.loss import check_limits, raise_on_status
+        check_limits(M, self.num_classes, criterion.matcher.ota_k, [starts[i + 1] - starts[i] for i in range(n)])
+        gt_abs, gt_norm, labels = torch.cat(gt_abs), torch.cat(gt_norm), torch.cat(labels)
+        starts = torch.tensor(starts, dtype=torch.int32)
+        steps = torch.tensor([self._train_step(i) for i in ids], dtype=torch.int64)
+
+        def run():
+            eng = self._get_engine()
+            dev = self.device
+            # every upload and draw before any kernel is queued (the rule of _detect_images)
+            sizes = ops.FrameSizes(torch.tensor(sizes_wh, dtype=torch.float32), dev)
+            noise, placeholder = self._still_draws("train_noise", ids, 0), self._still_draws("train_placeholder", ids, 0)
+            up = [t.to(dev) for t in (gt_abs, gt_norm, labels)]
+            canvas = imgs.tensors.to(dev, torch.float32).contiguous()
+            x_boxes = ops.q_sample_boxes(up[1], starts, steps, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, noise, placeholder,
+                                         self.scale, sizes)
+            cap = max(1, int(self.still_chunk or self.infer_batch * self.lookahead))
+            eng.reserve(min(cap, n), H, W, M)
+            logits, boxes = [], []
+            for a in range(0, n, cap):
+                b = min(n, a + cap)
+                feats = eng.backbone_frames([canvas[i:i + 1] for i in range(a, b)])
+                lg, bx = self.head.plain_heads(feats, x_boxes[a:b].contiguous(), steps[a:b], intermediate=True)
+                if not self.cfg.MODEL.DiffusionDet.DEEP_SUPERVISION:
+                    lg, bx = lg[-1:], bx[-1:]
+                logits.append(lg), boxes.append(bx)
+            logits, boxes = torch.cat(logits, dim=1), torch.cat(boxes, dim=1)
+            if self.debug_taps is not None:
+                self.debug_taps.setdefault("train_heads", []).append((logits, boxes, x_boxes, steps))
+            return criterion.sums(logits, boxes, (up[0], up[2], starts, sizes))
+
+        with torch.no_grad():
+            if self.device.type == "cuda" and self.device.index is not None:
+                with torch.cuda.device(self.device):
+                    out = run()
+            else:
+                out = run()
+        return out[2].detach().to("cpu", torch.float64), out
+
+    def compute_losses(self, images, targets, image_ids=None):
+        """The weighted training losses of a labelled batch of still images: what the reference's `_forward_train` returns
+        (diffusion_det.py:338-375), forward only.  images, image_ids: what detect_images takes; targets: one BoxList per image in the
+        image's own (w, h), mode xyxy or xywh, with a `labels` field (1-based).  Per image: t (see _train_step) and the draws
+        noise_fn("train_noise" / "train_placeholder", image_id, 0, 0, (M, 4)); ops.q_sample_boxes diffuses the ground truth to step t; the
+        NUM_HEADS heads run on the noisy boxes with every output kept when DEEP_SUPERVISION; ops.set_criterion matches and sums all of
+        them in one call.  -> {loss_ce, loss_bbox, loss_giou, and `_0 .. _{NUM_HEADS-2}`} as Python floats times CLASS_WEIGHT / L1_WEIGHT /
+        GIOU_WEIGHT.  Every draw is keyed by the image id and every stage is per-image independent, so the sums of an image depend
+        neither on its batch nor on the chunking.  The model stays in eval mode; nothing is cached, no video state is read or written,
+        nothing is replayed from a hipGraph.  The video item dict is refused by name (not built)."""
+        from ..roi_heads.box_head.loss import losses_from_sums
+        sums, _ = self.loss_sums(images, targets, image_ids)
+        weights = self._get_criterion().weight_dict
+        return {k: v * weights.get(k, 1.0) for k, v in losses_from_sums(sums).items()}
+
     def detect_images_aug(self, images, image_ids=None):
         """TEST.BBOX_AUG (mega_core/engine/bbox_aug.py: im_detect_bbox_aug): every image detected in flipped and rescaled views, the views'
         detections merged -> one BoxList per image in VIEW 0's (w, h) -- the size the plain test transform gives it -- with `scores` and

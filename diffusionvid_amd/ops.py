@@ -1246,3 +1246,77 @@ class Model:
             self.close()
         except Exception:
             pass
+
+
+# ---- the forward of the training objective (csrc/criterion.hip; the host mirror is modeling/roi_heads/box_head/loss.py) -----------------
+CRITERION_MAX_GT, CRITERION_MAX_ROWS, CRITERION_MAX_OTA_K, CRITERION_REPAIR_SLACK = 256, 4096, 64, 32          # include/dvid_hip.h
+CRITERION_ERR_ROUNDS, CRITERION_ERR_DEGENERATE, CRITERION_ERR_NONFINITE, CRITERION_ERR_LABEL = 1, 2, 4, 8
+
+
+def q_sample_boxes(gt_cxcywh, gt_starts, t, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, noise, placeholder, snr_scale, sizes):
+    """The noisy boxes of a labelled batch in one launch (dvid_q_sample_boxes: the reference's prepare_diffusion_concat + q_sample and the
+    scaling by (w, h, w, h)).  gt_cxcywh [G, 4] fp32 normalised (cx, cy, w, h) and gt_starts [n + 1] int32: the ragged ground truth;
+    t [n] integer time steps (the caller's draw, any device; read on the host for the range check); the two schedule tables [T] fp32;
+    noise and placeholder [n, M, 4] fp32 (the caller's draws); sizes: [n, 2] (w, h) or a FrameSizes.  -> absolute xyxy boxes [n, M, 4].
+    An image with more than M boxes is refused (the reference's random subset is not built)."""
+    noise, placeholder = _cuda(noise, torch.float32), _cuda(placeholder, torch.float32)
+    if noise.dim() != 3 or noise.shape[-1] != 4 or placeholder.shape != noise.shape:
+        raise _lib.DvidError(f"q_sample_boxes takes noise and placeholder [n, M, 4], got {tuple(noise.shape)} and {tuple(placeholder.shape)}")
+    n, M = noise.shape[:2]
+    dev = noise.device
+    starts_host = torch.as_tensor(gt_starts).detach().to("cpu", torch.int32).contiguous()
+    t_host = torch.as_tensor(t).detach().to("cpu", torch.int32).contiguous()
+    assert starts_host.shape == (n + 1,) and t_host.shape == (n,), "gt_starts is [n + 1], t is [n]"
+    gt = _cuda(gt_cxcywh, torch.float32).reshape(-1, 4)
+    assert int(starts_host[-1]) == gt.shape[0], "gt_starts ends at the box count"
+    sa, so = _cuda(sqrt_alphas_cumprod, torch.float32), _cuda(sqrt_one_minus_alphas_cumprod, torch.float32)
+    assert sa.dim() == 1 and sa.shape == so.shape, "the schedule tables are [T]"
+    fs = frame_sizes(sizes, n, dev)
+    out = torch.empty_like(noise)
+    starts_dev, t_dev = starts_host.to(dev), t_host.to(dev)          # named: a temporary would be freed, and its block reused, before the call
+    call("dvid_q_sample_boxes", ptr(gt), ptr(starts_dev), ptr(starts_host), n, M, ptr(t_dev), ptr(t_host), ptr(sa), ptr(so), sa.shape[0],
+         ptr(noise), ptr(placeholder), float(snr_scale), ptr(fs), ptr(out), stream_ptr())
+    return out
+
+
+def set_criterion_scratch_bytes(S, n, M, gmax):
+    """bytes of scratch dvid_set_criterion needs for S head outputs of n images with M queries and at most gmax boxes per image"""
+    return int(_lib.load().dvid_set_criterion_scratch_bytes(int(S), int(n), int(M), int(gmax)))
+
+
+def set_criterion(logits, boxes, gt_boxes, gt_labels, gt_starts, sizes, alpha, gamma, ota_k, cost_class, cost_bbox, cost_giou, out=None, gmax=None):
+    """The dynamic-k matcher and the loss sums of S head outputs of n images in ONE call (dvid_set_criterion, csrc/criterion.hip).
+    logits [S, n, M, C] and boxes [S, n, M, 4] (absolute xyxy) fp32; gt_boxes [G, 4] fp32 absolute xyxy, gt_labels [G] int32 1-based,
+    gt_starts [n + 1] int32 (any device: the counts are checked on the host); sizes [n, 2] (w, h) or a FrameSizes.  Returns (assign
+    [S, n, M] int32, matched_query [S, n, gmax] int32, sums [S, n, 4] float64, status [S, n] int32) on the device -- include/dvid_hip.h
+    says what each holds; the caller reads `status` (box_head.loss.raise_on_status).  `out`: such a tuple to write into; gmax: the width
+    of matched_query, by default the batch's largest box count (at least 1)."""
+    logits, boxes = _cuda(logits, torch.float32), _cuda(boxes, torch.float32)
+    assert logits.dim() == 4 and boxes.shape == logits.shape[:3] + (4,), "logits is [S, n, M, C], boxes [S, n, M, 4]"
+    S, n, M, c = logits.shape
+    dev = logits.device
+    starts_host = torch.as_tensor(gt_starts).detach().to("cpu", torch.int32).contiguous()
+    assert starts_host.shape == (n + 1,), "gt_starts is [n + 1]"
+    counts = (starts_host[1:] - starts_host[:-1]).tolist()
+    from .modeling.roi_heads.box_head.loss import check_limits
+    check_limits(M, c, int(ota_k), counts)
+    if gmax is None:
+        gmax = max(counts + [1])
+    gt_boxes, gt_labels = _cuda(gt_boxes, torch.float32).reshape(-1, 4), _cuda(gt_labels, torch.int32).reshape(-1)
+    assert int(starts_host[-1]) == gt_boxes.shape[0] == gt_labels.shape[0], "gt_starts ends at the box count"
+    fs = frame_sizes(sizes, n, dev)
+    if out is None:
+        out = (torch.empty((S, n, M), dtype=torch.int32, device=dev), torch.empty((S, n, gmax), dtype=torch.int32, device=dev),
+               torch.empty((S, n, 4), dtype=torch.float64, device=dev), torch.empty((S, n), dtype=torch.int32, device=dev))
+    assign, mq, sums, status = out
+    assert assign.shape == (S, n, M) and mq.shape == (S, n, gmax) and sums.shape == (S, n, 4) and status.shape == (S, n), "output shapes"
+    assert (assign.dtype, mq.dtype, sums.dtype, status.dtype) == (torch.int32, torch.int32, torch.float64, torch.int32), "output dtypes"
+    if S == 0 or n == 0:
+        return out
+    nbytes = set_criterion_scratch_bytes(S, n, M, gmax)
+    scratch = torch.empty(((nbytes + 15) // 16 * 2,), dtype=torch.float64, device=dev)
+    starts_dev = starts_host.to(dev)          # named: a temporary would be freed before the call
+    call("dvid_set_criterion", ptr(logits), ptr(boxes), S, n, M, c, ptr(gt_boxes), ptr(gt_labels), ptr(starts_dev), ptr(starts_host), ptr(fs),
+         float(alpha), float(gamma), int(ota_k), float(cost_class), float(cost_bbox), float(cost_giou), *(ptr(_cuda(o)) for o in (assign, mq)), int(gmax),
+         ptr(_cuda(sums)), ptr(_cuda(status)), ptr(scratch), scratch.numel() * 8, stream_ptr())
+    return out

@@ -229,14 +229,21 @@ def trained_like_scores(state_dict, gain=2.5, bias=-6.5):
     return out
 
 
-_KINDS = {"box_init": 0, "img": 1, "ddim": 2, "renew": 3}
+# The training draws (DiffusionDet.compute_losses) are kinds 4 .. 7.  The key has two bits for the kind, so they reuse the four slots on a video
+# number 50021 higher: every key of the kinds 0 .. 3 is what it was, and a training draw meets an inference draw only across videos 50021 apart.
+_KINDS = {"box_init": 0, "img": 1, "ddim": 2, "renew": 3, "train_t": 4, "train_noise": 5, "train_placeholder": 6, "train_uncond": 7}
+
+
+def draw_key(kind, frame_id, step, image, video=0):
+    k = _KINDS[kind]
+    return 2000 + (((((video + 50021 * (k >> 2)) * 100003 + frame_id) * 4 + (k & 3)) * 64 + step) * 64 + image)
 
 
 def noise_fn(kind, frame_id, step, image, shape, video=0):
     """Injected N(0,1) draws shared by the CPU oracle and the GPU path (the reference draws them on
     the device at diffusion_det.py:449,:542,:587,:595).  Keyed by (video, call frame, kind, step,
     image), not by RNG stream position, so 8-frame batches can be sharded across ranks."""
-    seed = 2000 + ((((video * 100003 + frame_id) * 4 + _KINDS[kind]) * 64 + step) * 64 + image)
+    seed = draw_key(kind, frame_id, step, image, video)
     g = torch.Generator().manual_seed(seed)
     return torch.randn(shape, generator=g)
 
@@ -253,7 +260,7 @@ class DeviceNoise:
         self.video = video
 
     def key(self, kind, frame_id, step, image):
-        return 2000 + ((((self.video * 100003 + frame_id) * 4 + _KINDS[kind]) * 64 + step) * 64 + image)
+        return draw_key(kind, frame_id, step, image, self.video)
 
     def draw(self, kind, frame_id, step, first_image, n_images, shape, device=None):
         from .. import ops

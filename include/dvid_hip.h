@@ -611,6 +611,48 @@ int dvid_jpeg_entropy_decode(const void* data, int64_t size, int16_t* coef, int6
 int dvid_jpeg_reconstruct_u8(const int16_t* coef, int64_t n_coef, const uint16_t* quant, int64_t n_quant, const long long* plan,
                              const long long* plan_host, int n, void* planes, int64_t planes_bytes, void* out, int64_t out_bytes, void* stream);
 
+/* ---- the forward of the training objective (dvid_version >= 12; csrc/criterion.hip) --------
+ * The host mirror is modeling/roi_heads/box_head/loss.py (the reference's box_head/loss.py:257-688, diffusion_det.py:681-725).  No gradient.
+ *
+ * dvid_q_sample_boxes: the noisy boxes of a labelled batch, one launch.  Image i: its ground truth gt[gt_starts[i] .. gt_starts[i + 1])
+ * as normalised (cx, cy, w, h) -- with none, the box (0.5, 0.5, 1, 1) -- padded to m rows with placeholder / 6 + 0.5 (w, h at least 1e-4;
+ * padding row j reads placeholder[i][j - real], the reference's draw of m - real rows), (x * 2 - 1) * snr_scale, sqrt_ac[t[i]] * x +
+ * sqrt_omac[t[i]] * noise, clamped to +-snr_scale, back to [0, 1], to xyxy, times the image's (w, h, w, h) from sizes [n][2].  fp32, one
+ * operation at a time.  t, noise [n][m][4] and placeholder [n][m][4] are the caller's draws; sqrt_ac / sqrt_omac are the detector's
+ * sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod tables of `timesteps` entries.  t_host / gt_starts_host: the same values on the
+ * host, checked before the launch.  DVID_ERR_UNSUPPORTED: an image with more than m ground-truth boxes (the reference draws a random
+ * subset there, which is not restated), with both numbers in the message; DVID_ERR_ARG: t outside [0, timesteps), null pointers.
+ *
+ * dvid_set_criterion: the dynamic-k matcher and the loss sums of n_sets head outputs of n images in one call.  logits [n_sets][n][m][c]
+ * and boxes [n_sets][n][m][4] (absolute xyxy) fp32; the ragged ground truth gt_boxes [G][4] fp32 absolute xyxy, gt_labels [G] int32
+ * 1-based, gt_starts [n + 1] (device) and gt_starts_host; sizes [n][2] = (w, h).  Outputs, all on the device:
+ *   assign [n_sets][n][m] int32          the ground-truth index within the image a query is matched to, -1 for none
+ *   matched_query [n_sets][n][gmax] int32 per ground-truth box its matched query of least cost (the matcher's second return value), -1 behind
+ *                                         the image's boxes; gmax >= the largest box count of the batch
+ *   sums [n_sets][n][4] float64          focal sum over the m x c elements, L1 sum and (1 - GIoU) sum over the matched queries, matched count
+ *   status [n_sets][n] int32             0, or DVID_CRITERION_ERR_* bits; a set with DEGENERATE, NONFINITE or LABEL is not matched
+ * Every term is fp32, summed in float64 by a fixed tree: two runs give the same bits.  The repair loop of the matcher is bounded by
+ * box count + DVID_CRITERION_REPAIR_SLACK rounds.  Refused before any launch, with the numbers: ota_k outside
+ * 1 .. DVID_CRITERION_MAX_OTA_K, m outside ota_k .. DVID_CRITERION_MAX_ROWS, c outside 1 .. DVID_MAX_CLASSES, an image with more than
+ * DVID_CRITERION_MAX_GT boxes or more than gmax (DVID_ERR_UNSUPPORTED); scratch smaller than dvid_set_criterion_scratch_bytes or not
+ * 16-byte aligned (DVID_ERR_ARG). */
+#define DVID_CRITERION_MAX_GT 256
+#define DVID_CRITERION_MAX_ROWS 4096
+#define DVID_CRITERION_MAX_OTA_K 64
+#define DVID_CRITERION_REPAIR_SLACK 32
+#define DVID_CRITERION_ERR_ROUNDS 1
+#define DVID_CRITERION_ERR_DEGENERATE 2
+#define DVID_CRITERION_ERR_NONFINITE 4
+#define DVID_CRITERION_ERR_LABEL 8
+int dvid_q_sample_boxes(const float* gt_cxcywh, const int* gt_starts, const int* gt_starts_host, int n, int m, const int* t, const int* t_host,
+                        const float* sqrt_ac, const float* sqrt_omac, int timesteps, const float* noise, const float* placeholder, float snr_scale,
+                        const float* sizes, float* boxes, void* stream);
+int dvid_set_criterion(const float* logits, const float* boxes, int n_sets, int n, int m, int c, const float* gt_boxes, const int* gt_labels,
+                       const int* gt_starts, const int* gt_starts_host, const float* sizes, float alpha, float gamma, int ota_k, float cost_class,
+                       float cost_bbox, float cost_giou, int* assign, int* matched_query, int gmax, double* sums, int* status, void* scratch,
+                       int64_t scratch_bytes, void* stream);
+int64_t dvid_set_criterion_scratch_bytes(int n_sets, int n, int m, int gmax);
+
 /* ---- options ------------------------------------------------------------------------------
  * The library's behaviour switches are ONE table set through this ABI, never through the environment (csrc/options.h; the defaults
  * are the benchmarked configuration).  Names: conv3x3, wstat, bneck_fuse (0 off / 1 by the layer's shape rule / 2 wherever the layer
