@@ -95,6 +95,7 @@ SIGNATURES = {
     "dvid_set_criterion": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 5 + [c_float, c_float, c_int] + [c_float] * 3 +
                            [c_void_p, c_void_p, c_int] + [c_void_p] * 3 + [c_int64, c_void_p]),
     "dvid_set_criterion_scratch_bytes": (c_int64, [c_int] * 4),
+    "dvid_set_criterion_backward": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 5 + [c_float, c_float] + [c_void_p] * 6),
     "dvid_cdist":(c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "dvid_fps_greedy": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dvid_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

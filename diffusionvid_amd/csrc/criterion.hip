@@ -1,10 +1,11 @@
-// The forward of the training objective (modeling/roi_heads/box_head/loss.py restates the same on the host; the reference's
+// The training objective, values and gradient (modeling/roi_heads/box_head/loss.py restates the same on the host; the reference's
 // box_head/loss.py:257-688 and diffusion_det.py:681-725):
 //
 //   q_sample_boxes_kernel    the noisy boxes of a labelled batch: ground truth padded to NUM_PROPOSALS, diffused to step t, as absolute xyxy
 //   criterion_match_kernel   the dynamic-k matcher, one workgroup per (head output, image)
 //   criterion_loss_kernel    the focal, L1 and 1 - GIoU sums over a chunk of CL_ROWS queries, fp32 terms added in float64 by a fixed tree
 //   criterion_sum_kernel     the chunks' partial sums added in chunk order
+//   criterion_grad_kernel    the gradient of a weighted sum of those sums with respect to every logit and box, one pass, fp32
 //
 // The matcher.  The M x G cost matrix lives in global scratch, column-major (cost[g * M + m]: a wave that walks a column reads
 // consecutive addresses), with one byte per entry of the matching matrix beside it; LDS holds the ground truth and the per-column and
@@ -29,6 +30,7 @@ typedef unsigned long long u64;
 #define CM_WAVES (CM_THREADS / WAVE)
 #define CL_THREADS 256
 #define CL_ROWS 16
+#define CG_DEPTH 4
 
 struct CritParams {
     float alpha, gamma, cost_class, cost_bbox, cost_giou;
@@ -426,6 +428,153 @@ __global__ __launch_bounds__(256) void criterion_sum_kernel(const double* __rest
     double v = 0.0;
     for (int c = 0; c < n_chunks; ++c) v = v + partial[((size_t)set * n_chunks + c) * 4 + q];
     sums[idx] = v;
+}
+
+// ---- the gradient of the loss sums -----------------------------------------------------------------------------------------------------
+// d/dq of coef2 * (1 - GIoU(q, gt)), one operation of cr_giou at a time backwards, with torch's conventions at the kinks: a maximum or
+// minimum of equal operands hands each half of the gradient, clamp(min = 0) passes it at exactly 0.
+__device__ __forceinline__ float cr_share_max(float a, float b) { return a > b ? 1.f : (a == b ? 0.5f : 0.f); }          // d max(a, b) / da
+__device__ __forceinline__ float cr_share_min(float a, float b) { return a < b ? 1.f : (a == b ? 0.5f : 0.f); }
+__device__ __forceinline__ void cr_giou_grad(const float4v a, const float4v b, float c2, float* g) {
+    const float wa = a[2] - a[0], ha = a[3] - a[1], area_a = wa * ha, area_b = cr_area(b);
+    const float wr = fminf(a[2], b[2]) - fmaxf(a[0], b[0]), hr = fminf(a[3], b[3]) - fmaxf(a[1], b[1]);
+    const float w = fmaxf(wr, 0.f), h = fmaxf(hr, 0.f), inter = w * h, uni = (area_a + area_b) - inter;
+    const float cwr = fmaxf(a[2], b[2]) - fminf(a[0], b[0]), chr = fmaxf(a[3], b[3]) - fminf(a[1], b[1]);
+    const float cw = fmaxf(cwr, 0.f), ch = fmaxf(chr, 0.f), area_c = cw * ch;
+    const float g_giou = -c2;                                                             // the loss is 1 - giou
+    const float g_areac = -g_giou * __fdiv_rn(uni, area_c * area_c);                      // giou = iou - (area_c - uni) / area_c
+    const float g_uni = __fdiv_rn(g_giou, area_c) - g_giou * __fdiv_rn(inter, uni * uni);
+    const float g_inter = __fdiv_rn(g_giou, uni) - g_uni;
+    const float g_wr = wr >= 0.f ? g_inter * h : 0.f, g_hr = hr >= 0.f ? g_inter * w : 0.f;
+    const float g_cwr = cwr >= 0.f ? g_areac * ch : 0.f, g_chr = chr >= 0.f ? g_areac * cw : 0.f;
+    g[0] = (-g_wr * cr_share_max(a[0], b[0]) - g_cwr * cr_share_min(a[0], b[0])) - g_uni * ha;
+    g[1] = (-g_hr * cr_share_max(a[1], b[1]) - g_chr * cr_share_min(a[1], b[1])) - g_uni * wa;
+    g[2] = (g_wr * cr_share_min(a[2], b[2]) + g_cwr * cr_share_max(a[2], b[2])) + g_uni * ha;
+    g[3] = (g_hr * cr_share_min(a[3], b[3]) + g_chr * cr_share_max(a[3], b[3])) + g_uni * wa;
+}
+
+// coef0 * d/dx of the element criterion_loss_kernel sums: ce * (1 - p_t)^gamma * alpha_t.  With q = 1 - p_t (1 - p on the one-hot
+// element, p elsewhere): d/dx = +-alpha_t * q^gamma * (q + gamma * p_t * ce), minus on the one-hot element; k_hot = -coef0 * alpha_t of
+// the one-hot element, k_cold = coef0 * alpha_t of the others.  p and 1 - p both come from e = exp(-|x|) -- sigmoid(|x|) = 1 / (1 + e),
+// sigmoid(-|x|) = e / (1 + e) -- so neither is a difference of near-equal numbers, and log1p(e) = -log(sigmoid(|x|)).  The pass is
+// paced by these operations, not by memory, so they are the hardware's: v_exp_f32, v_rcp_f32, v_log_f32 (1 ulp each; an error of 1e-7
+// in ce moves the result by under 2e-8 * coef0, the q^gamma * p_t in front of it is at most 0.15).  gamma == 2 is a product, decided
+// once per launch; any other gamma takes powf.
+template <bool GAMMA2>
+__device__ __forceinline__ float cr_focal_grad(float x, bool hot, float k_hot, float k_cold, float gamma) {
+    const float e = __expf(-fabsf(x)), big = __builtin_amdgcn_rcpf(1.f + e), small = e * big;
+    const bool up = hot == (x >= 0.f);          // the one-hot element of a positive logit, another element of a negative one: q is the small one
+    const float q = up ? small : big, pt = up ? big : small;
+    const float ce = (fmaxf(x, 0.f) - (hot ? x : 0.f)) - __logf(big);
+    const float pw = GAMMA2 ? q * q : powf(q, gamma);
+    return (hot ? k_hot : k_cold) * (pw * (q + (gamma * pt) * ce));
+}
+
+// One workgroup per chunk of CL_ROWS queries of one (head output, image), criterion_loss_kernel's decomposition.  The first `rows`
+// threads write the rows' d_boxes and leave the one-hot class in LDS; then all threads walk the chunk's flat rows * C range: scalars up to
+// the first 16-byte boundary, float4 from there, a scalar tail.  Every element of d_logits and d_boxes has exactly one writer.
+template <bool GAMMA2>
+__global__ __launch_bounds__(CL_THREADS) void criterion_grad_kernel(const float* __restrict__ logits, const float* __restrict__ boxes, int n, int M, int C,
+                                                                    const float* __restrict__ gt_boxes, const int* __restrict__ gt_labels,
+                                                                    const int* __restrict__ gt_starts, const float* __restrict__ sizes, float alpha,
+                                                                    float gamma, const int* __restrict__ assign, const int* __restrict__ status,
+                                                                    const double* __restrict__ coef, float* __restrict__ d_logits,
+                                                                    float* __restrict__ d_boxes) {
+    __shared__ int s_cls[CL_ROWS];
+    const int chunk = blockIdx.x, set = blockIdx.y, img = set % n, head = set / n, tid = threadIdx.x;
+    const int r0 = chunk * CL_ROWS, rows = min(CL_ROWS, M - r0);
+    const bool dead = (status[set] & (DVID_CRITERION_ERR_DEGENERATE | DVID_CRITERION_ERR_NONFINITE | DVID_CRITERION_ERR_LABEL)) != 0;          // uniform
+    const float c0 = dead ? 0.f : (float)coef[head * 3], c1 = dead ? 0.f : (float)coef[head * 3 + 1], c2 = dead ? 0.f : (float)coef[head * 3 + 2];
+    if (tid < rows) {
+        const int g0 = gt_starts[img], G = max(gt_starts[img + 1] - g0, 0);
+        const int a = dead ? -1 : assign[(size_t)set * M + r0 + tid];
+        int cls = -1;
+        float g[4] = {0.f, 0.f, 0.f, 0.f};
+        if (a >= 0 && a < G) {
+            cls = gt_labels[g0 + a] - 1;
+            const float iw = sizes[2 * img], ih = sizes[2 * img + 1];
+            const float* b = boxes + ((size_t)set * M + r0 + tid) * 4;
+            const float* t = gt_boxes + (size_t)(g0 + a) * 4;
+            const float4v q = {b[0], b[1], b[2], b[3]}, gt = {t[0], t[1], t[2], t[3]};
+            if (c2 != 0.f) cr_giou_grad(q, gt, c2, g);
+            if (c1 != 0.f) {          // the L1 target as criterion_loss_kernel forms it
+                const float n0 = __fdiv_rn(gt[0], iw), n1 = __fdiv_rn(gt[1], ih), n2 = __fdiv_rn(gt[2], iw), n3 = __fdiv_rn(gt[3], ih);
+                const float cx = __fdiv_rn(n0 + n2, 2.f), cy = __fdiv_rn(n1 + n3, 2.f), w = n2 - n0, h = n3 - n1;
+                const float d0 = __fdiv_rn(q[0], iw) - (cx - 0.5f * w), d1 = __fdiv_rn(q[1], ih) - (cy - 0.5f * h);
+                const float d2 = __fdiv_rn(q[2], iw) - (cx + 0.5f * w), d3 = __fdiv_rn(q[3], ih) - (cy + 0.5f * h);
+                const float sw = __fdiv_rn(c1, iw), sh = __fdiv_rn(c1, ih);
+                g[0] = g[0] + (d0 > 0.f ? sw : (d0 < 0.f ? -sw : 0.f)), g[1] = g[1] + (d1 > 0.f ? sh : (d1 < 0.f ? -sh : 0.f));
+                g[2] = g[2] + (d2 > 0.f ? sw : (d2 < 0.f ? -sw : 0.f)), g[3] = g[3] + (d3 > 0.f ? sh : (d3 < 0.f ? -sh : 0.f));
+            }
+        }
+        float* o = d_boxes + ((size_t)set * M + r0 + tid) * 4;
+        o[0] = g[0], o[1] = g[1], o[2] = g[2], o[3] = g[3];
+        s_cls[tid] = cls;
+    }
+    __syncthreads();
+    const size_t base = ((size_t)set * M + r0) * C;
+    const float* lg = logits + base;
+    float* dl = d_logits + base;
+    const int total = rows * C;
+    // the float4 range: both pointers must reach a 16-byte boundary after the same number of elements (they do whenever the two tensors
+    // start on one; a chunk starts r0 * C = a multiple of 4 elements into its set, but the set itself starts anywhere when M * C is odd)
+    const unsigned in_mis = (unsigned)((uintptr_t)lg & 15), out_mis = (unsigned)((uintptr_t)dl & 15);
+    const int lead = in_mis != out_mis ? total : min(total, (int)(((16u - in_mis) & 15u) >> 2));
+    const int nvec = (total - lead) >> 2, tail0 = lead + 4 * nvec;
+    if (c0 == 0.f) {          // uniform: exact zeros, and the logits are not read
+        for (int e = tid; e < lead; e += CL_THREADS) dl[e] = 0.f;
+        for (int v = tid; v < nvec; v += CL_THREADS) *reinterpret_cast<float4v*>(dl + lead + 4 * v) = (float4v){0.f, 0.f, 0.f, 0.f};
+        for (int e = tail0 + tid; e < total; e += CL_THREADS) dl[e] = 0.f;
+        return;
+    }
+    const unsigned inv = C > 1 ? 0xffffffffu / (unsigned)C + 1u : 0u;          // e / C = umulhi(e, inv): exact while e * C < 2^32 (e < 16 * 1280)
+    const float k_hot = -(c0 * (alpha >= 0.f ? alpha : 1.f)), k_cold = c0 * (alpha >= 0.f ? 1.f - alpha : 1.f);
+    for (int e = tid; e < lead; e += CL_THREADS) {          // (lead <= 3 on the float4 path, the whole chunk otherwise)
+        const int r = C > 1 ? (int)__umulhi((unsigned)e, inv) : e;
+        dl[e] = cr_focal_grad<GAMMA2>(lg[e], s_cls[r] == e - r * C, k_hot, k_cold, gamma);
+    }
+    // CG_DEPTH float4 loads of a thread are in flight before the first is used: at 16 rows x 1203 classes a workgroup makes 4.7 such rounds
+    for (int v0 = tid; v0 < nvec; v0 += CG_DEPTH * CL_THREADS) {
+        float4v x[CG_DEPTH];
+#pragma unroll
+        for (int k = 0; k < CG_DEPTH; ++k)
+            if (v0 + k * CL_THREADS < nvec) x[k] = *reinterpret_cast<const float4v*>(lg + lead + 4 * (v0 + k * CL_THREADS));
+#pragma unroll
+        for (int k = 0; k < CG_DEPTH; ++k) {
+            if (v0 + k * CL_THREADS >= nvec) break;
+            const int e = lead + 4 * (v0 + k * CL_THREADS);
+            int r = C > 1 ? (int)__umulhi((unsigned)e, inv) : e, c = e - r * C;
+            float4v o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                o[j] = cr_focal_grad<GAMMA2>(x[k][j], s_cls[r] == c, k_hot, k_cold, gamma);          // r < rows: the element lies inside the chunk
+                if (++c == C) c = 0, ++r;
+            }
+            *reinterpret_cast<float4v*>(dl + e) = o;
+        }
+    }
+    for (int e = tail0 + tid; e < total; e += CL_THREADS) {
+        const int r = C > 1 ? (int)__umulhi((unsigned)e, inv) : e;
+        dl[e] = cr_focal_grad<GAMMA2>(lg[e], s_cls[r] == e - r * C, k_hot, k_cold, gamma);
+    }
+}
+
+int dvid_set_criterion_backward_launch(const float* logits, const float* boxes, int n_sets, int n, int m, int c, const float* gt_boxes,
+                                       const int* gt_labels, const int* gt_starts, const float* sizes, float alpha, float gamma, const int* assign,
+                                       const int* status, const double* coef, float* d_logits, float* d_boxes, hipStream_t s) {
+    if (n_sets < 0 || n < 0 || m < 1 || m > DVID_CRITERION_MAX_ROWS || c < 1 || c > DVID_MAX_CLASSES) return DVID_ERR_ARG;
+    const long long sets = (long long)n_sets * n;
+    if (sets == 0) return DVID_OK;
+    if (sets > 65535) return DVID_ERR_ARG;          // grid y
+    const dim3 grid((unsigned)ceil_div(m, CL_ROWS), (unsigned)sets);
+    if (gamma == 2.f)
+        hipLaunchKernelGGL(criterion_grad_kernel<true>, grid, dim3(CL_THREADS), 0, s, logits, boxes, n, m, c, gt_boxes, gt_labels, gt_starts, sizes, alpha, gamma,
+                           assign, status, coef, d_logits, d_boxes);
+    else
+        hipLaunchKernelGGL(criterion_grad_kernel<false>, grid, dim3(CL_THREADS), 0, s, logits, boxes, n, m, c, gt_boxes, gt_labels, gt_starts, sizes, alpha, gamma,
+                           assign, status, coef, d_logits, d_boxes);
+    LAUNCH_CHECK();
+    return DVID_OK;
 }
 
 static long long cr_align16(long long v) { return (v + 15) & ~15ll; }

@@ -204,6 +204,9 @@ long long dvid_set_criterion_scratch_bytes_host(int n_sets, int n, int m, int gm
 int dvid_set_criterion_launch(const float* logits, const float* boxes, int n_sets, int n, int m, int c, const float* gt_boxes, const int* gt_labels,
                               const int* gt_starts, const float* sizes, float alpha, float gamma, int ota_k, float cost_class, float cost_bbox,
                               float cost_giou, int* assign, int* matched_query, int gmax, double* sums, int* status, void* scratch, hipStream_t s);
+int dvid_set_criterion_backward_launch(const float* logits, const float* boxes, int n_sets, int n, int m, int c, const float* gt_boxes,
+                                       const int* gt_labels, const int* gt_starts, const float* sizes, float alpha, float gamma, const int* assign,
+                                       const int* status, const double* coef, float* d_logits, float* d_boxes, hipStream_t s);
 
 // postproc.hip
 int dvid_topk_candidates_launch(const float* logits, const float* boxes, int n_img, int nsets, int m, int c, float* cand_boxes,

@@ -372,6 +372,34 @@ int dvid_set_criterion(const float* logits, const float* boxes, int n_sets, int 
     return DVID_OK;
 }
 
+int dvid_set_criterion_backward(const float* logits, const float* boxes, int n_sets, int n, int m, int c, const float* gt_boxes, const int* gt_labels,
+                                const int* gt_starts, const int* gt_starts_host, const float* sizes, float alpha, float gamma, const int* assign,
+                                const int* status, const double* coef, float* d_logits, float* d_boxes, void* stream) {
+    g_err[0] = 0;
+    if (n_sets < 0 || n < 0 || m < 1 || c < 1)
+        FAIL(DVID_ERR_ARG, "set criterion backward: bad sizes (%d head outputs, %d images, %d queries, %d classes)", n_sets, n, m, c);
+    if (m > DVID_CRITERION_MAX_ROWS)
+        FAIL(DVID_ERR_UNSUPPORTED, "set criterion backward: %d queries per image, the limit is %d (DVID_CRITERION_MAX_ROWS)", m, DVID_CRITERION_MAX_ROWS);
+    if (c > DVID_MAX_CLASSES) FAIL(DVID_ERR_UNSUPPORTED, "set criterion backward: %d classes exceed the limit of %d (DVID_MAX_CLASSES)", c, DVID_MAX_CLASSES);
+    if ((long long)n_sets * n > 65535)
+        FAIL(DVID_ERR_UNSUPPORTED, "set criterion backward: %d head outputs x %d images exceed 65535 sets per call", n_sets, n);
+    if (n_sets == 0 || n == 0) return DVID_OK;
+    if (!logits || !boxes || !gt_starts || !gt_starts_host || !sizes || !assign || !status || !coef || !d_logits || !d_boxes)
+        FAIL(DVID_ERR_ARG, "set criterion backward: null pointer");
+    if (gt_starts_host[0] != 0) FAIL(DVID_ERR_ARG, "set criterion backward: gt_starts[0] is %d, not 0", gt_starts_host[0]);
+    for (int i = 0; i < n; ++i) {
+        const int g = gt_starts_host[i + 1] - gt_starts_host[i];
+        if (g < 0) FAIL(DVID_ERR_ARG, "set criterion backward: gt_starts decreases at image %d", i);
+        if (g > DVID_CRITERION_MAX_GT)
+            FAIL(DVID_ERR_UNSUPPORTED, "set criterion backward: image %d holds %d ground-truth boxes, the limit is %d (DVID_CRITERION_MAX_GT)", i, g,
+                 DVID_CRITERION_MAX_GT);
+    }
+    if (gt_starts_host[n] > 0 && (!gt_boxes || !gt_labels)) FAIL(DVID_ERR_ARG, "set criterion backward: null ground truth");
+    TRY(dvid_set_criterion_backward_launch(logits, boxes, n_sets, n, m, c, gt_boxes, gt_labels, gt_starts, sizes, alpha, gamma, assign, status, coef, d_logits,
+                                           d_boxes, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
 int dvid_coco_eval_match(const float* dets, const int* counts, int n_images, int cap, const double* gt_boxes, const double* gt_areas,
                          const unsigned char* gt_crowd, const int* gt_labels, const int* gt_starts, const int* gt_starts_host,
                          const double* iou_thrs, const double* area_ranges, int num_classes, signed char* match, signed char* ignore,

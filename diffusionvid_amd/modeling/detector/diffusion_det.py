@@ -503,6 +503,12 @@ class DiffusionDet(nn.Module):
         """What compute_losses forms its dict from: (sums [S, n, 4] float64 on the host -- per head output (the final one last) and image the
         focal sum, the L1 sum, the 1 - GIoU sum and the matched count -- and the device tuple (assign, matched_query, sums, status) of
         ops.set_criterion).  engine.inference.validation_losses adds the sums of a data set's batches."""
+        out = self._loss_forward(images, targets, image_ids, False)[0]
+        return out[2].detach().to("cpu", torch.float64), out
+
+    def _loss_forward(self, images, targets, image_ids, gradients):
+        """The forward loss_sums and loss_gradients share -> (the device tuple of ops.set_criterion, None or (d_logits, d_boxes) of the sum of
+        the weighted losses with respect to the kept head outputs, from ops.set_criterion_backward on the same stream)."""
         if self.training:
             raise NotImplementedError("training is out of scope of the MI355X inference path")
         if isinstance(images, dict):
@@ -546,7 +552,7 @@ class DiffusionDet(nn.Module):
             gt_abs.append(b), labels.append(t.get_field("labels").detach().to("cpu", torch.int32).reshape(-1))
             gt_norm.append(torch.stack(((nb[:, 0] + nb[:, 2]) / 2, (nb[:, 1] + nb[:, 3]) / 2, nb[:, 2] - nb[:, 0], nb[:, 3] - nb[:, 1]), dim=1))
             starts.append(starts[-1] + b.shape[0])
-        from ..roi_heads.box_head.loss import check_limits, raise_on_status
+        from ..roi_heads.box_head.loss import LOSS_KEYS, check_limits, coef_from_counts, raise_on_status
         check_limits(M, self.num_classes, criterion.matcher.ota_k, [starts[i + 1] - starts[i] for i in range(n)])
         gt_abs, gt_norm, labels = torch.cat(gt_abs), torch.cat(gt_norm), torch.cat(labels)
         starts = torch.tensor(starts, dtype=torch.int32)
@@ -559,6 +565,9 @@ class DiffusionDet(nn.Module):
             sizes = ops.FrameSizes(torch.tensor(sizes_wh, dtype=torch.float32), dev)
             noise, placeholder = self._still_draws("train_noise", ids, 0), self._still_draws("train_placeholder", ids, 0)
             up = [t.to(dev) for t in (gt_abs, gt_norm, labels)]
+            if gradients:          # the weights of the kept head outputs, the final one last
+                sfx = ["_%d" % s for s in range(self.num_heads - 1)] + [""] if self.cfg.MODEL.DiffusionDet.DEEP_SUPERVISION else [""]
+                weights = torch.tensor([[float(criterion.weight_dict.get(k + x, 1.0)) for k in LOSS_KEYS] for x in sfx], dtype=torch.float64).to(dev)
             canvas = imgs.tensors.to(dev, torch.float32).contiguous()
             x_boxes = ops.q_sample_boxes(up[1], starts, steps, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, noise, placeholder,
                                          self.scale, sizes)
@@ -575,15 +584,20 @@ class DiffusionDet(nn.Module):
             logits, boxes = torch.cat(logits, dim=1), torch.cat(boxes, dim=1)
             if self.debug_taps is not None:
                 self.debug_taps.setdefault("train_heads", []).append((logits, boxes, x_boxes, steps))
-            return criterion.sums(logits, boxes, (up[0], up[2], starts, sizes))
+            out = criterion.sums(logits, boxes, (up[0], up[2], starts, sizes))
+            if not gradients:
+                return out, None
+            # d(sum of the weighted losses): weight / denominator per head output, the denominators from the matched counts on the device
+            assert logits.shape[0] == weights.shape[0], "one row of weights per kept head output"
+            p = criterion.matcher.params()
+            coef = coef_from_counts(weights, out[2][:, :, 3].sum(1))
+            return out, ops.set_criterion_backward(logits, boxes, up[0], up[2], starts, sizes, p["alpha"], p["gamma"], out[0], out[3], coef)
 
         with torch.no_grad():
             if self.device.type == "cuda" and self.device.index is not None:
                 with torch.cuda.device(self.device):
-                    out = run()
-            else:
-                out = run()
-        return out[2].detach().to("cpu", torch.float64), out
+                    return run()
+            return run()
 
     def compute_losses(self, images, targets, image_ids=None):
         """The weighted training losses of a labelled batch of still images: what the reference's `_forward_train` returns
@@ -599,6 +613,22 @@ class DiffusionDet(nn.Module):
         sums, _ = self.loss_sums(images, targets, image_ids)
         weights = self._get_criterion().weight_dict
         return {k: v * weights.get(k, 1.0) for k, v in losses_from_sums(sums).items()}
+
+    def loss_gradients(self, images, targets, image_ids=None):
+        """compute_losses and the first link of its backward pass: -> (losses, d_logits [S, n, M, C], d_boxes [S, n, M, 4]).  Inputs and
+        refusals are compute_losses'; `losses` is compute_losses' dict; the two fp32 tensors, which stay on the device, are the gradient of
+        the SUM of the weighted losses with respect to every kept head output (logits and absolute xyxy boxes as
+        debug_taps["train_heads"] records them), the final head output last; S is 1 without DEEP_SUPERVISION.  One
+        ops.set_criterion_backward launch behind the forward's ops.set_criterion, on the same tensors.
+
+        The gradient stops at the head outputs: the HIP head, the FPN and the backbone have no backward.  A coefficient divides by the
+        BATCH's matched count of its head output (the reference's denominators), so an image's gradient depends on the batch it is in; its
+        loss sums do not."""
+        from ..roi_heads.box_head.loss import losses_from_sums
+        out, grads = self._loss_forward(images, targets, image_ids, True)
+        weights = self._get_criterion().weight_dict
+        losses = {k: v * weights.get(k, 1.0) for k, v in losses_from_sums(out[2].detach().to("cpu", torch.float64)).items()}
+        return losses, grads[0], grads[1]
 
     def detect_images_aug(self, images, image_ids=None):
         """TEST.BBOX_AUG (mega_core/engine/bbox_aug.py: im_detect_bbox_aug): every image detected in flipped and rescaled views, the views'

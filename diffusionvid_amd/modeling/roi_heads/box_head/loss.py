@@ -1,11 +1,17 @@
-"""The forward of DiffusionDet's training objective: the SimOTA-style matcher `HungarianMatcherDynamicK` and the set-prediction
-criterion `SetCriterionDynamicK` (the reference's box_head/loss.py:257-688), with the reference's constructor signatures, `outputs` /
-`targets` dicts and loss dict.  No gradient: every tensor that comes out is detached.
+"""DiffusionDet's training objective: the SimOTA-style matcher `HungarianMatcherDynamicK` and the set-prediction criterion
+`SetCriterionDynamicK` (the reference's box_head/loss.py:257-688), with the reference's constructor signatures, `outputs` / `targets`
+dicts and loss dict.
 
-Two paths compute the same thing:
+Two paths compute the same values:
   * CUDA tensors: `ops.set_criterion` (csrc/criterion.hip), ONE call for all head outputs of the batch;
   * CPU tensors: `criterion_host` below, torch fp32 one operation at a time in the reference's order -- the default host path, and what
     the CPU suite holds the arithmetic with.
+
+Gradient.  The matcher never carries one (the reference's runs under no_grad too).  The criterion does when grad mode is on and a
+`pred_logits` / `pred_boxes` tensor requires grad: its losses then are 0-dim float64 tensors with a `grad_fn` on the inputs' device, and
+`backward()` reaches the head outputs -- on CUDA tensors through `ops.set_criterion_backward` (one launch for all head outputs), on CPU
+tensors through torch's autograd on `losses_host`.  In every other situation (no_grad, inputs that do not require grad) what comes out is
+detached, float64, on the CPU, as before.  The gradient stops at the head outputs: the HIP head has no backward.
 
 Both return, per (head output s, image i): `assign` [M] (the ground-truth index a query is matched to, -1 for none), `matched_query`
 [Gmax] (per ground-truth box the matched query of least cost, the matcher's second return value), `sums` [4] float64 (focal sum over the
@@ -31,6 +37,7 @@ from torch import nn
 STATUS_ROUNDS, STATUS_DEGENERATE, STATUS_NONFINITE, STATUS_LABEL = 1, 2, 4, 8          # include/dvid_hip.h: DVID_CRITERION_ERR_*
 MAX_GT, MAX_ROWS, MAX_OTA_K = 256, 4096, 64                                              # DVID_CRITERION_MAX_GT / _MAX_ROWS / _MAX_OTA_K
 MAX_CLASSES = 1280                                                                       # DVID_MAX_CLASSES
+LOSS_KEYS = ("loss_ce", "loss_bbox", "loss_giou")
 
 
 def repair_bound(num_gt):
@@ -248,6 +255,105 @@ def losses_from_sums(sums):
     return out
 
 
+def _giou_rows(a, b):
+    """a, b [K, 4] xyxy -> GIoU of row k of a with row k of b: _giou_pairs' arithmetic on the pairs alone"""
+    area_a = (a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1])
+    area_b = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    w = (torch.minimum(a[:, 2], b[:, 2]) - torch.maximum(a[:, 0], b[:, 0])).clamp(min=0)
+    h = (torch.minimum(a[:, 3], b[:, 3]) - torch.maximum(a[:, 1], b[:, 1])).clamp(min=0)
+    inter = w * h
+    union = (area_a + area_b) - inter
+    cw = (torch.maximum(a[:, 2], b[:, 2]) - torch.minimum(a[:, 0], b[:, 0])).clamp(min=0)
+    ch = (torch.maximum(a[:, 3], b[:, 3]) - torch.minimum(a[:, 1], b[:, 1])).clamp(min=0)
+    area = cw * ch
+    return inter / union - (area - union) / area
+
+
+def losses_host(logits, boxes, packed, assign, alpha=0.25, gamma=2.0):
+    """The differentiable host path: the three losses of every head output as torch operations on the tensors handed over, no loop over
+    elements, images or head outputs.  logits [S, n, M, C], boxes [S, n, M, 4] absolute xyxy, fp32 or float64 (the ground truth is taken
+    to their dtype); packed: pack_targets' tuple (gt_boxes [G, 4], gt_labels [G] 1-based, gt_starts [n + 1], sizes [n, 2]); assign
+    [S, n, M]: the matching (criterion_host's or ops.set_criterion's), not differentiated.  -> [S, 3] float64: loss_ce, loss_bbox,
+    loss_giou of head output s with the reference's denominators -- loss_ce = focal sum / max(matched, 1), the box terms / matched, and 0
+    with zero gradient when nothing matched.  The terms are criterion_host's arithmetic in the inputs' dtype, added in float64.
+
+    This is what torch's autograd differentiates on the CPU, and what states the device kernel's conventions at the kinks: torch.maximum
+    / torch.minimum of equal operands hand each half of the gradient, clamp(min=0) passes it at exactly 0, sign(0) = 0 in the L1 term."""
+    S, n, M, C = logits.shape
+    dt, dev = logits.dtype, logits.device
+    gt_boxes, gt_labels, gt_starts, sizes = packed
+    gt_boxes = gt_boxes.detach().reshape(-1, 4).to(dev, dt)
+    lab0 = gt_labels.detach().reshape(-1).to(dev, torch.int64) - 1
+    starts = torch.as_tensor(gt_starts).detach().to(dev, torch.int64)
+    sizes = torch.as_tensor(sizes).detach().to(dev, dt)
+    whwh = torch.cat((sizes, sizes), dim=1)                                             # [n, 4]
+    s_idx, i_idx, m_idx = torch.nonzero(assign.to(dev) >= 0, as_tuple=True)              # the matched queries, K of them
+    g_idx = starts[i_idx] + assign.to(dev)[s_idx, i_idx, m_idx].to(torch.int64)
+    onehot = torch.zeros((S, n, M, C), dtype=dt, device=dev)
+    onehot[s_idx, i_idx, m_idx, lab0[g_idx]] = 1
+    focal = focal_terms(logits, onehot, alpha, gamma).double().sum((1, 2, 3))
+    # the L1 target: normalised, to (cx, cy, w, h) and back, as prepare_targets and loss_boxes do
+    gt, w4 = gt_boxes[g_idx], whwh[i_idx]
+    gn = gt / w4
+    ncx, ncy, nw, nh = (gn[:, 0] + gn[:, 2]) / 2, (gn[:, 1] + gn[:, 3]) / 2, gn[:, 2] - gn[:, 0], gn[:, 3] - gn[:, 1]
+    target = torch.stack((ncx - 0.5 * nw, ncy - 0.5 * nh, ncx + 0.5 * nw, ncy + 0.5 * nh), dim=1)
+    q = boxes[s_idx, i_idx, m_idx]
+    d = (q / w4 - target).abs()
+    l1 = ((d[:, 0] + d[:, 1]) + d[:, 2]) + d[:, 3]
+    zero = torch.zeros((S,), dtype=torch.float64, device=dev)
+    l1 = zero.index_add(0, s_idx, l1.double())
+    giou = zero.index_add(0, s_idx, (1 - _giou_rows(q, gt)).double())
+    cnt = zero.index_add(0, s_idx, torch.ones_like(s_idx, dtype=torch.float64)).clamp(min=1)          # nothing matched: the box sums are 0
+    return torch.stack((focal / cnt, l1 / cnt, giou / cnt), dim=1)
+
+
+def _denominators(cnt):
+    """matched counts [S] float64 -> ([S, 3] what the three sums are divided by, [S, 3] 1 where the loss exists, 0 where it is defined as 0)"""
+    one = torch.ones_like(cnt)
+    return torch.stack((cnt.clamp(min=1),) * 3, dim=1), torch.stack((one, (cnt > 0).to(cnt.dtype), (cnt > 0).to(cnt.dtype)), dim=1)
+
+
+def coef_from_counts(upstream, cnt):
+    """upstream [S, 3] (d objective / d loss_ce, loss_bbox, loss_giou of each head output) and the matched counts [S] of the batch -> the
+    coef [S, 3] float64 ops.set_criterion_backward takes: upstream / max(matched, 1), and 0 for the box terms when nothing matched.
+    Device tensors stay on the device: nothing here synchronises."""
+    den, live = _denominators(cnt.to(torch.float64))
+    return (upstream.to(torch.float64) / den * live).contiguous()
+
+
+class _DeviceCriterion(torch.autograd.Function):
+    """ops.set_criterion forward, ops.set_criterion_backward backward: [S, n, M, C] logits and [S, n, M, 4] boxes -> losses [S, 3] float64
+    on the device (loss_ce, loss_bbox, loss_giou per head output, the reference's denominators)."""
+
+    @staticmethod
+    def forward(ctx, logits, boxes, packed, params, what):
+        from .... import ops
+        gt_boxes, gt_labels, gt_starts, sizes = packed
+        dev = logits.device
+        if not isinstance(sizes, ops.FrameSizes):
+            sizes = sizes.to(dev, torch.float32)
+        lg, bx = logits.detach().float().contiguous(), boxes.detach().float().contiguous()
+        gt_boxes, gt_labels = gt_boxes.to(dev, torch.float32), gt_labels.to(dev, torch.int32)
+        assign, _, sums, status = ops.set_criterion(lg, bx, gt_boxes, gt_labels, gt_starts, sizes, params["alpha"], params["gamma"], params["ota_k"],
+                                                    params["cost_class"], params["cost_bbox"], params["cost_giou"])
+        raise_on_status(status, what)
+        tot = sums.sum(1)                                                                # over the batch, on the device
+        den, live = _denominators(tot[:, 3])
+        ctx.save_for_backward(lg, bx, gt_boxes, gt_labels, assign, status, tot[:, 3])
+        ctx.rest = (gt_starts, sizes, params["alpha"], params["gamma"], logits.dtype, boxes.dtype)
+        return tot[:, :3] / den * live
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        from .... import ops
+        lg, bx, gt_boxes, gt_labels, assign, status, cnt = ctx.saved_tensors
+        gt_starts, sizes, alpha, gamma, dt_logits, dt_boxes = ctx.rest
+        d_logits, d_boxes = ops.set_criterion_backward(lg, bx, gt_boxes, gt_labels, gt_starts, sizes, alpha, gamma, assign, status,
+                                                       coef_from_counts(grad, cnt))
+        return d_logits.to(dt_logits), d_boxes.to(dt_boxes), None, None, None
+
+
 def q_sample_boxes_host(gt_cxcywh, gt_starts, t, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, noise, placeholder, snr_scale, sizes):
     """The host form of ops.q_sample_boxes (the reference's prepare_diffusion_concat + q_sample, diffusion_det.py:681-725, and the scaling
     by the image's (w, h, w, h)), torch fp32 one operation at a time: same arguments on the CPU, -> absolute xyxy boxes [n, M, 4]."""
@@ -343,7 +449,8 @@ class HungarianMatcherDynamicK(nn.Module):
 
 class SetCriterionDynamicK(nn.Module):
     """The set-prediction loss with the reference's constructor (loss.py:263).  forward(outputs, targets) -> {loss_ce, loss_bbox, loss_giou,
-    and `_0 .. _{S-2}` for outputs["aux_outputs"]}, unweighted 0-dim float64 tensors (no gradient flows: this is the forward only)."""
+    and `_0 .. _{S-2}` for outputs["aux_outputs"]}, unweighted 0-dim float64 tensors: detached and on the CPU, unless grad mode is on and a
+    `pred_logits` / `pred_boxes` requires grad -- then on the inputs' device with a grad_fn (the module docstring says through what)."""
 
     def __init__(self, cfg, num_classes, matcher, weight_dict, eos_coef, losses, use_focal):
         super().__init__()
@@ -367,10 +474,28 @@ class SetCriterionDynamicK(nn.Module):
         raise_on_status(out[3], "SetCriterionDynamicK")
         return out
 
-    @torch.no_grad()
+    def losses_with_grad(self, logits, boxes, packed):
+        """The differentiable path.  [S, n, M, C], [S, n, M, 4] and pack_targets' tuple -> losses [S, 3] float64 on the inputs' device
+        (loss_ce, loss_bbox, loss_giou per head output) with a grad_fn: the device pair ops.set_criterion / ops.set_criterion_backward on
+        CUDA tensors, the matcher under no_grad and then losses_host on CPU tensors.  Statuses are raised as `sums` raises them."""
+        if logits.shape[-1] != self.num_classes:
+            raise ValueError("SetCriterionDynamicK: the logits hold %d classes, num_classes is %d" % (logits.shape[-1], self.num_classes))
+        p = self.matcher.params()
+        if logits.is_cuda:
+            return _DeviceCriterion.apply(logits, boxes, packed, p, "SetCriterionDynamicK")
+        assign = self.sums(logits, boxes, packed)[0]
+        return losses_host(logits, boxes, packed, assign, p["alpha"], p["gamma"])
+
     def forward(self, outputs, targets):
         heads = list(outputs.get("aux_outputs", [])) + [outputs]                        # the final output last
-        logits = torch.stack([h["pred_logits"] for h in heads])
-        boxes = torch.stack([h["pred_boxes"] for h in heads])
-        sums = self.sums(logits, boxes, pack_targets(targets))[2]
-        return {k: torch.tensor(v, dtype=torch.float64) for k, v in losses_from_sums(sums).items()}
+        wanted = torch.is_grad_enabled() and any(h[k].requires_grad for h in heads for k in ("pred_logits", "pred_boxes"))
+        with torch.set_grad_enabled(wanted):
+            logits = torch.stack([h["pred_logits"] for h in heads])
+            boxes = torch.stack([h["pred_boxes"] for h in heads])
+        packed = pack_targets(targets)
+        if not wanted:
+            sums = self.sums(logits, boxes, packed)[2]
+            return {k: torch.tensor(v, dtype=torch.float64) for k, v in losses_from_sums(sums).items()}
+        losses = self.losses_with_grad(logits, boxes, packed)
+        S = losses.shape[0]
+        return {key + ("" if s == S - 1 else "_%d" % s): losses[s, k] for s in [S - 1] + list(range(S - 1)) for k, key in enumerate(LOSS_KEYS)}

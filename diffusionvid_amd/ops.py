@@ -1320,3 +1320,32 @@ def set_criterion(logits, boxes, gt_boxes, gt_labels, gt_starts, sizes, alpha, g
          float(alpha), float(gamma), int(ota_k), float(cost_class), float(cost_bbox), float(cost_giou), *(ptr(_cuda(o)) for o in (assign, mq)), int(gmax),
          ptr(_cuda(sums)), ptr(_cuda(status)), ptr(scratch), scratch.numel() * 8, stream_ptr())
     return out
+
+
+def set_criterion_backward(logits, boxes, gt_boxes, gt_labels, gt_starts, sizes, alpha, gamma, assign, status, coef, out=None):
+    """The gradient of sum_s sum_k coef[s, k] * (focal, L1, 1 - GIoU sum of head output s over the batch) with respect to logits and boxes in
+    ONE launch (dvid_set_criterion_backward, csrc/criterion.hip).  logits, boxes, gt_boxes, gt_labels, gt_starts, sizes, alpha, gamma: what
+    set_criterion was handed; assign [S, n, M] int32 and status [S, n] int32: what it returned; coef [S, 3] float64 (for the reference's
+    losses: upstream gradient / denominator, see box_head.loss).  Returns (d_logits [S, n, M, C], d_boxes [S, n, M, 4]) fp32 on the device,
+    every element written; include/dvid_hip.h states the arithmetic, the zeros and the conventions at the kinks.  `out`: such a pair to write
+    into."""
+    logits, boxes = _cuda(logits, torch.float32), _cuda(boxes, torch.float32)
+    assert logits.dim() == 4 and boxes.shape == logits.shape[:3] + (4,), "logits is [S, n, M, C], boxes [S, n, M, 4]"
+    S, n, M, c = logits.shape
+    dev = logits.device
+    starts_host = torch.as_tensor(gt_starts).detach().to("cpu", torch.int32).contiguous()
+    assert starts_host.shape == (n + 1,), "gt_starts is [n + 1]"
+    gt_boxes, gt_labels = _cuda(gt_boxes, torch.float32).reshape(-1, 4), _cuda(gt_labels, torch.int32).reshape(-1)
+    assert int(starts_host[-1]) == gt_boxes.shape[0] == gt_labels.shape[0], "gt_starts ends at the box count"
+    fs = frame_sizes(sizes, n, dev)
+    assign, status, coef = _cuda(assign, torch.int32), _cuda(status, torch.int32), _cuda(coef, torch.float64)
+    assert assign.shape == (S, n, M) and status.shape == (S, n) and coef.shape == (S, 3), "assign is [S, n, M], status [S, n], coef [S, 3]"
+    if out is None:
+        out = (torch.empty((S, n, M, c), dtype=torch.float32, device=dev), torch.empty((S, n, M, 4), dtype=torch.float32, device=dev))
+    d_logits, d_boxes = out
+    assert d_logits.shape == (S, n, M, c) and d_boxes.shape == (S, n, M, 4), "output shapes"
+    assert d_logits.dtype == d_boxes.dtype == torch.float32 and d_logits.is_contiguous() and d_boxes.is_contiguous(), "outputs are contiguous fp32"
+    starts_dev = starts_host.to(dev)          # named: a temporary would be freed before the call
+    call("dvid_set_criterion_backward", ptr(logits), ptr(boxes), S, n, M, c, ptr(gt_boxes), ptr(gt_labels), ptr(starts_dev), ptr(starts_host), ptr(fs),
+         float(alpha), float(gamma), ptr(assign), ptr(status), ptr(coef), ptr(_cuda(d_logits)), ptr(_cuda(d_boxes)), stream_ptr())
+    return out

@@ -611,8 +611,9 @@ int dvid_jpeg_entropy_decode(const void* data, int64_t size, int16_t* coef, int6
 int dvid_jpeg_reconstruct_u8(const int16_t* coef, int64_t n_coef, const uint16_t* quant, int64_t n_quant, const long long* plan,
                              const long long* plan_host, int n, void* planes, int64_t planes_bytes, void* out, int64_t out_bytes, void* stream);
 
-/* ---- the forward of the training objective (dvid_version >= 12; csrc/criterion.hip) --------
- * The host mirror is modeling/roi_heads/box_head/loss.py (the reference's box_head/loss.py:257-688, diffusion_det.py:681-725).  No gradient.
+/* ---- the training objective (dvid_version >= 12; its gradient >= 13; csrc/criterion.hip) ----
+ * The host mirror is modeling/roi_heads/box_head/loss.py (the reference's box_head/loss.py:257-688, diffusion_det.py:681-725).  The first
+ * three entries compute values only; dvid_set_criterion_backward is the gradient with respect to the head outputs.
  *
  * dvid_q_sample_boxes: the noisy boxes of a labelled batch, one launch.  Image i: its ground truth gt[gt_starts[i] .. gt_starts[i + 1])
  * as normalised (cx, cy, w, h) -- with none, the box (0.5, 0.5, 1, 1) -- padded to m rows with placeholder / 6 + 0.5 (w, h at least 1e-4;
@@ -652,6 +653,29 @@ int dvid_set_criterion(const float* logits, const float* boxes, int n_sets, int 
                        float cost_bbox, float cost_giou, int* assign, int* matched_query, int gmax, double* sums, int* status, void* scratch,
                        int64_t scratch_bytes, void* stream);
 int64_t dvid_set_criterion_scratch_bytes(int n_sets, int n, int m, int gmax);
+
+/* dvid_set_criterion_backward (dvid_version >= 13): the gradient of  sum_s sum_k coef[s][k] * sum_k(s)  with respect to logits and boxes,
+ * where sum_0 .. sum_2 (s) are the focal, L1 and (1 - GIoU) sums dvid_set_criterion reports for head output s, added over the batch.  One
+ * launch for all n_sets head outputs of n images.  logits, boxes, the ground truth, sizes, alpha and gamma: dvid_set_criterion's own
+ * arguments; assign [n_sets][n][m] and status [n_sets][n] as that call left them; coef [n_sets][3] float64 on the device, formed by the
+ * caller (the reference's losses: upstream gradient / denominator, the denominators from sums[..][3], so no host synchronise is needed).
+ * Outputs d_logits [n_sets][n][m][c] and d_boxes [n_sets][n][m][4], fp32; EVERY element is written (an uninitialised buffer is fine).
+ *   focal  coef0 * d/dx of BCE-with-logits * (1 - p_t)^gamma * alpha_t (alpha < 0: no alpha weight; gamma != 2: powf), fp32, the one-hot
+ *          built from assign and the labels as the forward builds it
+ *   L1     matched rows: coef1 * sign(q / whwh - target) / whwh, target the forward's normalised, to-cxcywh-and-back value; sign(0) = 0
+ *   GIoU   matched rows: coef2 * d(1 - GIoU(q, gt)) / dq
+ * At the kinks the gradient is what torch's autograd gives on the host restatement (loss.losses_host), and this is part of the contract:
+ * a maximum / minimum of EQUAL operands hands each operand half of the gradient; clamp(min = 0) passes the gradient at exactly 0 (an
+ * intersection of zero width still sends its gradient on, a negative one does not).
+ * Zeros: unmatched rows have d_boxes exactly 0; a set whose status carries DEGENERATE, NONFINITE or LABEL gets all zeros (the forward did
+ * not match it); a coef of 0 gives exact zeros for its term, whatever the inputs hold (never 0 * inf).
+ * No atomics and no reduction: every output element has one writer, so two runs give the same bits.
+ * Refused before any launch, with the numbers: m outside 1 .. DVID_CRITERION_MAX_ROWS, c outside 1 .. DVID_MAX_CLASSES, an image with
+ * more than DVID_CRITERION_MAX_GT boxes, more than 65535 sets (DVID_ERR_UNSUPPORTED); null pointers, a gt_starts that does not start at
+ * 0 or decreases (DVID_ERR_ARG). */
+int dvid_set_criterion_backward(const float* logits, const float* boxes, int n_sets, int n, int m, int c, const float* gt_boxes, const int* gt_labels,
+                                const int* gt_starts, const int* gt_starts_host, const float* sizes, float alpha, float gamma, const int* assign,
+                                const int* status, const double* coef, float* d_logits, float* d_boxes, void* stream);
 
 /* ---- options ------------------------------------------------------------------------------
  * The library's behaviour switches are ONE table set through this ABI, never through the environment (csrc/options.h; the defaults

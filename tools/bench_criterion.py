@@ -4,6 +4,13 @@ kernels separately (torch.profiler's device times per kernel name).  A record, n
 
     python tools/bench_criterion.py > profiles/criterion_bench.txt
 
+    python tools/bench_criterion.py --backward > profiles/criterion_backward_bench.txt
+
+--backward times the gradient instead: ops.set_criterion_backward (one launch for all head outputs) against torch's autograd through the
+same per-image loop -- the loop run once on inputs that require grad (the matcher on detached tensors, as the reference runs it), then
+`.backward()` of the weighted reference losses timed on the retained graph.  Beside each time: the bytes the gradient has to move (logits
+read, d_logits written, boxes, d_boxes, assign) and the rate they amount to.
+
 Case one: 8 images x 6 head outputs x 500 boxes x 80 classes; case two: 8 x 6 x 300 x 1203; 7 ground-truth boxes per image."""
 import os
 import sys
@@ -29,7 +36,7 @@ def torch_loop(logits, boxes, gt, lab, starts, sizes):
         g, l0 = gt[starts[i]:starts[i + 1]], lab[starts[i]:starts[i + 1]].long() - 1
         whwh = torch.stack((sizes[i, 0], sizes[i, 1], sizes[i, 0], sizes[i, 1]))
         for s in range(S):
-            a, _, _ = _match_on_device(logits[s, i], boxes[s, i], g, l0, whwh, idx)
+            a, _, _ = _match_on_device(logits[s, i].detach(), boxes[s, i].detach(), g, l0, whwh, idx)
             rows = torch.nonzero(a >= 0)[:, 0]
             onehot = torch.zeros_like(logits[s, i])
             onehot[rows, l0[a[rows]]] = 1
@@ -56,7 +63,7 @@ def timed(fn, reps):
     return (time.perf_counter() - t0) / reps * 1e3
 
 
-def kernel_times(fn, reps=20):
+def kernel_times(fn, reps=20, names=("criterion_match_kernel", "criterion_loss_kernel", "criterion_sum_kernel")):
     from torch.profiler import ProfilerActivity, profile
     fn()
     torch.cuda.synchronize()
@@ -66,14 +73,52 @@ def kernel_times(fn, reps=20):
         torch.cuda.synchronize()
     out = {}
     for e in prof.key_averages():
-        for name in ("criterion_match_kernel", "criterion_loss_kernel", "criterion_sum_kernel"):
+        for name in names:
             if name in e.key:
                 out[name] = getattr(e, "device_time_total", getattr(e, "cuda_time_total", 0.0)) / reps / 1e3
     return out
 
 
+def backward_main():
+    """the gradient launch against autograd's backward pass through the per-image loop"""
+    print("set criterion gradient: ops.set_criterion_backward against torch autograd's backward through the per-image loop on the same GPU tensors "
+          "(%s)" % torch.cuda.get_device_name(0))
+    w = torch.tensor([CC.W_CLASS, CC.W_L1, CC.W_GIOU], dtype=torch.float64, device="cuda")
+    for name, (n, S, M, C) in (("8 x 6 x 500 x 80", (8, 6, 500, 80)), ("8 x 6 x 300 x 1203", (8, 6, 300, 1203))):
+        logits, boxes, gt, lab, starts, sizes = CC.random_set(100 + C, S, M, C, [7] * n, sizes=[(1333, 800)] * n)
+        dev = [t.cuda() for t in (logits, boxes, gt, lab)]
+        sizes_d, st = sizes.cuda(), starts.tolist()
+        assign, _, sums, status = ops.set_criterion(*dev, starts, sizes_d, *CC.PARAMS)
+        cnt = sums[:, :, 3].sum(1)
+        coef = L.coef_from_counts(w[None, :].expand(S, 3), cnt)
+        out = ops.set_criterion_backward(*dev, starts, sizes_d, CC.ALPHA, CC.GAMMA, assign, status, coef)
+        run = lambda: ops.set_criterion_backward(*dev, starts, sizes_d, CC.ALPHA, CC.GAMMA, assign, status, coef, out=out)
+        nbytes = logits.numel() * 8 + boxes.numel() * 8 + assign.numel() * 4
+        ours = timed(run, 200)
+        kern = kernel_times(run, 50, ("criterion_grad_kernel",)).get("criterion_grad_kernel", float("nan"))
+        lg, bx = dev[0].clone().requires_grad_(True), dev[1].clone().requires_grad_(True)
+        t0 = time.perf_counter()
+        total = torch_loop(lg, bx, dev[2], dev[3], st, sizes_d)
+        objective = (total[:, :3] * coef).sum()
+        torch.cuda.synchronize()
+        fwd = (time.perf_counter() - t0) * 1e3
+
+        def autograd():
+            lg.grad, bx.grad = None, None
+            objective.backward(retain_graph=True)
+        loop = timed(autograd, 3)
+        scale = (float(out[0].abs().max()), float(out[1].abs().max()))
+        dev_l, dev_b = float((lg.grad - out[0]).abs().max()) / scale[0], float((bx.grad - out[1]).abs().max()) / scale[1]
+        print("%-20s %6.1f MB moved  set_criterion_backward %7.4f ms per call (%6.1f GB/s), criterion_grad_kernel %7.4f ms (%6.1f GB/s)  "
+              "autograd backward %8.2f ms (%5.2f GB/s; its forward with the graph %9.1f ms)  x%.0f  gradients agree to %.1e / %.1e of their largest, "
+              "matched %d" % (name, nbytes / 1e6, ours, nbytes / ours / 1e6, kern, nbytes / kern / 1e6, loop, nbytes / loop / 1e6, fwd, loop / ours,
+                              dev_l, dev_b, int(cnt.sum())))
+
+
 def main():
     assert torch.cuda.is_available()
+    if "--backward" in sys.argv:
+        return backward_main()
     print("set criterion: ops.set_criterion against the torch per-image loop on the same GPU tensors (ms per call, %s)" % torch.cuda.get_device_name(0))
     for name, (n, S, M, C) in (("8 x 6 x 500 x 80", (8, 6, 500, 80)), ("8 x 6 x 300 x 1203", (8, 6, 300, 1203))):
         logits, boxes, gt, lab, starts, sizes = CC.random_set(100 + C, S, M, C, [7] * n, sizes=[(1333, 800)] * n)
