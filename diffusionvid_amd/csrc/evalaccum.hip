@@ -30,7 +30,7 @@
 // Every count that a table supplies is clamped again where it indexes memory.
 #include "../../include/dvid_hip.h"
 #include "kernels.h"
-#include "evalkey.h"          // u64, ce_score_desc
+#include "evalmatch.h"          // em_sort; evalkey.h: u64, ce_score_desc
 
 #define EA_THREADS 256
 #define EA_WAVES (EA_THREADS / 64)
@@ -125,17 +125,7 @@ __global__ __launch_bounds__(EA_THREADS) void ea_emit_kernel(const float* __rest
     for (int i = tid; i < Pf; i += EA_THREADS)
         s_key[i] = ea_live_label(d, rk, i, n, K) ? ((unsigned)min(rk[i], EA_RANK_MAX) << 12) | (unsigned)i : EA_PAD;
     __syncthreads();
-    for (int k = 2; k <= Pf; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < Pf; i += EA_THREADS) {
-                const int x = i ^ j;
-                if (x > i) {
-                    const unsigned a = s_key[i], b = s_key[x];
-                    if ((a > b) == ((i & k) == 0)) s_key[i] = b, s_key[x] = a;
-                }
-            }
-            __syncthreads();
-        }
+    em_sort<EA_THREADS>(s_key, Pf, tid);
     const size_t plane = (size_t)N * cap, image = (size_t)f * cap;
     const int off = img_off[f];
     for (int j = tid; j < n; j += EA_THREADS) {

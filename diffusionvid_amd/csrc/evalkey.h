@@ -1,5 +1,5 @@
-// What the COCO and the LVIS evaluator kernels (cocoeval.hip, lviseval.hip) share: the score's place in a 64-bit sort key and the COCO
-// bbox IoU in float64.
+// u64 and the score's place in a sort key of the evaluator kernels.  Apart from the sort this is all that evalaccum.hip has in common with
+// the match kernels; evalmatch.h, which includes this file, holds the rest of the shared code.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,18 +10,4 @@ __device__ __forceinline__ unsigned ce_score_desc(float s) {
     if (s == 0.f) s = 0.f;          // -0 and +0 are one score
     const unsigned b = __float_as_uint(s);
     return ~(b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u));
-}
-
-// d, g: x, y, w, h
-__device__ __forceinline__ double coco_iou(const double dx, const double dy, const double dw, const double dh, const double* __restrict__ g,
-                                           const bool crowd) {
-#pragma clang fp contract(off)
-    const double w = fmin(dx + dw, g[0] + g[2]) - fmax(dx, g[0]);
-    if (w <= 0.0) return 0.0;
-    const double h = fmin(dy + dh, g[1] + g[3]) - fmax(dy, g[1]);
-    if (h <= 0.0) return 0.0;
-    const double i = w * h;
-    const double da = dw * dh, ga = g[2] * g[3];
-    const double u = crowd ? da : (da + ga) - i;
-    return __ddiv_rn(i, u);
 }

@@ -237,6 +237,8 @@ long long dvid_seq_nms_scratch_size(const int* class_counts, const int* video_st
 int dvid_seq_nms_launch(const float* dets, const int* counts, const int* class_counts, const int* video_starts, int n_videos, int cap, int num_classes,
                         unsigned char* keep, float* scores, int* status, void* scratch, hipStream_t s);
 
+// The evaluators.  evalmatch.h holds the device code they share (the sort key, the bitonic sort, the segment heads; for COCO and LVIS also the
+// IoU, the ground-truth load and the walk of one task), evalkey.h the score's key bits.
 // videval.hip: the VID evaluator's greedy matching and CorLoc test, a workgroup per frame; ranges / empty_w are host tables (include/dvid_hip.h)
 int dvid_vid_eval_match_launch(const float* dets, const int* counts, int n_frames, int cap, const float* gt_boxes, const int* gt_labels,
                                const int* gt_starts, const double* motion, const double* ranges, const double* empty_w, int n_ranges, float iou_thresh,

@@ -257,6 +257,30 @@ int dvid_nms_frames_tiled_sizes(const float* cand_boxes, const float* cand_score
     return DVID_OK;
 }
 
+// A host CSR start table of n units ("frame", "image", "video"): [0] is 0 and it never decreases; with a limit (LIMIT(macro)) no unit holds
+// more ground-truth boxes than that.  *most, when given, gets the greatest count of one unit.
+#define LIMIT(macro) macro, #macro
+static int csr_starts_ok(const char* entry, const char* table, const char* unit, const int* starts, int n, int* most = nullptr, int limit = 0,
+                         const char* limit_name = nullptr) {
+    if (starts[0] != 0) FAIL(DVID_ERR_ARG, "%s: %s[0] is %d, not 0", entry, table, starts[0]);
+    int top = 0;
+    for (int i = 0; i < n; ++i) {
+        const int g = starts[i + 1] - starts[i];
+        if (g < 0) FAIL(DVID_ERR_ARG, "%s: %s decreases at %s %d", entry, table, unit, i);
+        if (limit_name && g > limit)
+            FAIL(DVID_ERR_UNSUPPORTED, "%s: %s %d holds %d ground-truth boxes, the limit is %d (%s)", entry, unit, i, g, limit, limit_name);
+        top = g > top ? g : top;
+    }
+    if (most) *most = top;
+    return DVID_OK;
+}
+
+static int scratch_ok(const char* entry, const void* scratch, long long scratch_bytes, long long need) {
+    if (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 15))
+        FAIL(DVID_ERR_ARG, "%s: the scratch holds %lld bytes, %lld are needed (16-byte aligned)", entry, scratch_bytes, need);
+    return DVID_OK;
+}
+
 int64_t dvid_seq_nms_scratch_bytes(const int* class_counts, const int* video_starts, int n_videos, int num_classes) {
     return (int64_t)dvid_seq_nms_scratch_size(class_counts, video_starts, n_videos, num_classes);
 }
@@ -266,9 +290,7 @@ int dvid_seq_nms_video(const float* dets, const int* counts, const int* class_co
     g_err[0] = 0;
     if (!dets || !counts || !class_counts || !video_starts || !keep || !scores || !status) FAIL(DVID_ERR_ARG, "Seq-NMS: null pointer");
     if (n_videos < 1 || cap < 1 || num_classes < 1) FAIL(DVID_ERR_ARG, "Seq-NMS: bad sizes (%d videos, %d rows per frame, %d classes)", n_videos, cap, num_classes);
-    if (video_starts[0] != 0) FAIL(DVID_ERR_ARG, "Seq-NMS: video_starts[0] is %d, not 0", video_starts[0]);
-    for (int v = 0; v < n_videos; ++v)
-        if (video_starts[v + 1] < video_starts[v]) FAIL(DVID_ERR_ARG, "Seq-NMS: video_starts decreases at video %d", v);
+    TRY(csr_starts_ok("Seq-NMS", "video_starts", "video", video_starts, n_videos));
     if (cap > DVID_NMS_MAX_CANDIDATES || num_classes > DVID_MAX_CLASSES)
         FAIL(DVID_ERR_UNSUPPORTED, "Seq-NMS: %d rows per frame x %d classes exceed the limits of %d rows (DVID_NMS_MAX_CANDIDATES) and %d classes (DVID_MAX_CLASSES)",
              cap, num_classes, DVID_NMS_MAX_CANDIDATES, DVID_MAX_CLASSES);
@@ -277,8 +299,7 @@ int dvid_seq_nms_video(const float* dets, const int* counts, const int* class_co
     if (need > DVID_SEQ_NMS_MAX_SCRATCH_BYTES)
         FAIL(DVID_ERR_UNSUPPORTED, "Seq-NMS: %lld bytes of link rows and tables for %d frames x %d classes exceed the limit of %lld (DVID_SEQ_NMS_MAX_SCRATCH_BYTES): "
              "run fewer videos per call", need, video_starts[n_videos], num_classes, (long long)DVID_SEQ_NMS_MAX_SCRATCH_BYTES);
-    if (need > 0 && (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 15)))
-        FAIL(DVID_ERR_ARG, "Seq-NMS: the scratch holds %lld bytes, %lld are needed (16-byte aligned)", (long long)scratch_bytes, need);
+    if (need > 0) TRY(scratch_ok("Seq-NMS", scratch, scratch_bytes, need));
     TRY(dvid_seq_nms_launch(dets, counts, class_counts, video_starts, n_videos, cap, num_classes, keep, scores, status, scratch,
                             reinterpret_cast<hipStream_t>(stream)));
     return DVID_OK;
@@ -300,13 +321,7 @@ int dvid_vid_eval_match(const float* dets, const int* counts, int n_frames, int 
         FAIL(DVID_ERR_UNSUPPORTED, "VID evaluation: %d motion ranges, the limit is 1 .. %d (DVID_VID_EVAL_MAX_RANGES)", n_ranges, DVID_VID_EVAL_MAX_RANGES);
     if (label_min < 0 || label_max > num_classes)
         FAIL(DVID_ERR_UNSUPPORTED, "VID evaluation: labels %d .. %d leave the range 0 .. %d (num_classes)", label_min, label_max, num_classes);
-    if (gt_starts_host[0] != 0) FAIL(DVID_ERR_ARG, "VID evaluation: gt_starts[0] is %d, not 0", gt_starts_host[0]);
-    for (int f = 0; f < n_frames; ++f) {
-        const int g = gt_starts_host[f + 1] - gt_starts_host[f];
-        if (g < 0) FAIL(DVID_ERR_ARG, "VID evaluation: gt_starts decreases at frame %d", f);
-        if (g > DVID_VID_EVAL_MAX_GT)
-            FAIL(DVID_ERR_UNSUPPORTED, "VID evaluation: frame %d holds %d ground-truth boxes, the limit is %d (DVID_VID_EVAL_MAX_GT)", f, g, DVID_VID_EVAL_MAX_GT);
-    }
+    TRY(csr_starts_ok("VID evaluation", "gt_starts", "frame", gt_starts_host, n_frames, nullptr, LIMIT(DVID_VID_EVAL_MAX_GT)));
     if (gt_starts_host[n_frames] > 0 && (!gt_boxes || !gt_labels)) FAIL(DVID_ERR_ARG, "VID evaluation: null ground truth");
     TRY(dvid_vid_eval_match_launch(dets, counts, n_frames, cap, gt_boxes, gt_labels, gt_starts, motion, ranges, empty_w, n_ranges, iou_thresh, num_classes,
                                    match, weight, rank, n_pos, top_row, top_hit, reinterpret_cast<hipStream_t>(stream)));
@@ -321,11 +336,9 @@ int dvid_q_sample_boxes(const float* gt_cxcywh, const int* gt_starts, const int*
     if (n == 0) return DVID_OK;
     if (!gt_starts || !gt_starts_host || !t || !t_host || !sqrt_ac || !sqrt_omac || !noise || !placeholder || !sizes || !boxes)
         FAIL(DVID_ERR_ARG, "q_sample_boxes: null pointer");
-    if (gt_starts_host[0] != 0) FAIL(DVID_ERR_ARG, "q_sample_boxes: gt_starts[0] is %d, not 0", gt_starts_host[0]);
+    TRY(csr_starts_ok("q_sample_boxes", "gt_starts", "image", gt_starts_host, n));
     for (int i = 0; i < n; ++i) {
-        const int g = gt_starts_host[i + 1] - gt_starts_host[i];
-        if (g < 0) FAIL(DVID_ERR_ARG, "q_sample_boxes: gt_starts decreases at image %d", i);
-        if (g > m)
+        if (const int g = gt_starts_host[i + 1] - gt_starts_host[i]; g > m)
             FAIL(DVID_ERR_UNSUPPORTED, "q_sample_boxes: image %d holds %d ground-truth boxes, NUM_PROPOSALS is %d (the reference's random subset is not built)",
                  i, g, m);
         if (t_host[i] < 0 || t_host[i] >= timesteps) FAIL(DVID_ERR_ARG, "q_sample_boxes: t[%d] is %d, outside 0 .. %d", i, t_host[i], timesteps - 1);
@@ -355,18 +368,14 @@ int dvid_set_criterion(const float* logits, const float* boxes, int n_sets, int 
     if ((long long)n_sets * n > 65535) FAIL(DVID_ERR_UNSUPPORTED, "set criterion: %d head outputs x %d images exceed 65535 sets per call", n_sets, n);
     if (n_sets == 0 || n == 0) return DVID_OK;
     if (!logits || !boxes || !gt_starts || !gt_starts_host || !sizes || !assign || !matched_query || !sums || !status) FAIL(DVID_ERR_ARG, "set criterion: null pointer");
-    if (gt_starts_host[0] != 0) FAIL(DVID_ERR_ARG, "set criterion: gt_starts[0] is %d, not 0", gt_starts_host[0]);
-    for (int i = 0; i < n; ++i) {
-        const int g = gt_starts_host[i + 1] - gt_starts_host[i];
-        if (g < 0) FAIL(DVID_ERR_ARG, "set criterion: gt_starts decreases at image %d", i);
-        if (g > DVID_CRITERION_MAX_GT)
-            FAIL(DVID_ERR_UNSUPPORTED, "set criterion: image %d holds %d ground-truth boxes, the limit is %d (DVID_CRITERION_MAX_GT)", i, g, DVID_CRITERION_MAX_GT);
-        if (g > gmax) FAIL(DVID_ERR_ARG, "set criterion: image %d holds %d ground-truth boxes, gmax is %d", i, g, gmax);
-    }
+    int most = 0;
+    TRY(csr_starts_ok("set criterion", "gt_starts", "image", gt_starts_host, n, &most, LIMIT(DVID_CRITERION_MAX_GT)));
+    for (int i = 0; most > gmax && i < n; ++i)          // name the first image over gmax
+        if (const int g = gt_starts_host[i + 1] - gt_starts_host[i]; g > gmax)
+            FAIL(DVID_ERR_ARG, "set criterion: image %d holds %d ground-truth boxes, gmax is %d", i, g, gmax);
     if (gt_starts_host[n] > 0 && (!gt_boxes || !gt_labels)) FAIL(DVID_ERR_ARG, "set criterion: null ground truth");
     const long long need = dvid_set_criterion_scratch_bytes_host(n_sets, n, m, gmax);
-    if (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 15))
-        FAIL(DVID_ERR_ARG, "set criterion: the scratch holds %lld bytes, %lld are needed (16-byte aligned)", (long long)scratch_bytes, need);
+    TRY(scratch_ok("set criterion", scratch, scratch_bytes, need));
     TRY(dvid_set_criterion_launch(logits, boxes, n_sets, n, m, c, gt_boxes, gt_labels, gt_starts, sizes, alpha, gamma, ota_k, cost_class, cost_bbox, cost_giou,
                                   assign, matched_query, gmax, sums, status, scratch, reinterpret_cast<hipStream_t>(stream)));
     return DVID_OK;
@@ -386,18 +395,23 @@ int dvid_set_criterion_backward(const float* logits, const float* boxes, int n_s
     if (n_sets == 0 || n == 0) return DVID_OK;
     if (!logits || !boxes || !gt_starts || !gt_starts_host || !sizes || !assign || !status || !coef || !d_logits || !d_boxes)
         FAIL(DVID_ERR_ARG, "set criterion backward: null pointer");
-    if (gt_starts_host[0] != 0) FAIL(DVID_ERR_ARG, "set criterion backward: gt_starts[0] is %d, not 0", gt_starts_host[0]);
-    for (int i = 0; i < n; ++i) {
-        const int g = gt_starts_host[i + 1] - gt_starts_host[i];
-        if (g < 0) FAIL(DVID_ERR_ARG, "set criterion backward: gt_starts decreases at image %d", i);
-        if (g > DVID_CRITERION_MAX_GT)
-            FAIL(DVID_ERR_UNSUPPORTED, "set criterion backward: image %d holds %d ground-truth boxes, the limit is %d (DVID_CRITERION_MAX_GT)", i, g,
-                 DVID_CRITERION_MAX_GT);
-    }
+    TRY(csr_starts_ok("set criterion backward", "gt_starts", "image", gt_starts_host, n, nullptr, LIMIT(DVID_CRITERION_MAX_GT)));
     if (gt_starts_host[n] > 0 && (!gt_boxes || !gt_labels)) FAIL(DVID_ERR_ARG, "set criterion backward: null ground truth");
     TRY(dvid_set_criterion_backward_launch(logits, boxes, n_sets, n, m, c, gt_boxes, gt_labels, gt_starts, sizes, alpha, gamma, assign, status, coef, d_logits,
                                            d_boxes, reinterpret_cast<hipStream_t>(stream)));
     return DVID_OK;
+}
+
+// What dvid_coco_eval_match and dvid_lvis_eval_match check alike; `what` names the protocol, `pointers` is false when one the entry needs
+// is null, *max_gt gets the greatest box count of one image
+static int image_eval_args_ok(const char* what, bool pointers, int n_images, int cap, int num_classes, const int* gt_starts_host, int limit,
+                              const char* limit_name, int* max_gt) {
+    if (!pointers) FAIL(DVID_ERR_ARG, "%s: null pointer", what);
+    if (n_images < 0 || cap < 1 || num_classes < 1) FAIL(DVID_ERR_ARG, "%s: bad sizes (%d images, %d rows per image, %d classes)", what, n_images, cap, num_classes);
+    if (cap > DVID_NMS_MAX_CANDIDATES)
+        FAIL(DVID_ERR_UNSUPPORTED, "%s: %d rows per image exceed the limit of %d (DVID_NMS_MAX_CANDIDATES)", what, cap, DVID_NMS_MAX_CANDIDATES);
+    if (num_classes > DVID_MAX_CLASSES) FAIL(DVID_ERR_UNSUPPORTED, "%s: %d classes exceed the limit of %d (DVID_MAX_CLASSES)", what, num_classes, DVID_MAX_CLASSES);
+    return csr_starts_ok(what, "gt_starts", "image", gt_starts_host, n_images, max_gt, limit, limit_name);
 }
 
 int dvid_coco_eval_match(const float* dets, const int* counts, int n_images, int cap, const double* gt_boxes, const double* gt_areas,
@@ -405,34 +419,12 @@ int dvid_coco_eval_match(const float* dets, const int* counts, int n_images, int
                          const double* iou_thrs, const double* area_ranges, int num_classes, signed char* match, signed char* ignore,
                          int* rank, int* npig, void* stream) {
     g_err[0] = 0;
-    if (!dets || !counts || !gt_starts || !gt_starts_host || !iou_thrs || !area_ranges || !match || !ignore || !rank || !npig)
-        FAIL(DVID_ERR_ARG, "COCO evaluation: null pointer");
-    if (n_images < 0 || cap < 1 || num_classes < 1)
-        FAIL(DVID_ERR_ARG, "COCO evaluation: bad sizes (%d images, %d rows per image, %d classes)", n_images, cap, num_classes);
-    if (cap > DVID_NMS_MAX_CANDIDATES)
-        FAIL(DVID_ERR_UNSUPPORTED, "COCO evaluation: %d rows per image exceed the limit of %d (DVID_NMS_MAX_CANDIDATES)", cap, DVID_NMS_MAX_CANDIDATES);
-    if (num_classes > DVID_MAX_CLASSES)
-        FAIL(DVID_ERR_UNSUPPORTED, "COCO evaluation: %d classes exceed the limit of %d (DVID_MAX_CLASSES)", num_classes, DVID_MAX_CLASSES);
-    if (gt_starts_host[0] != 0) FAIL(DVID_ERR_ARG, "COCO evaluation: gt_starts[0] is %d, not 0", gt_starts_host[0]);
-    for (int f = 0; f < n_images; ++f) {
-        const int g = gt_starts_host[f + 1] - gt_starts_host[f];
-        if (g < 0) FAIL(DVID_ERR_ARG, "COCO evaluation: gt_starts decreases at image %d", f);
-        if (g > DVID_COCO_EVAL_MAX_GT)
-            FAIL(DVID_ERR_UNSUPPORTED, "COCO evaluation: image %d holds %d ground-truth boxes, the limit is %d (DVID_COCO_EVAL_MAX_GT)", f, g,
-                 DVID_COCO_EVAL_MAX_GT);
-    }
+    TRY(image_eval_args_ok("COCO evaluation", dets && counts && gt_starts && gt_starts_host && iou_thrs && area_ranges && match && ignore && rank && npig,
+                           n_images, cap, num_classes, gt_starts_host, LIMIT(DVID_COCO_EVAL_MAX_GT), nullptr));
     if (gt_starts_host[n_images] > 0 && (!gt_boxes || !gt_areas || !gt_crowd || !gt_labels)) FAIL(DVID_ERR_ARG, "COCO evaluation: null ground truth");
     TRY(dvid_coco_eval_match_launch(dets, counts, n_images, cap, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_starts, iou_thrs, area_ranges, num_classes,
                                     match, ignore, rank, npig, reinterpret_cast<hipStream_t>(stream)));
     return DVID_OK;
-}
-
-// a CSR table of per-image label lists: starts at 0 and never decreases
-static const char* lvis_list_fault(const int* starts, int n_images, int* at) {
-    if (starts[0] != 0) return *at = 0, "does not start at 0";
-    for (int f = 0; f < n_images; ++f)
-        if (starts[f + 1] < starts[f]) return *at = f, "decreases";
-    return nullptr;
 }
 
 int dvid_lvis_eval_match(const float* dets, const int* counts, int n_images, int cap, const double* gt_boxes, const double* gt_areas,
@@ -441,28 +433,12 @@ int dvid_lvis_eval_match(const float* dets, const int* counts, int n_images, int
                          const int* nex_starts_host, const double* iou_thrs, const double* area_ranges, int num_classes, signed char* match,
                          signed char* ignore, int* rank, int* npig, void* stream) {
     g_err[0] = 0;
-    if (!dets || !counts || !gt_starts || !gt_starts_host || !neg_starts || !neg_starts_host || !nex_starts || !nex_starts_host || !iou_thrs ||
-        !area_ranges || !match || !ignore || !rank || !npig)
-        FAIL(DVID_ERR_ARG, "LVIS evaluation: null pointer");
-    if (n_images < 0 || cap < 1 || num_classes < 1)
-        FAIL(DVID_ERR_ARG, "LVIS evaluation: bad sizes (%d images, %d rows per image, %d classes)", n_images, cap, num_classes);
-    if (cap > DVID_NMS_MAX_CANDIDATES)
-        FAIL(DVID_ERR_UNSUPPORTED, "LVIS evaluation: %d rows per image exceed the limit of %d (DVID_NMS_MAX_CANDIDATES)", cap, DVID_NMS_MAX_CANDIDATES);
-    if (num_classes > DVID_MAX_CLASSES)
-        FAIL(DVID_ERR_UNSUPPORTED, "LVIS evaluation: %d classes exceed the limit of %d (DVID_MAX_CLASSES)", num_classes, DVID_MAX_CLASSES);
-    if (gt_starts_host[0] != 0) FAIL(DVID_ERR_ARG, "LVIS evaluation: gt_starts[0] is %d, not 0", gt_starts_host[0]);
     int max_gt = 0;
-    for (int f = 0; f < n_images; ++f) {
-        const int g = gt_starts_host[f + 1] - gt_starts_host[f];
-        if (g < 0) FAIL(DVID_ERR_ARG, "LVIS evaluation: gt_starts decreases at image %d", f);
-        if (g > DVID_LVIS_EVAL_MAX_GT)
-            FAIL(DVID_ERR_UNSUPPORTED, "LVIS evaluation: image %d holds %d ground-truth boxes, the limit is %d (DVID_LVIS_EVAL_MAX_GT)", f, g,
-                 DVID_LVIS_EVAL_MAX_GT);
-        max_gt = g > max_gt ? g : max_gt;
-    }
-    int at = 0;
-    if (const char* what = lvis_list_fault(neg_starts_host, n_images, &at)) FAIL(DVID_ERR_ARG, "LVIS evaluation: neg_starts %s (image %d)", what, at);
-    if (const char* what = lvis_list_fault(nex_starts_host, n_images, &at)) FAIL(DVID_ERR_ARG, "LVIS evaluation: nex_starts %s (image %d)", what, at);
+    TRY(image_eval_args_ok("LVIS evaluation", dets && counts && gt_starts && gt_starts_host && neg_starts && neg_starts_host && nex_starts && nex_starts_host &&
+                                                  iou_thrs && area_ranges && match && ignore && rank && npig,
+                           n_images, cap, num_classes, gt_starts_host, LIMIT(DVID_LVIS_EVAL_MAX_GT), &max_gt));
+    TRY(csr_starts_ok("LVIS evaluation", "neg_starts", "image", neg_starts_host, n_images));
+    TRY(csr_starts_ok("LVIS evaluation", "nex_starts", "image", nex_starts_host, n_images));
     if (gt_starts_host[n_images] > 0 && (!gt_boxes || !gt_areas || !gt_ignore || !gt_labels)) FAIL(DVID_ERR_ARG, "LVIS evaluation: null ground truth");
     if ((neg_starts_host[n_images] > 0 && !neg_labels) || (nex_starts_host[n_images] > 0 && !nex_labels))
         FAIL(DVID_ERR_ARG, "LVIS evaluation: null negative or not-exhaustive labels");
@@ -508,8 +484,7 @@ int dvid_eval_accumulate(const float* dets, const int* counts, const int* rank, 
     if (need > DVID_EVAL_ACCUMULATE_MAX_SCRATCH_BYTES)
         FAIL(DVID_ERR_UNSUPPORTED, "evaluation accumulate: %lld bytes of sort buffers for %lld rows (56 bytes per row) exceed the limit of %lld "
              "(DVID_EVAL_ACCUMULATE_MAX_SCRATCH_BYTES): evaluate fewer images per call", need, rows, (long long)DVID_EVAL_ACCUMULATE_MAX_SCRATCH_BYTES);
-    if (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 15))
-        FAIL(DVID_ERR_ARG, "evaluation accumulate: the scratch holds %lld bytes, %lld are needed (16-byte aligned)", scratch_bytes, need);
+    TRY(scratch_ok("evaluation accumulate", scratch, scratch_bytes, need));
     if (rows > 0 && (!dets || !counts || !rank || !match || !ignore)) FAIL(DVID_ERR_ARG, "evaluation accumulate: null pointer");
     TRY(dvid_eval_accumulate_launch(dets, counts, rank, match, ignore, npig, n_images, cap, num_classes, max_dets, max_dets_count, rec_thrs, precision,
                                     recall, scratch, reinterpret_cast<hipStream_t>(stream)));

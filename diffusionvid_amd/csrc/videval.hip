@@ -15,25 +15,14 @@
 // comparisons and ig.sum() / len float64.  The comparisons are written as calc_prec_rec writes them, so a NaN takes the same branch.
 #include "../../include/dvid_hip.h"
 #include "kernels.h"
-
-typedef unsigned long long u64;
+#include "evalmatch.h"          // the key, the sort and the segment heads
 
 #define VE_THREADS 256
-#define VE_PAD (~(u64)0)
 #define VE_MAX_SEGS (DVID_MAX_CLASSES + 1)          // labels 0 .. DVID_MAX_CLASSES
 
 struct VidEvalRanges {
     double lo[DVID_VID_EVAL_MAX_RANGES], hi[DVID_VID_EVAL_MAX_RANGES], empty_w[DVID_VID_EVAL_MAX_RANGES];
 };
-
-// key: label (bits 44..), the score's bits mapped so that a greater score is a smaller number (bits 12..43), the row (bits 0..11)
-__device__ __forceinline__ unsigned ve_score_desc(float s) {
-    if (s == 0.f) s = 0.f;          // -0 and +0 are one score
-    const unsigned b = __float_as_uint(s);
-    return ~(b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u));
-}
-__device__ __forceinline__ int ve_label(u64 key) { return (int)(key >> 44); }
-__device__ __forceinline__ int ve_row(u64 key) { return (int)(key & 0xfff); }
 
 // `g` already has + 1 on x2, y2; `p` gets it here
 __device__ __forceinline__ float vid_iou(const float* __restrict__ d, const float4v g, const float ga) {
@@ -92,16 +81,16 @@ __global__ __launch_bounds__(VE_THREADS) void vid_eval_match_kernel(const float*
     // ---- the keys; the rows that belong to no segment; the top-scoring row (the lowest row of equal scores) ----
     u64 top = 0;
     for (int i = tid; i < P; i += VE_THREADS) {
-        u64 key = VE_PAD;
+        u64 key = EM_PAD;
         if (i < n) {
             const float sc = d[(size_t)i * 6 + 4];
             const int l = (int)d[(size_t)i * 6 + 5];
-            if (l >= 0 && l <= num_classes) key = ((u64)l << 44) | ((u64)ve_score_desc(sc) << 12) | (u64)i;
-            const u64 t = ((u64)(~ve_score_desc(sc)) << 32) | (u64)(0xffffffffu - (unsigned)i);
+            if (l >= 0 && l <= num_classes) key = em_key(l, ce_score_desc(sc), i);
+            const u64 t = ((u64)(~ce_score_desc(sc)) << 32) | (u64)(0xffffffffu - (unsigned)i);
             top = t > top ? t : top;
         }
         s_key[i] = key;
-        if (i < cap && key == VE_PAD) {
+        if (i < cap && key == EM_PAD) {
             rank[frame + i] = -1;
             for (int r = 0; r < R; ++r) match[r * plane + frame + i] = 0, weight[r * plane + frame + i] = 0.0;
         }
@@ -129,42 +118,22 @@ __global__ __launch_bounds__(VE_THREADS) void vid_eval_match_kernel(const float*
         if (tid == 0) top_row[f] = row, top_hit[f] = (signed char)s_hit;
     }
 
-    // ---- sort ----
     int Pf = 64;          // the frame's own power of two
     while (Pf < n) Pf <<= 1;
-    for (int k = 2; k <= Pf; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < Pf; i += VE_THREADS) {
-                const int x = i ^ j;
-                if (x > i) {
-                    const u64 a = s_key[i], b = s_key[x];
-                    if ((a > b) == ((i & k) == 0)) s_key[i] = b, s_key[x] = a;
-                }
-            }
-            __syncthreads();
-        }
-    // ---- segment heads (their order in s_seg does not matter: the segments are independent) ----
-    for (int i = tid; i < n; i += VE_THREADS) {
-        const u64 key = s_key[i];
-        if (key != VE_PAD && (i == 0 || ve_label(s_key[i - 1]) != ve_label(key))) {
-            const int at = atomicAdd(&s_nseg, 1);
-            if (at < VE_MAX_SEGS) s_seg[at] = (unsigned short)i;
-        }
-    }
-    __syncthreads();
-    const int nseg = min(s_nseg, VE_MAX_SEGS);
+    em_sort<VE_THREADS>(s_key, Pf, tid);
+    const int nseg = em_segment_heads<VE_THREADS>(s_key, n, tid, &s_nseg, s_seg, VE_MAX_SEGS);
 
     // ---- the matching: a lane per (segment, range) ----
     for (int t = tid; t < nseg * R; t += VE_THREADS) {
         const int start = s_seg[t / R], r = t - (t / R) * R;
-        const int l = ve_label(s_key[start]);
+        const int l = em_label(s_key[start]);
         const double empty_w = rg.empty_w[r];
         signed char* m_out = match + r * plane + frame;
         double* w_out = weight + r * plane + frame;
         for (int i = start; i < n; ++i) {
             const u64 key = s_key[i];
-            if (key == VE_PAD || ve_label(key) != l) break;
-            const int row = ve_row(key);
+            if (key == EM_PAD || em_label(key) != l) break;
+            const int row = em_row(key);
             if (r == 0) rank[frame + row] = i - start;
             const float* p = d + (size_t)row * 6;
             float best = thr, top_ig = -1.f, top_cnt = -1.f;

@@ -25,6 +25,7 @@ total -- label, score descending, image, rank -- and the rest is integer counts 
 Not here: segmentation and keypoint evaluation, proposal recall, evaluation spread over ranks; LVIS' federated protocol is lvis_eval.py."""
 import json
 import os
+import sys
 from collections import OrderedDict
 
 import numpy as np
@@ -130,6 +131,46 @@ def _ious(d, g, crowd):
         return np.where((w <= 0) | (h <= 0), 0.0, i / u)
 
 
+def _match_setup(N, cap, gt_flag, gt_areas, gt_labels, num_classes):
+    """what a match_numpy starts from -> (match, ignore, rank, npig, gig_all): the four outputs with no row matched and npig counted, and
+    gig_all [A, G] bool: the box is flagged (COCO: crowd, LVIS: ignore) or its area lies outside the range"""
+    A, T = len(AREA_RANGES), len(IOU_THRS)
+    match, ignore = np.zeros((A, T, N, cap), dtype=np.int8), np.zeros((A, T, N, cap), dtype=np.int8)
+    rank = np.full((N, cap), -1, dtype=np.int32)
+    npig = np.zeros((A, num_classes + 1), dtype=np.int32)
+    gig_all = np.stack([gt_flag | (gt_areas < lo) | (gt_areas > hi) for lo, hi in AREA_RANGES])
+    ok = (gt_labels >= 0) & (gt_labels <= num_classes)
+    for a in range(A):
+        np.add.at(npig[a], gt_labels[ok & ~gig_all[a]], 1)
+    return match, ignore, rank, npig, gig_all
+
+
+def _match_label(match, ignore, f, sel, xywh, g_boxes, gig, crowd, unmatched):
+    """The rows `sel` of image f, one label's in descending score, against that label's boxes g_boxes [n_g, 4] with gig [A, n_g]; written
+    to match / ignore [:, :, f, sel].  crowd [n_g] bool: the box can be taken again; unmatched [A, n] bool by row of the image: what a row
+    that takes no box gets as its ignore."""
+    if len(g_boxes) == 0:
+        ignore[:, :, f, sel] = unmatched[:, None, sel]
+        return
+    T, best0 = len(IOU_THRS), np.minimum(IOU_THRS, 1 - 1e-10)
+    iou = _ious(tuple(c[sel] for c in xywh), g_boxes.T, crowd)
+    for a in range(len(AREA_RANGES)):
+        gorder = np.argsort(gig[a], kind="mergesort")
+        taken = np.zeros((T, len(g_boxes)), dtype=bool)
+        for d, row in enumerate(sel):
+            best, m, m_ig = best0.copy(), np.full(T, -1), np.zeros(T, dtype=bool)
+            for k in gorder:
+                free = ~taken[:, k] | crowd[k]
+                if gig[a, k]:
+                    free &= ~((m > -1) & ~m_ig)
+                take = free & ~(iou[d, k] < best)
+                best[take], m[take], m_ig[take] = iou[d, k], k, gig[a, k]
+            hit = m > -1
+            taken[hit, m[hit]] = True
+            match[a, :, f, row] = hit
+            ignore[a, :, f, row] = np.where(hit, m_ig, unmatched[a, row])
+
+
 def match_numpy(dets, counts, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_starts, num_classes):
     """The matching, in the layout of ops.coco_eval_match: (match [4, 10, N, cap] int8, ignore [4, 10, N, cap] int8, rank [N, cap] int32,
     npig [4, num_classes + 1] int32).  Vectorised over the thresholds; images, labels, area ranges, detections and boxes are loops."""
@@ -137,15 +178,8 @@ def match_numpy(dets, counts, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_starts
     gt_boxes, gt_areas, gt_crowd = _np(gt_boxes, np.float64).reshape(-1, 4), _np(gt_areas, np.float64), _np(gt_crowd).astype(bool)
     gt_labels, gt_starts = _np(gt_labels, np.int64), _np(gt_starts, np.int64)
     N, cap = dets.shape[:2]
-    A, T, top = len(AREA_RANGES), len(IOU_THRS), MAX_DETS[-1]
-    match, ignore = np.zeros((A, T, N, cap), dtype=np.int8), np.zeros((A, T, N, cap), dtype=np.int8)
-    rank = np.full((N, cap), -1, dtype=np.int32)
-    npig = np.zeros((A, num_classes + 1), dtype=np.int32)
-    gig_all = np.stack([gt_crowd | (gt_areas < lo) | (gt_areas > hi) for lo, hi in AREA_RANGES])          # [A, G]
-    ok = (gt_labels >= 0) & (gt_labels <= num_classes)
-    for a in range(A):
-        np.add.at(npig[a], gt_labels[ok & ~gig_all[a]], 1)
-    best0 = np.minimum(IOU_THRS, 1 - 1e-10)
+    top = MAX_DETS[-1]
+    match, ignore, rank, npig, gig_all = _match_setup(N, cap, gt_crowd, gt_areas, gt_labels, num_classes)
     for f in range(N):
         n = int(min(max(counts[f], 0), cap))
         if n == 0:
@@ -160,27 +194,7 @@ def match_numpy(dets, counts, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_starts
             sel = idx[np.argsort(-rows[idx, 4], kind="mergesort")[:top]]
             rank[f, sel] = np.arange(len(sel))
             gi = g0 + np.nonzero(gt_labels[g0:g1] == l)[0]
-            if len(gi) == 0:
-                ignore[:, :, f, sel] = d_out[:, None, sel]
-                continue
-            crowd = gt_crowd[gi]
-            iou = _ious((x[sel], y[sel], w[sel], h[sel]), gt_boxes[gi].T, crowd)
-            for a in range(A):
-                gig = gig_all[a][gi]
-                gorder = np.argsort(gig, kind="mergesort")
-                taken = np.zeros((T, len(gi)), dtype=bool)
-                for d, row in enumerate(sel):
-                    best, m, m_ig = best0.copy(), np.full(T, -1), np.zeros(T, dtype=bool)
-                    for k in gorder:
-                        free = ~taken[:, k] | crowd[k]
-                        if gig[k]:
-                            free &= ~((m > -1) & ~m_ig)
-                        take = free & ~(iou[d, k] < best)
-                        best[take], m[take], m_ig[take] = iou[d, k], k, gig[k]
-                    hit = m > -1
-                    taken[hit, m[hit]] = True
-                    match[a, :, f, row] = hit
-                    ignore[a, :, f, row] = np.where(hit, m_ig, d_out[a, row])
+            _match_label(match, ignore, f, sel, (x, y, w, h), gt_boxes[gi], gig_all[:, gi], gt_crowd[gi], d_out)
     return match, ignore, rank, npig
 
 
@@ -287,41 +301,48 @@ def evaluate_numpy(dets, counts, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_sta
     return _tail(dets, counts, got[2], got[0], got[1], got[3])
 
 
+def _evaluate_on_device(dets, counts, gt, match_op, num_classes, max_dets, summarize, device, times, accumulate):
+    """What the evaluate_device of COCO and of LVIS do alike.  gt: the ground truth as (array, numpy dtype) pairs in the order match_op
+    (ops.coco_eval_match / ops.lvis_eval_match) takes them; max_dets: the protocol's detection limits; summarize(precision, recall) -> stats"""
+    from ... import ops
+    dets = torch.as_tensor(dets)
+    device = torch.device(device) if device is not None else dets.device
+    check_accumulate(accumulate, device)
+    lap = _Laps(times, device)
+    dets = dets.to(device=device, dtype=torch.float32)
+    counts = torch.as_tensor(counts).to(device=device, dtype=torch.int32)
+    if dets.shape[1] == 0:
+        dets = dets.new_zeros((dets.shape[0], 1, 6))
+    gt = [torch.from_numpy(np.ascontiguousarray(_np(a, t))).to(device) for a, t in gt]
+    lap("copy_in")
+    got = match_op(dets, counts, *gt, num_classes, IOU_THRS, AREA_RANGES)
+    lap("kernel")
+    if accumulate == "device":
+        match, ignore, rank, npig = got
+        pr, rc = ops.eval_accumulate(dets, counts, rank, match, ignore, npig, max_dets, REC_THRS)
+        lap("accumulate")
+        precision, recall = pr.cpu().numpy(), rc.cpu().numpy()
+        lap("copy_out")
+    else:
+        match, ignore, rank, npig = (t.cpu().numpy() for t in got)
+        host, counts = dets.cpu(), counts.cpu().numpy()
+        lap("copy_out")
+        host = _np(host[:, :, 4:6])
+        precision, recall = accumulate_arrays(np.ascontiguousarray(host[:, :, 0]), host[:, :, 1].astype(np.int64), counts, rank, match, ignore, npig,
+                                              max_dets)
+    out = {"precision": precision, "recall": recall, "stats": summarize(precision, recall)}
+    lap("tail")
+    return out
+
+
 def evaluate_device(dets, counts, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_starts, num_classes, device=None, times=None, accumulate="numpy"):
     """evaluate_numpy with the matching as one kernel call on `device` (default: where dets is); the accumulation is the same numpy
     code on the same arrays, so the result is equal.  times: see vid_eval._Laps (copy_in, kernel, copy_out, tail).
     accumulate "device": match, ignore and rank stay on the device, ops.eval_accumulate runs there and only precision and recall
     come back (equal again: csrc/evalaccum.hip); the laps are then copy_in, kernel, accumulate, copy_out, tail (summarize)."""
     from ... import ops
-    if accumulate not in ACCUMULATE_MODES:
-        raise ValueError("accumulate is 'numpy' or 'device', not %r" % (accumulate,))
-    dets = torch.as_tensor(dets)
-    device = torch.device(device) if device is not None else dets.device
-    lap = _Laps(times, device)
-    dets = dets.to(device=device, dtype=torch.float32)
-    counts = torch.as_tensor(counts).to(device=device, dtype=torch.int32)
-    if dets.shape[1] == 0:
-        dets = dets.new_zeros((dets.shape[0], 1, 6))
-    gt = [torch.from_numpy(np.ascontiguousarray(_np(a, t))).to(device) for a, t in
-          ((gt_boxes, np.float64), (gt_areas, np.float64), (gt_crowd, np.uint8), (gt_labels, np.int32), (gt_starts, np.int32))]
-    lap("copy_in")
-    got = ops.coco_eval_match(dets, counts, *gt, num_classes, IOU_THRS, AREA_RANGES)
-    lap("kernel")
-    if accumulate == "device":
-        match, ignore, rank, npig = got
-        pr, rc = ops.eval_accumulate(dets, counts, rank, match, ignore, npig, MAX_DETS, REC_THRS)
-        lap("accumulate")
-        precision, recall = pr.cpu().numpy(), rc.cpu().numpy()
-        lap("copy_out")
-        out = {"precision": precision, "recall": recall, "stats": summarize(precision, recall)}
-        lap("tail")
-        return out
-    match, ignore, rank, npig = (t.cpu().numpy() for t in got)
-    host, counts = dets.cpu(), counts.cpu().numpy()
-    lap("copy_out")
-    out = _tail(host, counts, rank, match, ignore, npig)
-    lap("tail")
-    return out
+    gt = ((gt_boxes, np.float64), (gt_areas, np.float64), (gt_crowd, np.uint8), (gt_labels, np.int32), (gt_starts, np.int32))
+    return _evaluate_on_device(dets, counts, gt, ops.coco_eval_match, num_classes, MAX_DETS, summarize, device, times, accumulate)
 
 
 def result_string(stats):
@@ -338,15 +359,11 @@ def result_string(stats):
     return text
 
 
-def do_coco_evaluation(annotations, predictions, output_folder=None, device=None, logger=None, times=None, accumulate="numpy"):
-    """annotations: a CocoAnnotations, a path or a dict; predictions: {image id: BoxList} as engine.inference_images returns them (boxes
-    xyxy in the original image's pixels, `scores`, `labels` 1 .. K in CocoAnnotations' order).  Every image of the annotations is
-    evaluated, one without a prediction as an image without detections; a prediction for an image the annotations do not list, or a
-    label outside 1 .. K, is an error.  -> an ordered dict of the twelve numbers (STAT_NAMES); the text goes to the logger and to
-    `output_folder/coco_eval.txt`.  device: a torch.device runs the matching there and writes the same text; None is the numpy path.
-    accumulate: "device" runs the accumulation on `device` too (evaluate_device) and writes the same text again."""
+def _do_evaluation(protocol, annotations_class, file_name, annotations, predictions, output_folder, device, logger, times, accumulate):
+    """What do_coco_evaluation and do_lvis_evaluation do alike.  protocol: the module (this one or lvis_eval) with pack_groundtruth,
+    evaluate_numpy, evaluate_device, result_string and STAT_NAMES; the text goes to output_folder/file_name"""
     check_accumulate(accumulate, device)
-    ann = annotations if isinstance(annotations, CocoAnnotations) else CocoAnnotations(annotations)
+    ann = annotations if isinstance(annotations, annotations_class) else annotations_class(annotations)
     lap = _Laps(times, torch.device(device) if device is not None else torch.device("cpu"))
     counts, dets = pack_detections(predictions, ann.image_ids)
     live = torch.arange(dets.shape[1])[None, :] < counts[:, None]
@@ -354,17 +371,27 @@ def do_coco_evaluation(annotations, predictions, output_folder=None, device=None
     if bool(bad.any()):
         f, r = [int(v) for v in torch.nonzero(bad)[0]]
         raise ValueError("image id %d: label %d is outside 1 .. %d" % (ann.image_ids[f], int(dets[f, r, 5]), ann.num_classes))
-    gt = pack_groundtruth(ann)
+    gt = protocol.pack_groundtruth(ann)
     lap("pack")
     if device is None:
-        res = evaluate_numpy(dets, counts, *gt, max(1, ann.num_classes))
+        res = protocol.evaluate_numpy(dets, counts, *gt, max(1, ann.num_classes))
     else:
-        res = evaluate_device(dets, counts, *gt, max(1, ann.num_classes), device=device, times=times, accumulate=accumulate)
-    text = result_string(res["stats"])
+        res = protocol.evaluate_device(dets, counts, *gt, max(1, ann.num_classes), device=device, times=times, accumulate=accumulate)
+    text = protocol.result_string(res["stats"])
     if logger is not None:
         logger.info("\n" + text)
     if output_folder:
         os.makedirs(output_folder, exist_ok=True)
-        with open(os.path.join(output_folder, "coco_eval.txt"), "w") as fid:
+        with open(os.path.join(output_folder, file_name), "w") as fid:
             fid.write(text)
-    return OrderedDict(zip(STAT_NAMES, (float(v) for v in res["stats"])))
+    return OrderedDict(zip(protocol.STAT_NAMES, (float(v) for v in res["stats"])))
+
+
+def do_coco_evaluation(annotations, predictions, output_folder=None, device=None, logger=None, times=None, accumulate="numpy"):
+    """annotations: a CocoAnnotations, a path or a dict; predictions: {image id: BoxList} as engine.inference_images returns them (boxes
+    xyxy in the original image's pixels, `scores`, `labels` 1 .. K in CocoAnnotations' order).  Every image of the annotations is
+    evaluated, one without a prediction as an image without detections; a prediction for an image the annotations do not list, or a
+    label outside 1 .. K, is an error.  -> an ordered dict of the twelve numbers (STAT_NAMES); the text goes to the logger and to
+    `output_folder/coco_eval.txt`.  device: a torch.device runs the matching there and writes the same text; None is the numpy path.
+    accumulate: "device" runs the accumulation on `device` too (evaluate_device) and writes the same text again."""
+    return _do_evaluation(sys.modules[__name__], CocoAnnotations, "coco_eval.txt", annotations, predictions, output_folder, device, logger, times, accumulate)

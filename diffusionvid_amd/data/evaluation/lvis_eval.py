@@ -25,15 +25,13 @@ that nobody looked for as a false positive.  This module states the LVIS protoco
 Both paths produce (match, ignore, rank, npig) in coco_eval's layout and share the accumulation, so their results are equal, not close.
 Not here: segmentation masks, the `ignore`-region variants of the protocol, evaluation spread over ranks."""
 import json
-import os
-from collections import OrderedDict
+import sys
 
 import numpy as np
 import torch
 
 from . import coco_eval
 from .coco_eval import AREA_NAMES, AREA_RANGES, IOU_THRS, REC_THRS, _ious, _mean, _np, _xywh, pack_detections          # noqa: F401
-from .vid_eval import _Laps
 
 MAX_DETS = 300
 FREQUENCIES = ("r", "c", "f")
@@ -117,15 +115,7 @@ def match_numpy(dets, counts, gt_boxes, gt_areas, gt_ignore, gt_labels, gt_start
     neg_starts, neg_labels = _np(neg_starts, np.int64), _np(neg_labels, np.int64)
     nex_starts, nex_labels = _np(nex_starts, np.int64), _np(nex_labels, np.int64)
     N, cap = dets.shape[:2]
-    A, T = len(AREA_RANGES), len(IOU_THRS)
-    match, ignore = np.zeros((A, T, N, cap), dtype=np.int8), np.zeros((A, T, N, cap), dtype=np.int8)
-    rank = np.full((N, cap), -1, dtype=np.int32)
-    npig = np.zeros((A, num_classes + 1), dtype=np.int32)
-    gig_all = np.stack([gt_ignore | (gt_areas < lo) | (gt_areas > hi) for lo, hi in AREA_RANGES])          # [A, G]
-    ok = (gt_labels >= 0) & (gt_labels <= num_classes)
-    for a in range(A):
-        np.add.at(npig[a], gt_labels[ok & ~gig_all[a]], 1)
-    best0 = np.minimum(IOU_THRS, 1 - 1e-10)
+    match, ignore, rank, npig, gig_all = coco_eval._match_setup(N, cap, gt_ignore, gt_areas, gt_labels, num_classes)
     for f in range(N):
         n = int(min(max(counts[f], 0), cap))
         if n == 0:
@@ -144,28 +134,8 @@ def match_numpy(dets, counts, gt_boxes, gt_areas, gt_ignore, gt_labels, gt_start
         for l in np.unique(lab[cand]):
             sel = cand[lab[cand] == l]
             rank[f, sel] = np.arange(len(sel))
-            unmatched = d_out | nex[l]
             gi = g0 + np.nonzero(gt_labels[g0:g1] == l)[0]
-            if len(gi) == 0:
-                ignore[:, :, f, sel] = unmatched[:, None, sel]
-                continue
-            iou = _ious((x[sel], y[sel], w[sel], h[sel]), gt_boxes[gi].T, np.zeros(len(gi), dtype=bool))
-            for a in range(A):
-                gig = gig_all[a][gi]
-                gorder = np.argsort(gig, kind="mergesort")
-                taken = np.zeros((T, len(gi)), dtype=bool)
-                for d, row in enumerate(sel):
-                    best, m, m_ig = best0.copy(), np.full(T, -1), np.zeros(T, dtype=bool)
-                    for k in gorder:
-                        free = ~taken[:, k]
-                        if gig[k]:
-                            free &= ~((m > -1) & ~m_ig)
-                        take = free & ~(iou[d, k] < best)
-                        best[take], m[take], m_ig[take] = iou[d, k], k, gig[k]
-                    hit = m > -1
-                    taken[hit, m[hit]] = True
-                    match[a, :, f, row] = hit
-                    ignore[a, :, f, row] = np.where(hit, m_ig, unmatched[a, row])
+            coco_eval._match_label(match, ignore, f, sel, (x, y, w, h), gt_boxes[gi], gig_all[:, gi], np.zeros(len(gi), dtype=bool), d_out | nex[l])
     return match, ignore, rank, npig
 
 
@@ -213,36 +183,11 @@ def evaluate_device(dets, counts, gt_boxes, gt_areas, gt_ignore, gt_labels, gt_s
     code on the same arrays, so the result is equal.  times: see vid_eval._Laps (copy_in, kernel, copy_out, tail).
     accumulate "device": as coco_eval.evaluate_device, with the one limit 300 (laps copy_in, kernel, accumulate, copy_out, tail)."""
     from ... import ops
-    if accumulate not in coco_eval.ACCUMULATE_MODES:
-        raise ValueError("accumulate is 'numpy' or 'device', not %r" % (accumulate,))
-    dets = torch.as_tensor(dets)
-    device = torch.device(device) if device is not None else dets.device
-    lap = _Laps(times, device)
-    dets = dets.to(device=device, dtype=torch.float32)
-    counts = torch.as_tensor(counts).to(device=device, dtype=torch.int32)
-    if dets.shape[1] == 0:
-        dets = dets.new_zeros((dets.shape[0], 1, 6))
-    gt = [torch.from_numpy(np.ascontiguousarray(_np(a, t))).to(device) for a, t in
-          ((gt_boxes, np.float64), (gt_areas, np.float64), (gt_ignore, np.uint8), (gt_labels, np.int32), (gt_starts, np.int32),
-           (neg_starts, np.int32), (neg_labels, np.int32), (nex_starts, np.int32), (nex_labels, np.int32))]
-    lap("copy_in")
-    got = ops.lvis_eval_match(dets, counts, *gt, num_classes, IOU_THRS, AREA_RANGES)
-    lap("kernel")
-    if accumulate == "device":
-        match, ignore, rank, npig = got
-        pr, rc = ops.eval_accumulate(dets, counts, rank, match, ignore, npig, (MAX_DETS,), coco_eval.REC_THRS)
-        lap("accumulate")
-        precision, recall = pr.cpu().numpy(), rc.cpu().numpy()
-        lap("copy_out")
-        out = {"precision": precision, "recall": recall, "stats": summarize(precision, recall, _frequency(frequency, num_classes))}
-        lap("tail")
-        return out
-    match, ignore, rank, npig = (t.cpu().numpy() for t in got)
-    host, counts = dets.cpu(), counts.cpu().numpy()
-    lap("copy_out")
-    out = _tail(host, counts, rank, match, ignore, npig, _frequency(frequency, num_classes))
-    lap("tail")
-    return out
+    gt = ((gt_boxes, np.float64), (gt_areas, np.float64), (gt_ignore, np.uint8), (gt_labels, np.int32), (gt_starts, np.int32),
+          (neg_starts, np.int32), (neg_labels, np.int32), (nex_starts, np.int32), (nex_labels, np.int32))
+    return coco_eval._evaluate_on_device(dets, counts, gt, ops.lvis_eval_match, num_classes, (MAX_DETS,),
+                                         lambda precision, recall: summarize(precision, recall, _frequency(frequency, num_classes)), device, times,
+                                         accumulate)
 
 
 def result_string(stats):
@@ -280,26 +225,5 @@ def do_lvis_evaluation(annotations, predictions, output_folder=None, device=None
     label outside 1 .. K, is an error.  -> an ordered dict of the thirteen numbers (STAT_NAMES); the text goes to the logger and to
     `output_folder/lvis_eval.txt`.  device: a torch.device runs the matching there and writes the same text; None is the numpy path.
     accumulate: "device" runs the accumulation on `device` too (evaluate_device) and writes the same text again."""
-    coco_eval.check_accumulate(accumulate, device)
-    ann = annotations if isinstance(annotations, LvisAnnotations) else LvisAnnotations(annotations)
-    lap = _Laps(times, torch.device(device) if device is not None else torch.device("cpu"))
-    counts, dets = pack_detections(predictions, ann.image_ids)
-    live = torch.arange(dets.shape[1])[None, :] < counts[:, None]
-    bad = live & ((dets[:, :, 5] < 1) | (dets[:, :, 5] > ann.num_classes))
-    if bool(bad.any()):
-        f, r = [int(v) for v in torch.nonzero(bad)[0]]
-        raise ValueError("image id %d: label %d is outside 1 .. %d" % (ann.image_ids[f], int(dets[f, r, 5]), ann.num_classes))
-    gt = pack_groundtruth(ann)
-    lap("pack")
-    if device is None:
-        res = evaluate_numpy(dets, counts, *gt, max(1, ann.num_classes))
-    else:
-        res = evaluate_device(dets, counts, *gt, max(1, ann.num_classes), device=device, times=times, accumulate=accumulate)
-    text = result_string(res["stats"])
-    if logger is not None:
-        logger.info("\n" + text)
-    if output_folder:
-        os.makedirs(output_folder, exist_ok=True)
-        with open(os.path.join(output_folder, "lvis_eval.txt"), "w") as fid:
-            fid.write(text)
-    return OrderedDict(zip(STAT_NAMES, (float(v) for v in res["stats"])))
+    return coco_eval._do_evaluation(sys.modules[__name__], LvisAnnotations, "lvis_eval.txt", annotations, predictions, output_folder, device, logger,
+                                    times, accumulate)

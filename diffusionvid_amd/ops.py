@@ -753,14 +753,9 @@ def vid_eval_match(dets, counts, gt_boxes, gt_labels, gt_starts, num_classes, mo
 COCO_EVAL_MAX_GT, COCO_EVAL_THRESHOLDS, COCO_EVAL_AREAS, COCO_EVAL_MAX_DETS = 256, 10, 4, 100          # include/dvid_hip.h
 
 
-def coco_eval_match(dets, counts, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_starts, num_classes, iou_thrs, area_ranges, out=None):
-    """The COCO bbox evaluator's matching (coco_eval.evaluate_numpy's loop) for the ten IoU thresholds and the four area ranges in one
-    launch (csrc/cocoeval.hip).  dets [N, cap, 6] fp32 and counts [N] int32 in engine.pack_predictions' layout with the boxes in
-    annotation pixels; gt_boxes [G, 4] float64 xywh, gt_areas [G] float64, gt_crowd [G] uint8, gt_labels [G] int32, gt_starts [N + 1]
-    int32: the ragged ground truth (coco_eval.pack_groundtruth).  All tensors on the device.  iou_thrs: 10 floats, area_ranges: 4 pairs
-    (lo, hi), taken as float64.  Returns (match [4, 10, N, cap] int8, ignore [4, 10, N, cap] int8, rank [N, cap] int32, npig
-    [4, num_classes + 1] int32) on the device (include/dvid_hip.h says what each holds); `out`: such a tuple to write into.  The scores
-    must be finite."""
+def _eval_match_tables(dets, counts, num_classes, iou_thrs, area_ranges, out):
+    """what coco_eval_match and lvis_eval_match do alike in front of the ground truth -> (dets, counts, thr, rng, out): the casts, the
+    threshold and range tables on the host, and the (match, ignore, rank, npig) tuple, made or checked"""
     dets, counts = _cuda(dets, torch.float32), _cuda(counts, torch.int32)
     N, cap = counts.shape[0], dets.shape[1] if dets.dim() == 3 else -1
     assert dets.shape == (N, cap, 6), "dets is [images, cap, 6]"
@@ -775,17 +770,36 @@ def coco_eval_match(dets, counts, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_st
     match, ignore, rank, npig = out
     assert match.shape == ignore.shape == (A, T, N, cap) and rank.shape == (N, cap) and npig.shape == (A, num_classes + 1), "output shapes"
     assert (match.dtype, ignore.dtype, rank.dtype, npig.dtype) == (torch.int8, torch.int8, torch.int32, torch.int32), "output dtypes"
-    if N == 0 or cap == 0:
-        npig.zero_()
-        return out
+    return dets, counts, thr, rng, out
+
+
+def _eval_match_groundtruth(N, gt_boxes, gt_areas, gt_flag, gt_labels, gt_starts):
+    """the five ground-truth tensors of N images, cast and checked, and gt_starts on the host"""
     gt_boxes, gt_areas = _cuda(gt_boxes, torch.float64).reshape(-1, 4), _cuda(gt_areas, torch.float64)
-    gt_crowd, gt_labels, gt_starts = _cuda(gt_crowd, torch.uint8), _cuda(gt_labels, torch.int32), _cuda(gt_starts, torch.int32)
+    gt_flag, gt_labels, gt_starts = _cuda(gt_flag, torch.uint8), _cuda(gt_labels, torch.int32), _cuda(gt_starts, torch.int32)
     G = gt_boxes.shape[0]
-    assert gt_starts.shape == (N + 1,) and gt_areas.shape == gt_crowd.shape == gt_labels.shape == (G,), "gt_starts is [images + 1]"
+    assert gt_starts.shape == (N + 1,) and gt_areas.shape == gt_flag.shape == gt_labels.shape == (G,), "gt_starts is [images + 1]"
     starts_host = gt_starts.cpu()
     assert int(starts_host[-1]) == G, "gt_starts ends at the box count"
-    call("dvid_coco_eval_match", ptr(dets), ptr(counts), N, cap, ptr(gt_boxes), ptr(gt_areas), ptr(gt_crowd), ptr(gt_labels), ptr(gt_starts),
-         ptr(starts_host), ptr(thr), ptr(rng), int(num_classes), *(ptr(_cuda(o)) for o in out), stream_ptr())
+    return gt_boxes, gt_areas, gt_flag, gt_labels, gt_starts, starts_host
+
+
+def coco_eval_match(dets, counts, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_starts, num_classes, iou_thrs, area_ranges, out=None):
+    """The COCO bbox evaluator's matching (coco_eval.evaluate_numpy's loop) for the ten IoU thresholds and the four area ranges in one
+    launch (csrc/cocoeval.hip).  dets [N, cap, 6] fp32 and counts [N] int32 in engine.pack_predictions' layout with the boxes in
+    annotation pixels; gt_boxes [G, 4] float64 xywh, gt_areas [G] float64, gt_crowd [G] uint8, gt_labels [G] int32, gt_starts [N + 1]
+    int32: the ragged ground truth (coco_eval.pack_groundtruth).  All tensors on the device.  iou_thrs: 10 floats, area_ranges: 4 pairs
+    (lo, hi), taken as float64.  Returns (match [4, 10, N, cap] int8, ignore [4, 10, N, cap] int8, rank [N, cap] int32, npig
+    [4, num_classes + 1] int32) on the device (include/dvid_hip.h says what each holds); `out`: such a tuple to write into.  The scores
+    must be finite."""
+    dets, counts, thr, rng, out = _eval_match_tables(dets, counts, num_classes, iou_thrs, area_ranges, out)
+    N, cap = dets.shape[:2]
+    if N == 0 or cap == 0:
+        out[3].zero_()
+        return out
+    gt = _eval_match_groundtruth(N, gt_boxes, gt_areas, gt_crowd, gt_labels, gt_starts)
+    call("dvid_coco_eval_match", ptr(dets), ptr(counts), N, cap, *(ptr(t) for t in gt), ptr(thr), ptr(rng), int(num_classes),
+         *(ptr(_cuda(o)) for o in out), stream_ptr())
     return out
 
 
@@ -799,29 +813,12 @@ def lvis_eval_match(dets, counts, gt_boxes, gt_areas, gt_ignore, gt_labels, gt_s
     returned (match, ignore, rank, npig) are coco_eval_match's; gt_ignore [G] uint8 is the annotation's `ignore`; neg_starts [N + 1] int32
     with neg_labels and nex_starts [N + 1] int32 with nex_labels are the images' negative and not-exhaustive label lists as CSR tables
     (lvis_eval.pack_groundtruth).  All tensors on the device.  The scores must be finite."""
-    dets, counts = _cuda(dets, torch.float32), _cuda(counts, torch.int32)
-    N, cap = counts.shape[0], dets.shape[1] if dets.dim() == 3 else -1
-    assert dets.shape == (N, cap, 6), "dets is [images, cap, 6]"
-    dev = dets.device
-    A, T = COCO_EVAL_AREAS, COCO_EVAL_THRESHOLDS
-    thr = torch.tensor([float(t) for t in iou_thrs], dtype=torch.float64)
-    rng = torch.tensor([[float(lo), float(hi)] for lo, hi in area_ranges], dtype=torch.float64).reshape(-1, 2)
-    assert thr.shape == (T,) and rng.shape == (A, 2) and num_classes >= 1, "ten thresholds and four area ranges"
-    if out is None:
-        out = (torch.empty((A, T, N, cap), dtype=torch.int8, device=dev), torch.empty((A, T, N, cap), dtype=torch.int8, device=dev),
-               torch.empty((N, cap), dtype=torch.int32, device=dev), torch.zeros((A, num_classes + 1), dtype=torch.int32, device=dev))
-    match, ignore, rank, npig = out
-    assert match.shape == ignore.shape == (A, T, N, cap) and rank.shape == (N, cap) and npig.shape == (A, num_classes + 1), "output shapes"
-    assert (match.dtype, ignore.dtype, rank.dtype, npig.dtype) == (torch.int8, torch.int8, torch.int32, torch.int32), "output dtypes"
+    dets, counts, thr, rng, out = _eval_match_tables(dets, counts, num_classes, iou_thrs, area_ranges, out)
+    N, cap = dets.shape[:2]
     if N == 0 or cap == 0:
-        npig.zero_()
+        out[3].zero_()
         return out
-    gt_boxes, gt_areas = _cuda(gt_boxes, torch.float64).reshape(-1, 4), _cuda(gt_areas, torch.float64)
-    gt_ignore, gt_labels, gt_starts = _cuda(gt_ignore, torch.uint8), _cuda(gt_labels, torch.int32), _cuda(gt_starts, torch.int32)
-    G = gt_boxes.shape[0]
-    assert gt_starts.shape == (N + 1,) and gt_areas.shape == gt_ignore.shape == gt_labels.shape == (G,), "gt_starts is [images + 1]"
-    starts_host = gt_starts.cpu()
-    assert int(starts_host[-1]) == G, "gt_starts ends at the box count"
+    gt = _eval_match_groundtruth(N, gt_boxes, gt_areas, gt_ignore, gt_labels, gt_starts)
     lists = []
     for name, starts, labels in (("neg", neg_starts, neg_labels), ("nex", nex_starts, nex_labels)):
         starts, labels = _cuda(starts, torch.int32), _cuda(labels, torch.int32).reshape(-1)
@@ -829,8 +826,8 @@ def lvis_eval_match(dets, counts, gt_boxes, gt_areas, gt_ignore, gt_labels, gt_s
         host = starts.cpu()
         assert int(host[-1]) == labels.shape[0], "%s_starts ends at the length of %s_labels" % (name, name)
         lists += [starts, labels, host]
-    call("dvid_lvis_eval_match", ptr(dets), ptr(counts), N, cap, ptr(gt_boxes), ptr(gt_areas), ptr(gt_ignore), ptr(gt_labels), ptr(gt_starts),
-         ptr(starts_host), *(ptr(t) for t in lists), ptr(thr), ptr(rng), int(num_classes), *(ptr(_cuda(o)) for o in out), stream_ptr())
+    call("dvid_lvis_eval_match", ptr(dets), ptr(counts), N, cap, *(ptr(t) for t in gt), *(ptr(t) for t in lists), ptr(thr), ptr(rng),
+         int(num_classes), *(ptr(_cuda(o)) for o in out), stream_ptr())
     return out
 
 

@@ -349,8 +349,8 @@ int dvid_vid_eval_match(const float* dets, const int* counts, int n_frames, int 
                         const int* gt_starts, const int* gt_starts_host, int label_min, int label_max, const double* motion,
                         const double* ranges, const double* empty_w, int n_ranges, float iou_thresh, int num_classes, signed char* match,
                         double* weight, int* rank, double* n_pos, int* top_row, signed char* top_hit, void* stream);
-/* The matching of the COCO bbox evaluator on the device (dvid_version >= 6; csrc/cocoeval.hip; data/evaluation/coco_eval.py:
- * evaluate_numpy's loop), one workgroup per image, the ten IoU thresholds and the four area ranges in one launch.  No model handle,
+/* The matching of the COCO bbox evaluator on the device (dvid_version >= 6; csrc/cocoeval.hip on csrc/evalmatch.h;
+ * data/evaluation/coco_eval.py: evaluate_numpy's loop), one workgroup per image, the ten IoU thresholds and the four area ranges in one launch.  No model handle,
  * independent of DTYPE.
  * in   dets [n_images, cap, 6] fp32 (xyxy box in annotation pixels, score, label as a float), counts [n_images] int32 (device), the
  *      layout of engine.pack_predictions; the ragged ground truth gt_boxes [G, 4] float64 (x, y, w, h), gt_areas [G] float64 (the
@@ -379,8 +379,8 @@ int dvid_coco_eval_match(const float* dets, const int* counts, int n_images, int
                          const unsigned char* gt_crowd, const int* gt_labels, const int* gt_starts, const int* gt_starts_host,
                          const double* iou_thrs, const double* area_ranges, int num_classes, signed char* match, signed char* ignore,
                          int* rank, int* npig, void* stream);
-/* The matching of the LVIS bbox evaluator on the device, the federated protocol (dvid_version >= 8; csrc/lviseval.hip;
- * data/evaluation/lvis_eval.py: match_numpy), one workgroup per image, the ten IoU thresholds and the four area ranges in one launch.  No
+/* The matching of the LVIS bbox evaluator on the device, the federated protocol (dvid_version >= 8; csrc/lviseval.hip on
+ * csrc/evalmatch.h; data/evaluation/lvis_eval.py: match_numpy), one workgroup per image, the ten IoU thresholds and the four area ranges in one launch.  No
  * model handle, independent of DTYPE.
  * in   dets, counts, gt_boxes, gt_areas, gt_labels, gt_starts, gt_starts_host, iou_thrs, area_ranges: as dvid_coco_eval_match; gt_ignore
  *      [G] uint8 (the annotation's `ignore`) where that entry has gt_crowd; the image's negative and not-exhaustive label lists as two CSR
