@@ -507,7 +507,7 @@ def validation_losses(model, loader, output_folder=None):
         total = sums if total is None else total + sums
     if total is None:
         raise ValueError("validation_losses: the loader yielded no batch")
-    weights = model._get_criterion().weight_dict
+    weights = model.objective.weights
     out = OrderedDict((k, v * weights.get(k, 1.0)) for k, v in losses_from_sums(total).items())
     out["total_loss"] = sum(out.values())
     if output_folder:

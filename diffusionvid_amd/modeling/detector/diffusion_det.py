@@ -13,14 +13,19 @@ box-level memory (the top-75 / top-25 object features of the frames in the local
 398-400, :507-512), see _local_memory; every numerical step is a HIP kernel launched through
 `ops` on the current stream.  Random draws go through `self.noise_fn(kind, frame_id, step, image,
 shape)` when set (parity/bench), else torch.randn on the device like the reference.
+
+What is not video lives beside this file and is reached through one-line delegations that keep their contracts here: batches of still
+images (detect_images, detect_images_aug) in stills.py -- `self.stills`, a StillImages --, the training objective (loss_sums,
+compute_losses, loss_gradients) in objective.py -- `self.objective`, an Objective --, several live streams in streams.py (open_streams).
+Those objects hold this module and read its configuration, head and stateless helpers; none of them touches the video state.
 """
+import contextlib
 import functools
 import math
 import os
 import time
 from collections import deque
 
-import numpy as np
 import torch
 from torch import nn
 
@@ -91,6 +96,12 @@ def take(per_frame, a, b, keys=("logits", "boxes", "obj", "k1", "k2"), with_feat
     if with_feats:
         out["feats"] = [torch.cat([src["feats"][l][i0:i1] for src, i0, i1 in runs]) for l in range(len(runs[0][0]["feats"]))]
     return out
+
+
+def _img_wh(size):
+    """The (img_w, img_h) pair of the `ops` wrappers for the frame size that runs through the detector: the floats of a (w, h) pair, or an
+    ops.FrameSizes table -- every frame by its own row -- and None."""
+    return (size, None) if isinstance(size, ops.FrameSizes) else (float(size[0]), float(size[1]))
 
 
 def _result_class(image_list):
@@ -277,6 +288,11 @@ class DiffusionDet(nn.Module):
         self.demo = False
         # images per launch sequence of detect_images; None: INFER_BATCH * LOOKAHEAD_BATCHES, the video path's group (_extract)
         self.still_chunk = None
+        # still batches and the training objective on these weights: plain objects that hold this module (no parameters, no state_dict keys)
+        from .objective import Objective
+        from .stills import StillImages
+        self.stills = StillImages(self)
+        self.objective = Objective(self)
 
     # ---- engine (repacked weights on the GPU) -------------------------------------------------
     def _get_engine(self):
@@ -359,14 +375,16 @@ class DiffusionDet(nn.Module):
         images["ref_g"] = [to_image_list(image) for image in images["ref_g"]]
         infos = dict(images)
         infos.pop("cur")
-        if self.device.type == "cuda" and self.device.index is not None:
-            # the library allocates and launches on the current device: scoped to this call, the caller's current device
-            # is restored on return
-            with torch.cuda.device(self.device):
-                return self._forward_test(images["cur"], infos, targets)
-        return self._forward_test(images["cur"], infos, targets)
+        with self._on_device():
+            return self._forward_test(images["cur"], infos, targets)
 
-    # ---- still images ---------------------------------------------------------------------------------------------------
+    def _on_device(self):
+        """The library allocates and launches on the current device: `with self._on_device():` makes that this model's for the block and
+        restores the caller's on the way out; nothing to do for a device without an index (the current one, or the host)."""
+        scoped = self.device.type == "cuda" and self.device.index is not None
+        return torch.cuda.device(self.device) if scoped else contextlib.nullcontext()
+
+    # ---- still images (detector/stills.py) ------------------------------------------------------------------------------------------------
     def detect_images(self, images, image_ids=None):
         """Detections of a batch of still images, each with its own size -> one BoxList per image, carrying the image's own (w, h).
 
@@ -379,256 +397,7 @@ class DiffusionDet(nn.Module):
         Draws are keyed by image -- noise_fn(kind, image_id, step, 0, (M, 4)), image_ids defaulting to 0 .. n-1 -- and every stage is
         per-image independent, so an image's detections depend neither on what shares its batch nor on the chunking (launch sequences
         of `still_chunk` images).  Reads and writes no video state; never replayed from a hipGraph."""
-        if self.training:
-            raise NotImplementedError("training is out of scope of the MI355X inference path")
-        vid = self.cfg.MODEL.VID
-        if vid.MEGA.GLOBAL.ENABLE:
-            raise NotImplementedError("detect_images: MODEL.VID.MEGA.GLOBAL.ENABLE is True, and a still image has no global memory to condition on")
-        if vid.ROI_BOX_HEAD.ATTENTION.ENABLE:
-            raise NotImplementedError("detect_images: MODEL.VID.ROI_BOX_HEAD.ATTENTION.ENABLE is True, and a still image has no local memory to condition on")
-        if self.num_heads_local > 0:
-            raise NotImplementedError("detect_images: MODEL.DiffusionDet.NUM_HEADS_LOCAL is %d: the conditioned heads have nothing to be conditioned on "
-                                      "(still images need NUM_HEADS_LOCAL 0)" % self.num_heads_local)
-        result_cls = self.boxlist_cls or _result_class(images)
-        if isinstance(images, torch.Tensor):
-            images = list(images) if images.dim() == 4 else [images]
-        imgs = to_image_list(images, self.size_divisibility)
-        n, ch, H, W = imgs.tensors.shape
-        if ch != 3 or H % self.size_divisibility or W % self.size_divisibility:
-            raise ValueError("detect_images: the canvas must be [n, 3, H, W] with H and W multiples of %d, got %s"
-                             % (self.size_divisibility, tuple(imgs.tensors.shape)))
-        sizes_wh = [(int(s[1]), int(s[0])) for s in imgs.image_sizes]
-        if len(sizes_wh) != n or any(not (0 < w <= W and 0 < h <= H) for w, h in sizes_wh):
-            raise ValueError("detect_images: image_sizes must hold one (h, w) inside the %d x %d canvas per image, got %s" % (H, W, list(imgs.image_sizes)))
-        ids = list(range(n)) if image_ids is None else [int(i) for i in image_ids]
-        if len(ids) != n:
-            raise ValueError("detect_images: %d image_ids for %d images" % (len(ids), n))
-        if n == 0:
-            return []
-        if self.device.type == "cuda" and self.device.index is not None:
-            with torch.cuda.device(self.device):
-                return self._detect_images(imgs.tensors, sizes_wh, ids, result_cls)
-        return self._detect_images(imgs.tensors, sizes_wh, ids, result_cls)
-
-    def _still_draws(self, kind, ids, step, views=(0,)):
-        """[n * len(views), M, 4]: the draw of every image of the batch, keyed by its id and -- in the key's `image` slot -- its view (0 for
-        a plain still image), image-major; an injected noise_fn draws on the host and ONE tensor is uploaded"""
-        shape = (self.num_proposals, 4)
-        if getattr(self.noise_fn, "on_device", False):          # per view one launch for consecutive ids: keys a fixed stride apart
-            per_view = [self.noise_fn.draw_ids(kind, ids, step, shape, self.device, image=v) for v in views]
-            return per_view[0] if len(views) == 1 else torch.stack(per_view, dim=1).reshape((-1,) + shape)
-        if self.noise_fn is not None:
-            return torch.stack([self.noise_fn(kind, i, step, v, shape) for i in ids for v in views]).to(self.device, torch.float32)
-        return torch.randn((len(ids) * len(views),) + shape, device=self.device)
-
-    def _still_uploads(self, sizes_wh, ids, views=(0,)):
-        """the size table and every draw of one launch sequence of still images (slots: image-major, then `views`), on the device"""
-        up = {"sizes": ops.FrameSizes(torch.tensor(sizes_wh, dtype=torch.float32), self.device), "ids": ids}
-        if self.sampling_timesteps == 1:
-            up["box_init"] = self._still_draws("box_init", ids, 0, views)
-        else:
-            up["draws"] = {"img": self._still_draws("img", ids, 0, views)}
-            for step, (_, time_next) in enumerate(self._time_pairs()):
-                if time_next >= 0:
-                    up["draws"][step] = (self._still_draws("ddim", ids, step, views), self._still_draws("renew", ids, step, views))
-        return up
-
-    def _detect_images(self, canvas, sizes_wh, ids, result_cls):
-        # every upload of the call -- the size table, the frames of a host-side loader, the draws -- BEFORE any kernel is queued (the rule
-        # of _extract: a host->device copy from pageable memory blocks the host until the stream has drained)
-        up = self._still_uploads(sizes_wh, ids)
-        canvas = canvas.to(self.device, torch.float32).contiguous()
-        cap = max(1, int(self.still_chunk or self.infer_batch * self.lookahead))
-        outs = self._still_launches(canvas, up)
-        results = []          # the host reads the counts only behind the last chunk's launches
-        for k, out in enumerate(outs):
-            results += self._to_boxlists(*out, sizes_wh[k * cap:(k + 1) * cap], result_cls=result_cls)
-        return results
-
-    def _still_launches(self, canvas, up):
-        """the launch sequences of one canvas of still images: -> per chunk of `still_chunk` slots the detection buffers (boxes, scores,
-        labels, counts) of postproc_topk_nms.  Queues kernels only."""
-        eng = self._get_engine()
-        n, M = canvas.shape[0], self.num_proposals
-        H, W = canvas.shape[-2:]
-        pairs = self._time_pairs()
-        sizes, ids, box_init, draws = up["sizes"], up["ids"], up.get("box_init"), up.get("draws")
-        cap = max(1, int(self.still_chunk or self.infer_batch * self.lookahead))
-        eng.reserve(min(cap, n), H, W, M)
-        outs = []
-        for a in range(0, n, cap):
-            b = min(n, a + cap)
-            feats = eng.backbone_frames([canvas[i:i + 1] for i in range(a, b)])
-            fs = sizes[a:b]
-            if self.sampling_timesteps == 1:
-                t = torch.full((b - a,), pairs[0][0], dtype=torch.long)
-                logits, boxes = self.head.plain_heads(feats, ops.noise_to_boxes(box_init[a:b], self.scale, fs), t)
-                if self.debug_taps is not None:
-                    self.debug_taps.setdefault("still_final_0", []).append((logits, boxes))
-                outs.append(ops.postproc_topk_nms(logits, boxes, fs, None, 0.5, self.use_nms))
-            else:
-                chunk = {k: (v[a:b] if k == "img" else (v[0][a:b], v[1][a:b])) for k, v in draws.items()}
-                outs.append(self._ddim_ensemble(feats, fs, b - a, ids[0], pairs, fs, None, chunk, skip_last=True))          # (the id is not read: the draws are made)
-        return outs
-
-    # ---- still images with TEST.BBOX_AUG -------------------------------------------------------------------------------------------------
-    # ---- the forward of the training objective (diffusion_det.py:338-375, still batches) -------------------------------------------------
-    def _get_criterion(self):
-        """SetCriterionDynamicK over HungarianMatcherDynamicK with the weights of diffusion_det.py:275-299, built on first use: a config the
-        criterion refuses (USE_FED_LOSS) still detects"""
-        if getattr(self, "_criterion", None) is None:
-            from ..roi_heads.box_head.loss import HungarianMatcherDynamicK, SetCriterionDynamicK
-            d = self.cfg.MODEL.DiffusionDet
-            matcher = HungarianMatcherDynamicK(cfg=self.cfg, cost_class=d.CLASS_WEIGHT, cost_bbox=d.L1_WEIGHT, cost_giou=d.GIOU_WEIGHT, use_focal=self.use_focal)
-            weights = {"loss_ce": d.CLASS_WEIGHT, "loss_bbox": d.L1_WEIGHT, "loss_giou": d.GIOU_WEIGHT}
-            if d.DEEP_SUPERVISION:
-                for i in range(self.num_heads + self.num_heads_local - 1):
-                    weights.update({k + "_%d" % i: v for k, v in list(weights.items())[:3]})
-            object.__setattr__(self, "_criterion", SetCriterionDynamicK(cfg=self.cfg, num_classes=self.num_classes, matcher=matcher, weight_dict=weights,
-                                                                        eos_coef=d.NO_OBJECT_WEIGHT, losses=["labels", "boxes"], use_focal=self.use_focal))
-        return self._criterion
-
-    def _train_step(self, image_id):
-        """The diffusion step of an image's loss, a uniform integer in [0, num_timesteps): the reference draws torch.randint per image
-        (diffusion_det.py:695).  With a noise_fn it is derived from the image's key on the host: z = the one N(0, 1) draw of kind
-        "train_t" keyed (image_id, step 0, image 0), u = Phi(z) = (1 + erf(z / sqrt 2)) / 2 in float64, t = min(floor(u * num_timesteps),
-        num_timesteps - 1) -- a pure function of the id, uniform because Phi(z) is.  Without a noise_fn: torch.randint."""
-        if self.noise_fn is None:
-            return int(torch.randint(0, self.num_timesteps, (1,)))
-        z = float(self.noise_fn("train_t", int(image_id), 0, 0, (1,)).reshape(-1)[0])
-        u = 0.5 * (1.0 + math.erf(z / math.sqrt(2.0)))
-        return min(int(u * self.num_timesteps), self.num_timesteps - 1)
-
-    def loss_sums(self, images, targets, image_ids=None):
-        """What compute_losses forms its dict from: (sums [S, n, 4] float64 on the host -- per head output (the final one last) and image the
-        focal sum, the L1 sum, the 1 - GIoU sum and the matched count -- and the device tuple (assign, matched_query, sums, status) of
-        ops.set_criterion).  engine.inference.validation_losses adds the sums of a data set's batches."""
-        out = self._loss_forward(images, targets, image_ids, False)[0]
-        return out[2].detach().to("cpu", torch.float64), out
-
-    def _loss_forward(self, images, targets, image_ids, gradients):
-        """The forward loss_sums and loss_gradients share -> (the device tuple of ops.set_criterion, None or (d_logits, d_boxes) of the sum of
-        the weighted losses with respect to the kept head outputs, from ops.set_criterion_backward on the same stream)."""
-        if self.training:
-            raise NotImplementedError("training is out of scope of the MI355X inference path")
-        if isinstance(images, dict):
-            raise NotImplementedError("compute_losses: the video item dict (cur / ref_l / ref_g) of the training protocol is not built; "
-                                      "hand over a batch of still images")
-        vid = self.cfg.MODEL.VID
-        if vid.ROI_BOX_HEAD.ATTENTION.ENABLE:
-            raise NotImplementedError("compute_losses: MODEL.VID.ROI_BOX_HEAD.ATTENTION.ENABLE True is not built (local-attention training batches)")
-        if vid.MEGA.GLOBAL.ENABLE or self.num_heads_local > 0:
-            raise NotImplementedError("compute_losses: still batches need MODEL.VID.MEGA.GLOBAL.ENABLE False and NUM_HEADS_LOCAL 0 (got %s, %d): the "
-                                      "conditioned heads have nothing to be conditioned on" % (vid.MEGA.GLOBAL.ENABLE, self.num_heads_local))
-        criterion = self._get_criterion()          # refuses USE_FED_LOSS by key
-        if isinstance(images, torch.Tensor):
-            images = list(images) if images.dim() == 4 else [images]
-        imgs = to_image_list(images, self.size_divisibility)
-        n, ch, H, W = imgs.tensors.shape
-        if ch != 3 or H % self.size_divisibility or W % self.size_divisibility:
-            raise ValueError("compute_losses: the canvas must be [n, 3, H, W] with H and W multiples of %d, got %s"
-                             % (self.size_divisibility, tuple(imgs.tensors.shape)))
-        sizes_wh = [(int(s[1]), int(s[0])) for s in imgs.image_sizes]
-        if len(sizes_wh) != n or any(not (0 < w <= W and 0 < h <= H) for w, h in sizes_wh):
-            raise ValueError("compute_losses: image_sizes must hold one (h, w) inside the %d x %d canvas per image, got %s" % (H, W, list(imgs.image_sizes)))
-        ids = list(range(n)) if image_ids is None else [int(i) for i in image_ids]
-        if len(ids) != n or len(targets) != n:
-            raise ValueError("compute_losses: %d image_ids and %d targets for %d images" % (len(ids), len(targets), n))
-        if n == 0:
-            raise ValueError("compute_losses: an empty batch has no loss")
-        M = self.num_proposals
-        # the ground truth, ragged, on the host: absolute xyxy in the image's own size, labels 1-based; normalised (cx, cy, w, h) for q_sample
-        gt_abs, gt_norm, labels, starts = [], [], [], [0]
-        for i, (t, (w, h)) in enumerate(zip(targets, sizes_wh)):
-            if tuple(int(v) for v in t.size) != (w, h):
-                raise ValueError("compute_losses: target %d is for a %s image, the image is %s" % (i, tuple(t.size), (w, h)))
-            if not t.has_field("labels"):
-                raise ValueError("compute_losses: target %d carries no `labels` field" % i)
-            b = t.convert("xyxy").bbox.detach().to("cpu", torch.float32).reshape(-1, 4)
-            if b.shape[0] > M:
-                raise NotImplementedError("compute_losses: image %d holds %d ground-truth boxes, MODEL.DiffusionDet.NUM_PROPOSALS is %d (the reference's "
-                                          "random subset is not built)" % (i, b.shape[0], M))
-            nb = b / torch.tensor([w, h, w, h], dtype=torch.float32)
-            gt_abs.append(b), labels.append(t.get_field("labels").detach().to("cpu", torch.int32).reshape(-1))
-            gt_norm.append(torch.stack(((nb[:, 0] + nb[:, 2]) / 2, (nb[:, 1] + nb[:, 3]) / 2, nb[:, 2] - nb[:, 0], nb[:, 3] - nb[:, 1]), dim=1))
-            starts.append(starts[-1] + b.shape[0])
-        from ..roi_heads.box_head.loss import LOSS_KEYS, check_limits, coef_from_counts, raise_on_status
-        check_limits(M, self.num_classes, criterion.matcher.ota_k, [starts[i + 1] - starts[i] for i in range(n)])
-        gt_abs, gt_norm, labels = torch.cat(gt_abs), torch.cat(gt_norm), torch.cat(labels)
-        starts = torch.tensor(starts, dtype=torch.int32)
-        steps = torch.tensor([self._train_step(i) for i in ids], dtype=torch.int64)
-
-        def run():
-            eng = self._get_engine()
-            dev = self.device
-            # every upload and draw before any kernel is queued (the rule of _detect_images)
-            sizes = ops.FrameSizes(torch.tensor(sizes_wh, dtype=torch.float32), dev)
-            noise, placeholder = self._still_draws("train_noise", ids, 0), self._still_draws("train_placeholder", ids, 0)
-            up = [t.to(dev) for t in (gt_abs, gt_norm, labels)]
-            if gradients:          # the weights of the kept head outputs, the final one last
-                sfx = ["_%d" % s for s in range(self.num_heads - 1)] + [""] if self.cfg.MODEL.DiffusionDet.DEEP_SUPERVISION else [""]
-                weights = torch.tensor([[float(criterion.weight_dict.get(k + x, 1.0)) for k in LOSS_KEYS] for x in sfx], dtype=torch.float64).to(dev)
-            canvas = imgs.tensors.to(dev, torch.float32).contiguous()
-            x_boxes = ops.q_sample_boxes(up[1], starts, steps, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, noise, placeholder,
-                                         self.scale, sizes)
-            cap = max(1, int(self.still_chunk or self.infer_batch * self.lookahead))
-            eng.reserve(min(cap, n), H, W, M)
-            logits, boxes = [], []
-            for a in range(0, n, cap):
-                b = min(n, a + cap)
-                feats = eng.backbone_frames([canvas[i:i + 1] for i in range(a, b)])
-                lg, bx = self.head.plain_heads(feats, x_boxes[a:b].contiguous(), steps[a:b], intermediate=True)
-                if not self.cfg.MODEL.DiffusionDet.DEEP_SUPERVISION:
-                    lg, bx = lg[-1:], bx[-1:]
-                logits.append(lg), boxes.append(bx)
-            logits, boxes = torch.cat(logits, dim=1), torch.cat(boxes, dim=1)
-            if self.debug_taps is not None:
-                self.debug_taps.setdefault("train_heads", []).append((logits, boxes, x_boxes, steps))
-            out = criterion.sums(logits, boxes, (up[0], up[2], starts, sizes))
-            if not gradients:
-                return out, None
-            # d(sum of the weighted losses): weight / denominator per head output, the denominators from the matched counts on the device
-            assert logits.shape[0] == weights.shape[0], "one row of weights per kept head output"
-            p = criterion.matcher.params()
-            coef = coef_from_counts(weights, out[2][:, :, 3].sum(1))
-            return out, ops.set_criterion_backward(logits, boxes, up[0], up[2], starts, sizes, p["alpha"], p["gamma"], out[0], out[3], coef)
-
-        with torch.no_grad():
-            if self.device.type == "cuda" and self.device.index is not None:
-                with torch.cuda.device(self.device):
-                    return run()
-            return run()
-
-    def compute_losses(self, images, targets, image_ids=None):
-        """The weighted training losses of a labelled batch of still images: what the reference's `_forward_train` returns
-        (diffusion_det.py:338-375), forward only.  images, image_ids: what detect_images takes; targets: one BoxList per image in the
-        image's own (w, h), mode xyxy or xywh, with a `labels` field (1-based).  Per image: t (see _train_step) and the draws
-        noise_fn("train_noise" / "train_placeholder", image_id, 0, 0, (M, 4)); ops.q_sample_boxes diffuses the ground truth to step t; the
-        NUM_HEADS heads run on the noisy boxes with every output kept when DEEP_SUPERVISION; ops.set_criterion matches and sums all of
-        them in one call.  -> {loss_ce, loss_bbox, loss_giou, and `_0 .. _{NUM_HEADS-2}`} as Python floats times CLASS_WEIGHT / L1_WEIGHT /
-        GIOU_WEIGHT.  Every draw is keyed by the image id and every stage is per-image independent, so the sums of an image depend
-        neither on its batch nor on the chunking.  The model stays in eval mode; nothing is cached, no video state is read or written,
-        nothing is replayed from a hipGraph.  The video item dict is refused by name (not built)."""
-        from ..roi_heads.box_head.loss import losses_from_sums
-        sums, _ = self.loss_sums(images, targets, image_ids)
-        weights = self._get_criterion().weight_dict
-        return {k: v * weights.get(k, 1.0) for k, v in losses_from_sums(sums).items()}
-
-    def loss_gradients(self, images, targets, image_ids=None):
-        """compute_losses and the first link of its backward pass: -> (losses, d_logits [S, n, M, C], d_boxes [S, n, M, 4]).  Inputs and
-        refusals are compute_losses'; `losses` is compute_losses' dict; the two fp32 tensors, which stay on the device, are the gradient of
-        the SUM of the weighted losses with respect to every kept head output (logits and absolute xyxy boxes as
-        debug_taps["train_heads"] records them), the final head output last; S is 1 without DEEP_SUPERVISION.  One
-        ops.set_criterion_backward launch behind the forward's ops.set_criterion, on the same tensors.
-
-        The gradient stops at the head outputs: the HIP head, the FPN and the backbone have no backward.  A coefficient divides by the
-        BATCH's matched count of its head output (the reference's denominators), so an image's gradient depends on the batch it is in; its
-        loss sums do not."""
-        from ..roi_heads.box_head.loss import losses_from_sums
-        out, grads = self._loss_forward(images, targets, image_ids, True)
-        weights = self._get_criterion().weight_dict
-        losses = {k: v * weights.get(k, 1.0) for k, v in losses_from_sums(out[2].detach().to("cpu", torch.float64)).items()}
-        return losses, grads[0], grads[1]
+        return self.stills.detect(images, image_ids)
 
     def detect_images_aug(self, images, image_ids=None):
         """TEST.BBOX_AUG (mega_core/engine/bbox_aug.py: im_detect_bbox_aug): every image detected in flipped and rescaled views, the views'
@@ -644,79 +413,38 @@ class DiffusionDet(nn.Module):
         View v of image id i draws noise_fn(kind, i, step, v, (M, 4)): view 0 draws what detect_images draws.  filter_results' score threshold
         is not applied (the detector's own post-processing has run), nothing is re-scored or box-voted.  Reads and writes no video state;
         never replayed from a hipGraph."""
-        if self.training:
-            raise NotImplementedError("training is out of scope of the MI355X inference path")
-        vid = self.cfg.MODEL.VID
-        if vid.MEGA.GLOBAL.ENABLE:
-            raise NotImplementedError("detect_images_aug: MODEL.VID.MEGA.GLOBAL.ENABLE is True, and a still image has no global memory to condition on")
-        if vid.ROI_BOX_HEAD.ATTENTION.ENABLE:
-            raise NotImplementedError("detect_images_aug: MODEL.VID.ROI_BOX_HEAD.ATTENTION.ENABLE is True, and a still image has no local memory to condition on")
-        if self.num_heads_local > 0:
-            raise NotImplementedError("detect_images_aug: MODEL.DiffusionDet.NUM_HEADS_LOCAL is %d: the conditioned heads have nothing to be conditioned on "
-                                      "(still images need NUM_HEADS_LOCAL 0)" % self.num_heads_local)
-        if not self.cfg.TEST.BBOX_AUG.ENABLED:
-            raise NotImplementedError("detect_images_aug: TEST.BBOX_AUG.ENABLED is False (detect_images is the plain path)")
-        images = list(images)
-        ids = list(range(len(images))) if image_ids is None else [int(i) for i in image_ids]
-        if len(ids) != len(images):
-            raise ValueError("detect_images_aug: %d image_ids for %d images" % (len(ids), len(images)))
-        if not images:
-            return []
-        if self.device.type == "cuda" and self.device.index is not None:
-            with torch.cuda.device(self.device):
-                return self._detect_images_aug(images, ids)
-        return self._detect_images_aug(images, ids)
+        return self.stills.detect_aug(images, image_ids)
 
-    def _detect_images_aug(self, images, ids):
-        from ...data import transforms as T
-        result_cls = self.boxlist_cls or BoxList
-        n, div = len(images), self.size_divisibility
-        # every upload of the call first (the rule of _detect_images): the images, their pointer table, per scale group the resample plan,
-        # the size table and the draws, then the merge's table and view 0's sizes
-        dev_images = []
-        for im in images:
-            if not isinstance(im, (torch.Tensor, np.ndarray)):
-                im = np.array(im.convert("RGB"))          # a PIL image (a writable copy)
-            if im.dtype not in (torch.uint8, np.uint8) or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError("detect_images_aug takes uint8 [h, w, 3] images, got %s %s" % (im.dtype, tuple(im.shape)))
-            if isinstance(im, np.ndarray):
-                im = torch.from_numpy(np.ascontiguousarray(im))
-            dev_images.append(im.to(self.device).contiguous())
-        srcs = ops.ImageTable(dev_images)
-        views = [T.bbox_aug_views(self.cfg, (w, h)) for h, w in srcs.sizes_hw]
-        V = len(views[0])
-        if not hasattr(self, "_aug_tables"):
-            self._aug_tables = {}          # resample tables by (in, out) size: a dataset repeats its sizes
-        groups, v0 = [], 0
-        for g, (_, _, nv) in enumerate(T.bbox_aug_scales(self.cfg)):
-            out_hw = [(vs[v0].h, vs[v0].w) for vs in views]
-            plan = T.ViewsPlan(srcs.sizes_hw, out_hw, cache=self._aug_tables).to(self.device)
-            PH, PW = -(-plan.max_oh // div) * div, -(-plan.max_ow // div) * div
-            sizes_wh = [(ow, oh) for oh, ow in out_hw for _ in range(nv)]
-            groups.append((plan, PH, PW, nv, self._still_uploads(sizes_wh, ids, tuple(range(v0, v0 + nv)))))
-            v0 += nv
-        if len(self._aug_tables) > 4096:
-            self._aug_tables.clear()
-        table = ops.bbox_aug_table(views).to(self.device)
-        sizes0_wh = [(vs[0].w, vs[0].h) for vs in views]
-        sizes0 = ops.FrameSizes(torch.tensor(sizes0_wh, dtype=torch.float32), self.device)
-        # launches only from here on
-        per_group = []
-        for plan, PH, PW, nv, up in groups:
-            canvas = ops.resize_views_u8(srcs, plan, PH, PW, nv == 2)
-            outs = self._still_launches(canvas, up)
-            ob, osc, ol, oc = (outs[0] if len(outs) == 1 else [torch.cat([o[k] for o in outs]) for k in range(4)])
-            cap = osc.shape[1]
-            per_group.append((ob.reshape(n, nv, cap, 4), osc.reshape(n, nv, cap), ol.reshape(n, nv, cap), oc.reshape(n, nv)))
-        if len(per_group) == 1:
-            ob, osc, ol, oc = per_group[0]
-        else:
-            ob, osc, ol, oc = (torch.cat([g[k] for g in per_group], dim=1) for k in range(4))
-        cap = osc.shape[2]
-        cand = ops.bbox_aug_merge(ob.reshape(n * V, cap, 4), osc.reshape(n * V, cap), ol.reshape(n * V, cap), oc.reshape(n * V), table, V)
-        heads = self.cfg.MODEL.ROI_HEADS
-        out = ops.bbox_aug_finish(*cand, sizes0, float(heads.NMS), int(heads.DETECTIONS_PER_IMG))
-        return self._to_boxlists(*out, sizes0_wh, result_cls=result_cls)
+    # ---- the training objective (detector/objective.py) -----------------------------------------------------------------------------------
+    def loss_sums(self, images, targets, image_ids=None):
+        """What compute_losses forms its dict from: (sums [S, n, 4] float64 on the host -- per head output (the final one last) and image the
+        focal sum, the L1 sum, the 1 - GIoU sum and the matched count -- and the device tuple (assign, matched_query, sums, status) of
+        ops.set_criterion).  engine.inference.validation_losses adds the sums of a data set's batches."""
+        return self.objective.sums(images, targets, image_ids)
+
+    def compute_losses(self, images, targets, image_ids=None):
+        """The weighted training losses of a labelled batch of still images: what the reference's `_forward_train` returns
+        (diffusion_det.py:338-375), forward only.  images, image_ids: what detect_images takes; targets: one BoxList per image in the
+        image's own (w, h), mode xyxy or xywh, with a `labels` field (1-based).  Per image: t (see Objective.train_step) and the draws
+        noise_fn("train_noise" / "train_placeholder", image_id, 0, 0, (M, 4)); ops.q_sample_boxes diffuses the ground truth to step t; the
+        NUM_HEADS heads run on the noisy boxes with every output kept when DEEP_SUPERVISION; ops.set_criterion matches and sums all of
+        them in one call.  -> {loss_ce, loss_bbox, loss_giou, and `_0 .. _{NUM_HEADS-2}`} as Python floats times CLASS_WEIGHT / L1_WEIGHT /
+        GIOU_WEIGHT.  Every draw is keyed by the image id and every stage is per-image independent, so the sums of an image depend
+        neither on its batch nor on the chunking.  The model stays in eval mode; nothing is cached, no video state is read or written,
+        nothing is replayed from a hipGraph.  The video item dict is refused by name (not built)."""
+        return self.objective.losses(images, targets, image_ids)
+
+    def loss_gradients(self, images, targets, image_ids=None):
+        """compute_losses and the first link of its backward pass: -> (losses, d_logits [S, n, M, C], d_boxes [S, n, M, 4]).  Inputs and
+        refusals are compute_losses'; `losses` is compute_losses' dict; the two fp32 tensors, which stay on the device, are the gradient of
+        the SUM of the weighted losses with respect to every kept head output (logits and absolute xyxy boxes as
+        debug_taps["train_heads"] records them), the final head output last; S is 1 without DEEP_SUPERVISION.  One
+        ops.set_criterion_backward launch behind the forward's ops.set_criterion, on the same tensors.
+
+        The gradient stops at the head outputs: the HIP head, the FPN and the backbone have no backward.  A coefficient divides by the
+        BATCH's matched count of its head output (the reference's denominators), so an image's gradient depends on the batch it is in; its
+        loss sums do not."""
+        return self.objective.gradients(images, targets, image_ids)
 
     def _reset_video(self):
         self._ahead = {}
@@ -777,13 +505,10 @@ class DiffusionDet(nn.Module):
         from .streams import StreamSet
         return StreamSet(self, frames_per_launch)
 
-    def model_predictions(self, backbone_feats, images_whwh, x, t, box_extract=0):
-        """diffusion_det.py:655-677.  images_whwh: (w, h) of the un-padded frame (same for all frames)."""
-        if isinstance(images_whwh, ops.FrameSizes):          # still images: frame f by its own row
-            x_boxes = ops.noise_to_boxes(x, self.scale, images_whwh)
-        else:
-            w, h = images_whwh
-            x_boxes = ops.noise_to_boxes(x, self.scale, w, h)
+    def model_predictions(self, backbone_feats, size, x, t, box_extract=0):
+        """diffusion_det.py:655-677.  size: (w, h) of the un-padded frame (same for all frames), or an ops.FrameSizes (still images: frame f
+        by its own row)."""
+        x_boxes = ops.noise_to_boxes(x, self.scale, *_img_wh(size))
         if box_extract:
             return self.head(backbone_feats, x_boxes, t, None, box_extract)
         outputs_class, outputs_coord = self.head(backbone_feats, x_boxes, t, None)
@@ -805,7 +530,7 @@ class DiffusionDet(nn.Module):
         self.local_img_queue = []
         ref_g = infos["ref_g"]
         h, w = imgs.image_sizes[0]
-        whwh = (float(w), float(h))
+        size = (int(w), int(h))
         batch = min(self.infer_batch, end_id - frame_id + 1)
         pairs = self._time_pairs()
         ahead = infos.get("ref_ahead") or {}
@@ -817,11 +542,11 @@ class DiffusionDet(nn.Module):
 
         # 0. the steady-state call of the reference's protocol as ONE hipGraph launch (see _graphed_call)
         if self._call_graph_applies(infos, ref_l, ref_g, ahead, batch, frame_id):
-            out = self._graphed_call(frame_id, ref_l, whwh, w, h, pairs, batch, ddim_draws.get(frame_id))
+            out = self._graphed_call(frame_id, ref_l, size, pairs, batch, ddim_draws.get(frame_id))
             if out is not None:
                 return out
         elif self._stream_graph_applies(infos, ref_l, ref_g, ahead, batch, frame_id):
-            out = self._graphed_call(frame_id, ref_l, whwh, w, h, pairs, batch, ddim_draws.get(frame_id), ref_g=ref_g)
+            out = self._graphed_call(frame_id, ref_l, size, pairs, batch, ddim_draws.get(frame_id), ref_g=ref_g)
             if out is not None:
                 return out
 
@@ -834,7 +559,7 @@ class DiffusionDet(nn.Module):
             raise NotImplementedError("more local frames than INFER_BATCH in one call")
         gsplit = None
         if ref_l_run or ref_g or ahead_keys:
-            fresh_local, gsplit, fresh_ahead = self._extract(frame_id, ref_l_run, ref_g, {fb: ahead[fb] for fb in ahead_keys}, whwh,
+            fresh_local, gsplit, fresh_ahead = self._extract(frame_id, ref_l_run, ref_g, {fb: ahead[fb] for fb in ahead_keys}, size,
                                                              on_global=self._build_memory_aside if ref_g else None)
             if fresh_local is not None:
                 local_split = fresh_local
@@ -894,7 +619,7 @@ class DiffusionDet(nn.Module):
                     sp_run = src if run["src"] is not None else run["split"]
                     a, b = (i0, i1) if run["src"] is not None else (0, sp_run["k1"].shape[0])
                     self._set_local_memory([sp_run[k][a:b].reshape(-1, self.hidden_dim) for k in ("k1", "k2")], groups=len(run["items"]))
-                per_slot = self._final_stage(feats_run, cached, whwh, w, h, pairs, run["items"], ddim_draws)
+                per_slot = self._final_stage(feats_run, cached, size, pairs, run["items"], ddim_draws)
                 for k, (fb, nb) in enumerate(run["items"]):
                     out = per_slot[k * self.infer_batch: k * self.infer_batch + nb]
                     if fb == frame_id:
@@ -908,7 +633,7 @@ class DiffusionDet(nn.Module):
         # current batch only (diffusion_det.py:515-523)
         entries = [self.queue[i] for i in range(self.key_frame_location, self.key_frame_location + batch)]
         feats_cur, cached = self._gather_entries(entries)
-        return self._final_stage(feats_cur, cached, whwh, w, h, pairs, [(frame_id, batch)], ddim_draws, slots=batch)
+        return self._final_stage(feats_cur, cached, size, pairs, [(frame_id, batch)], ddim_draws, slots=batch)
 
     @staticmethod
     def _fire_on_global(on_global, take, len_l, n_own, done, total):
@@ -1003,7 +728,7 @@ class DiffusionDet(nn.Module):
         return all(f.tensors.is_cuda and f.tensors.device == self.device and f.tensors.dtype == torch.float32
                    and f.tensors.shape == f0.shape and f.tensors.shape[0] == 1 for f in list(ref_l) + list(ref_g))
 
-    def _graphed_call(self, frame_id, ref_l, whwh, w, h, pairs, batch, draws, ref_g=None):
+    def _graphed_call(self, frame_id, ref_l, size, pairs, batch, draws, ref_g=None):
         """One batch of the reference's call protocol (mega_core/engine/inference.py:22-94: 8 frames per working call) is ~180
         kernel launches of 10-90 us -- backbone, 3 + 1 heads, attention, post-processing -- that differ from call to call only in
         their INPUT VALUES: the frames and the random draws.  The first steady call of a shape runs kernel by kernel (tuner,
@@ -1024,7 +749,7 @@ class DiffusionDet(nn.Module):
         # ... and it bakes in every switch the eager path reads per call
         gframes = [im.tensors for im in ref_g] if ref_g else []
         key = (tuple(frames[0].shape), len(frames), self.sampling_timesteps, int(mem[0].shape[0]), int(mem[1].shape[0]) if mem[1] is not None else 0,
-               id(eng), (float(w), float(h)), bool(self.skip_unobservable), bool(self.use_nms), eng.chains, eng.precision, len(gframes),
+               id(eng), _img_wh(size), bool(self.skip_unobservable), bool(self.use_nms), eng.chains, eng.precision, len(gframes),
                bool(self.local_box_enable), int(self.head.local_stage))
         M = self.num_proposals
         g = self._graphs.get(key)
@@ -1032,7 +757,7 @@ class DiffusionDet(nn.Module):
             self._graph_seen[key] = self._graph_seen.get(key, 0) + 1
             if self._graph_seen[key] < 2:
                 return None                      # the first steady call of this shape: eager (it also warms everything a capture may not do)
-            g = self._capture_call(key, frames, whwh, w, h, pairs, batch, draws, gframes)
+            g = self._capture_call(key, frames, size, pairs, batch, draws, gframes)
             if g is None:
                 return None
         # this call's inputs into the graph's static buffers (device-to-device, on the launch stream), then ONE launch
@@ -1076,9 +801,9 @@ class DiffusionDet(nn.Module):
             # the BoxLists would be views of the graph's static output buffer, which the next replay overwrites: hand out copies
             # (results_on_host copies the buffer to the host anyway)
             out = tuple(t.clone() for t in out)
-        return self._to_boxlists(*out, (int(w), int(h)))
+        return self._to_boxlists(*out, size)
 
-    def _capture_call(self, key, frames, whwh, w, h, pairs, batch, draws, gframes=()):
+    def _capture_call(self, key, frames, size, pairs, batch, draws, gframes=()):
         M = self.num_proposals
         static = {"frames": [torch.empty_like(f) for f in frames], "box_init": torch.empty((batch, M, 4), device=self.device),
                   "draws": None}
@@ -1100,16 +825,16 @@ class DiffusionDet(nn.Module):
                 # [frame | new global frame] through backbone + extraction, then both memory updates on the STATIC memory buffers: the
                 # pruned memories are written back into them, so that the next replay starts from this one's result
                 self.head.proposal_feats_global = list(static["mem"])
-                local, gsplit, _ = self._extract(0, static_l, static_g, {}, whwh, box_init=[static["box_init"], static["box_init_g"]])
+                local, gsplit, _ = self._extract(0, static_l, static_g, {}, size, box_init=[static["box_init"], static["box_init_g"]])
                 self._build_memory(gsplit)
                 for i in range(2):
                     static["mem"][i].copy_(self.head.proposal_feats_global[i])
                 self._set_global_memory(static["mem"])
             else:
-                local, _, _ = self._extract(0, static_l, [], {}, whwh, box_init=[static["box_init"]])
+                local, _, _ = self._extract(0, static_l, [], {}, size, box_init=[static["box_init"]])
             static["local"] = local
             feats_cur, cached = local["feats"], (local["logits"], local["boxes"], local["obj"])
-            return self._final_stage_launch(feats_cur, cached, whwh, w, h, pairs, [(0, batch)], {0: static["draws"]} if static["draws"] is not None else {}, slots=batch)
+            return self._final_stage_launch(feats_cur, cached, size, pairs, [(0, batch)], {0: static["draws"]} if static["draws"] is not None else {}, slots=batch)
 
         try:
             torch._foreach_copy_(static["frames"], frames)
@@ -1152,7 +877,7 @@ class DiffusionDet(nn.Module):
         self._graphs[key] = static
         return static
 
-    def _extract(self, frame_id, ref_l, ref_g, ahead, whwh, on_global=None, box_init=None):
+    def _extract(self, frame_id, ref_l, ref_g, ahead, size, on_global=None, box_init=None):
         """Backbone + the 3 extraction RCNNHeads + top-k feature selection over [local | global | look-ahead] frames.
         Every stage here is per-frame independent, so the reference's splits of INFER_BATCH -- and with
         INPUT.LOOKAHEAD_BATCHES > 1 the frames of the next batches -- run as launches of up to INFER_BATCH *
@@ -1199,7 +924,7 @@ class DiffusionDet(nn.Module):
             if ci == 0 and self.after_first_launch is not None:
                 self.after_first_launch()          # e.g. the data layer's prefetch of the next group: behind this call's own uploads
             B = feats[0].shape[0]
-            res = self._extract_launch(feats, whwh, box_init_all[a:a + B], max(len_l, a) - a, min(n_own, a + B) - a, ci)
+            res = self._extract_launch(feats, size, box_init_all[a:a + B], max(len_l, a) - a, min(n_own, a + B) - a, ci)
             per_frame += [(res, i) for i in range(B)]
             if self.debug_taps is not None and not self.skip_unobservable:
                 self.debug_taps.setdefault("extract", []).append((res["logits"], res["boxes"], res["obj"], feats))
@@ -1213,7 +938,7 @@ class DiffusionDet(nn.Module):
             pos += len(ahead[fb])
         return local, glob, out_ahead
 
-    def _extract_launch(self, feats, whwh, box_init, g0, g1, ci):
+    def _extract_launch(self, feats, size, box_init, g0, g1, ci):
         """The extraction heads + top-k selection of launch sequence `ci` over the B frames of `feats` (box_init: their draws) -> the
         launch's result dict of per-frame tensors.  [g0, g1): the launch's global frames."""
         B, M, d = feats[0].shape[0], self.num_proposals, self.hidden_dim
@@ -1226,21 +951,21 @@ class DiffusionDet(nn.Module):
                    "k2": torch.empty((B, self.top_k[1], d), device=dev)}
             if g1 > g0:
                 t = torch.full((g1 - g0,), 999, dtype=torch.long)
-                _, k1, k2 = self.model_predictions([f[g0:g1] for f in feats], whwh, box_init[g0:g1], t, box_extract=ci + 1)
+                _, k1, k2 = self.model_predictions([f[g0:g1] for f in feats], size, box_init[g0:g1], t, box_extract=ci + 1)
                 res["k1"][g0:g1] = k1.view(g1 - g0, self.top_k[0], d)
                 res["k2"][g0:g1] = k2.view(g1 - g0, self.top_k[1], d)
             return res
         t = torch.full((B,), 999, dtype=torch.long)
-        (cl, bx, pf), k1, k2 = self.model_predictions(feats, whwh, box_init, t, box_extract=ci + 1)
+        (cl, bx, pf), k1, k2 = self.model_predictions(feats, size, box_init, t, box_extract=ci + 1)
         return {"feats": feats, "logits": cl, "boxes": bx, "obj": pf[0].view(B, M, d), "k1": k1.view(B, self.top_k[0], d),
                 "k2": k2.view(B, self.top_k[1], d)}
 
-    def _final_stage(self, feats, cached, whwh, w, h, pairs, items, ddim_draws, slots=None):
+    def _final_stage(self, feats, cached, size, pairs, items, ddim_draws, slots=None):
         """Global attention + conditioned head (+ DDIM loop) + top-k/NMS over `R` frame slots holding the batches `items`
         = [(call frame id, real frames)], INFER_BATCH slots each unless `slots` says otherwise; -> one BoxList per slot."""
-        return self._to_boxlists(*self._final_stage_launch(feats, cached, whwh, w, h, pairs, items, ddim_draws, slots), (int(w), int(h)))
+        return self._to_boxlists(*self._final_stage_launch(feats, cached, size, pairs, items, ddim_draws, slots), size)
 
-    def _final_stage_launch(self, feats, cached, whwh, w, h, pairs, items, ddim_draws, slots=None):
+    def _final_stage_launch(self, feats, cached, size, pairs, items, ddim_draws, slots=None):
         """the device part of _final_stage: queues every kernel, no host synchronisation -> the post-processing outputs"""
         M = self.num_proposals
         R = cached[0].shape[0]
@@ -1252,8 +977,8 @@ class DiffusionDet(nn.Module):
             self.head.proposals_feat_cur = [[cached[0], cached[1], cached[2].reshape(1, R * M, self.hidden_dim)]]
             t = torch.full((R,), pairs[0][0], dtype=torch.long)
             img = torch.zeros((R, M, 4), device=self.device)
-            outputs_class, outputs_coord = self.model_predictions(feats, whwh, img, t)
-            ob, osc, ol, oc = ops.postproc_topk_nms(outputs_class[-1], outputs_coord[-1], w, h, 0.5, self.use_nms)
+            outputs_class, outputs_coord = self.model_predictions(feats, size, img, t)
+            ob, osc, ol, oc = ops.postproc_topk_nms(outputs_class[-1], outputs_coord[-1], *_img_wh(size), 0.5, self.use_nms)
             if self.debug_taps is not None:
                 self.debug_taps["final_0"] = (outputs_class[-1], outputs_coord[-1])
         else:
@@ -1263,7 +988,7 @@ class DiffusionDet(nn.Module):
             for step, (_, time_next) in enumerate(pairs):
                 if time_next >= 0:
                     draws[step] = tuple(torch.cat([padded(ddim_draws[fb][step][i], nb) for fb, nb in items]) for i in (0, 1))
-            ob, osc, ol, oc = self._ddim_ensemble(feats, whwh, R, items[0][0], pairs, w, h, draws)
+            ob, osc, ol, oc = self._ddim_ensemble(feats, size, R, pairs, draws)
         return ob, osc, ol, oc
 
     # ---- helpers --------------------------------------------------------------------------------
@@ -1287,13 +1012,12 @@ class DiffusionDet(nn.Module):
         return ([f.index_select(0, sel) for f in src["feats"]],
                 tuple(src[k].index_select(0, sel) for k in ("logits", "boxes", "obj")))
 
-    def _ddim_ensemble(self, feats_cur, whwh, batch, frame_id, pairs, w, h, draws=None, skip_last=None):
+    def _ddim_ensemble(self, feats_cur, size, batch, pairs, draws, skip_last=None):
         """SAMPLE_STEP > 1 (diffusion_det.py:551-627): every step re-runs the 3 heads + global attention +
         cond head on the current noisy boxes, renews low-score boxes, and all but the last step feed the
-        NMS ensemble.  whwh = w: an ops.FrameSizes (h None) for still images, every frame by its own size."""
+        NMS ensemble.  size: the frames' (w, h), or an ops.FrameSizes for still images, every frame by its own size; draws: the call's
+        (_ddim_draws, StillImages.uploads)."""
         skip_last = self.skip_unobservable if skip_last is None else skip_last
-        if draws is None:
-            draws = self._ddim_draws(batch, frame_id, pairs)
         img = draws["img"]
         coef = {t: (float(self._sr_host[t]), float(self._srm1_host[t])) for t, _ in pairs}
         ens_logits, ens_boxes = [], []
@@ -1301,7 +1025,7 @@ class DiffusionDet(nn.Module):
             if time_next < 0 and skip_last:
                 continue            # nothing reads the last step's outputs (diffusion_det.py:573-575, :607-627)
             t = torch.full((batch,), time, dtype=torch.long)
-            outputs_class, outputs_coord = self.model_predictions(feats_cur, whwh, img, t)
+            outputs_class, outputs_coord = self.model_predictions(feats_cur, size, img, t)
             if self.debug_taps is not None:
                 self.debug_taps[f"final_{step}"] = (outputs_class[-1], outputs_coord[-1])
             if time_next < 0:
@@ -1311,11 +1035,11 @@ class DiffusionDet(nn.Module):
             sigma = self.ddim_sampling_eta * ((1 - a / an) * (1 - an) / (1 - a)).sqrt()
             c = (1 - an - sigma ** 2).sqrt()
             noise, fresh = draws[step]
-            img = ops.ddim_renew_step(outputs_class[-1], outputs_coord[-1], img, noise, fresh, whwh, self.scale,
+            img = ops.ddim_renew_step(outputs_class[-1], outputs_coord[-1], img, noise, fresh, size, self.scale,
                                       coef[time][0], coef[time][1], float(self._ac_host[time_next].sqrt()), float(c), float(sigma), 0.5)
             ens_logits.append(outputs_class[-1])
             ens_boxes.append(outputs_coord[-1])
-        return ops.postproc_topk_nms(torch.stack(ens_logits), torch.stack(ens_boxes), w, h, 0.5, self.use_nms)
+        return ops.postproc_topk_nms(torch.stack(ens_logits), torch.stack(ens_boxes), *_img_wh(size), 0.5, self.use_nms)
 
     def _to_boxlists(self, ob, osc, ol, oc, size_wh, result_cls=None):
         """size_wh: (w, h) of every frame, or a list of one (w, h) per frame (still images)"""

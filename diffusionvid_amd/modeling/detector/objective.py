@@ -1,0 +1,134 @@
+"""The training objective of a DiffusionDet on labelled batches of still images (diffusion_det.py:338-375): the criterion, the diffusion
+step of an image, the ragged ground truth, the forward that DiffusionDet.loss_sums / compute_losses / loss_gradients share, and the
+gradient with respect to the head outputs.  A batch is admitted and chunked by the detector's StillImages (detector/stills.py); like it,
+an `Objective` holds the detector and none of its video state.
+"""
+import functools
+import math
+
+import torch
+
+from ... import ops
+from ..roi_heads.box_head.loss import (LOSS_KEYS, HungarianMatcherDynamicK, SetCriterionDynamicK, check_limits, coef_from_counts,
+                                       losses_from_sums)
+
+
+class Objective:
+    def __init__(self, detector):
+        self.det = detector
+
+    @functools.cached_property
+    def criterion(self):
+        """SetCriterionDynamicK over HungarianMatcherDynamicK with the weights of diffusion_det.py:275-299, built on first use: a config the
+        criterion refuses (USE_FED_LOSS) still detects"""
+        det = self.det
+        d = det.cfg.MODEL.DiffusionDet
+        matcher = HungarianMatcherDynamicK(cfg=det.cfg, cost_class=d.CLASS_WEIGHT, cost_bbox=d.L1_WEIGHT, cost_giou=d.GIOU_WEIGHT, use_focal=det.use_focal)
+        weights = {"loss_ce": d.CLASS_WEIGHT, "loss_bbox": d.L1_WEIGHT, "loss_giou": d.GIOU_WEIGHT}
+        if d.DEEP_SUPERVISION:
+            for i in range(det.num_heads + det.num_heads_local - 1):
+                weights.update({k + "_%d" % i: v for k, v in list(weights.items())[:3]})
+        return SetCriterionDynamicK(cfg=det.cfg, num_classes=det.num_classes, matcher=matcher, weight_dict=weights, eos_coef=d.NO_OBJECT_WEIGHT,
+                                    losses=["labels", "boxes"], use_focal=det.use_focal)
+
+    @property
+    def weights(self):
+        """{loss name: CLASS_WEIGHT / L1_WEIGHT / GIOU_WEIGHT}, every head output's names with DEEP_SUPERVISION"""
+        return self.criterion.weight_dict
+
+    def train_step(self, image_id):
+        """The diffusion step of an image's loss, a uniform integer in [0, num_timesteps): the reference draws torch.randint per image
+        (diffusion_det.py:695).  With a noise_fn it is derived from the image's key on the host: z = the one N(0, 1) draw of kind
+        "train_t" keyed (image_id, step 0, image 0), u = Phi(z) = (1 + erf(z / sqrt 2)) / 2 in float64, t = min(floor(u * num_timesteps),
+        num_timesteps - 1) -- a pure function of the id, uniform because Phi(z) is.  Without a noise_fn: torch.randint."""
+        det = self.det
+        if det.noise_fn is None:
+            return int(torch.randint(0, det.num_timesteps, (1,)))
+        z = float(det.noise_fn("train_t", int(image_id), 0, 0, (1,)).reshape(-1)[0])
+        u = 0.5 * (1.0 + math.erf(z / math.sqrt(2.0)))
+        return min(int(u * det.num_timesteps), det.num_timesteps - 1)
+
+    def _pack(self, what, targets, sizes_wh):
+        """The ground truth, ragged, on the host -> (absolute xyxy in the image's own size, normalised (cx, cy, w, h) for q_sample, labels
+        1-based, starts int32 [n + 1])"""
+        M = self.det.num_proposals
+        gt_abs, gt_norm, labels, starts = [], [], [], [0]
+        for i, (t, (w, h)) in enumerate(zip(targets, sizes_wh)):
+            if tuple(int(v) for v in t.size) != (w, h):
+                raise ValueError("%s: target %d is for a %s image, the image is %s" % (what, i, tuple(t.size), (w, h)))
+            if not t.has_field("labels"):
+                raise ValueError("%s: target %d carries no `labels` field" % (what, i))
+            b = t.convert("xyxy").bbox.detach().to("cpu", torch.float32).reshape(-1, 4)
+            if b.shape[0] > M:
+                raise NotImplementedError("%s: image %d holds %d ground-truth boxes, MODEL.DiffusionDet.NUM_PROPOSALS is %d (the reference's "
+                                          "random subset is not built)" % (what, i, b.shape[0], M))
+            nb = b / torch.tensor([w, h, w, h], dtype=torch.float32)
+            gt_abs.append(b), labels.append(t.get_field("labels").detach().to("cpu", torch.int32).reshape(-1))
+            gt_norm.append(torch.stack(((nb[:, 0] + nb[:, 2]) / 2, (nb[:, 1] + nb[:, 3]) / 2, nb[:, 2] - nb[:, 0], nb[:, 3] - nb[:, 1]), dim=1))
+            starts.append(starts[-1] + b.shape[0])
+        return torch.cat(gt_abs), torch.cat(gt_norm), torch.cat(labels), torch.tensor(starts, dtype=torch.int32)
+
+    def forward(self, images, targets, image_ids, gradients):
+        """The forward sums and gradients share -> (the device tuple of ops.set_criterion, None or (d_logits, d_boxes) of the sum of the
+        weighted losses with respect to the kept head outputs, from ops.set_criterion_backward on the same stream)."""
+        det = self.det
+        what = "loss_gradients" if gradients else "compute_losses"
+        if isinstance(images, dict):
+            raise NotImplementedError("%s: the video item dict (cur / ref_l / ref_g) of the training protocol is not built; "
+                                      "hand over a batch of still images" % what)
+        imgs, sizes_wh, ids = det.stills.admit(what, images)
+        n = len(sizes_wh)
+        if image_ids is not None:
+            ids = [int(i) for i in image_ids]
+        if len(ids) != n or len(targets) != n:
+            raise ValueError("%s: %d image_ids and %d targets for %d images" % (what, len(ids), len(targets), n))
+        if n == 0:
+            raise ValueError("%s: an empty batch has no loss" % what)
+        criterion = self.criterion          # refuses USE_FED_LOSS by key
+        gt_abs, gt_norm, labels, starts = self._pack(what, targets, sizes_wh)
+        check_limits(det.num_proposals, det.num_classes, criterion.matcher.ota_k, (starts[1:] - starts[:-1]).tolist())
+        steps = torch.tensor([self.train_step(i) for i in ids], dtype=torch.int64)
+        deep = det.cfg.MODEL.DiffusionDet.DEEP_SUPERVISION
+        with torch.no_grad(), det._on_device():
+            dev = det.device
+            # every upload and draw before any kernel is queued (the rule of StillImages.detect)
+            sizes = ops.FrameSizes(torch.tensor(sizes_wh, dtype=torch.float32), dev)
+            noise, placeholder = det.stills.draws("train_noise", ids, 0), det.stills.draws("train_placeholder", ids, 0)
+            up = [t.to(dev) for t in (gt_abs, gt_norm, labels)]
+            if gradients:          # the weights of the kept head outputs, the final one last
+                sfx = ["_%d" % s for s in range(det.num_heads - 1)] + [""] if deep else [""]
+                weights = torch.tensor([[float(self.weights.get(k + x, 1.0)) for k in LOSS_KEYS] for x in sfx], dtype=torch.float64).to(dev)
+            canvas = imgs.tensors.to(dev, torch.float32).contiguous()
+            x_boxes = ops.q_sample_boxes(up[1], starts, steps, det.sqrt_alphas_cumprod, det.sqrt_one_minus_alphas_cumprod, noise, placeholder,
+                                         det.scale, sizes)
+            logits, boxes = [], []
+            for a, b, feats in det.stills.chunks(canvas):
+                lg, bx = det.head.plain_heads(feats, x_boxes[a:b].contiguous(), steps[a:b], intermediate=True)
+                if not deep:
+                    lg, bx = lg[-1:], bx[-1:]
+                logits.append(lg), boxes.append(bx)
+            logits, boxes = torch.cat(logits, dim=1), torch.cat(boxes, dim=1)
+            if det.debug_taps is not None:
+                det.debug_taps.setdefault("train_heads", []).append((logits, boxes, x_boxes, steps))
+            out = criterion.sums(logits, boxes, (up[0], up[2], starts, sizes))
+            if not gradients:
+                return out, None
+            # d(sum of the weighted losses): weight / denominator per head output, the denominators from the matched counts on the device
+            assert logits.shape[0] == weights.shape[0], "one row of weights per kept head output"
+            p = criterion.matcher.params()
+            coef = coef_from_counts(weights, out[2][:, :, 3].sum(1))
+            return out, ops.set_criterion_backward(logits, boxes, up[0], up[2], starts, sizes, p["alpha"], p["gamma"], out[0], out[3], coef)
+
+    def _weighted(self, sums):
+        return {k: v * self.weights.get(k, 1.0) for k, v in losses_from_sums(sums).items()}
+
+    def sums(self, images, targets, image_ids=None):
+        out = self.forward(images, targets, image_ids, False)[0]
+        return out[2].detach().to("cpu", torch.float64), out
+
+    def losses(self, images, targets, image_ids=None):
+        return self._weighted(self.sums(images, targets, image_ids)[0])
+
+    def gradients(self, images, targets, image_ids=None):
+        out, grads = self.forward(images, targets, image_ids, True)
+        return self._weighted(out[2].detach().to("cpu", torch.float64)), grads[0], grads[1]

@@ -148,10 +148,8 @@ class StreamSet:
         parsed = self._validate(items)
         for sid in items:
             self._open(sid)
-        if det.device.type == "cuda" and det.device.index is not None:
-            with torch.cuda.device(det.device):
-                return self._step(items, parsed)
-        return self._step(items, parsed)
+        with det._on_device():
+            return self._step(items, parsed)
 
     def _step(self, items, parsed):
         det = self.det
@@ -172,7 +170,7 @@ class StreamSet:
         self._update_memories(updates, glob)
 
         h, w = parsed[order[0]][0].image_sizes[0]
-        whwh, pairs = (float(w), float(h)), det._time_pairs()
+        size, pairs = (int(w), int(h)), det._time_pairs()
         launched, pos = [], {s: i for i, s in enumerate(order)}
         for _, sids in finals:
             a, b = pos[sids[0]], pos[sids[-1]] + 1          # a pass's streams are adjacent in the layout
@@ -181,7 +179,7 @@ class StreamSet:
             memory = self._packed(0, sids)
             det.head.proposal_feats_global_groups = memory
             try:
-                out = det._final_stage_launch(sp["feats"], (sp["logits"], sp["boxes"], sp["obj"]), whwh, w, h, pairs,
+                out = det._final_stage_launch(sp["feats"], (sp["logits"], sp["boxes"], sp["obj"]), size, pairs,
                                               [(items[s]["frame_id"], 1) for s in sids], ddim, slots=1)
             finally:
                 det.head.proposal_feats_global_groups = None
@@ -189,7 +187,7 @@ class StreamSet:
         results = {}          # the host reads the counts only behind the last pass's launches
         cls = det.boxlist_cls
         for sids, out in launched:
-            boxlists = det._to_boxlists(*out, (int(w), int(h)), result_cls=cls or _result_class(items[sids[0]]["cur"]))
+            boxlists = det._to_boxlists(*out, size, result_cls=cls or _result_class(items[sids[0]]["cur"]))
             for s, bl in zip(sids, boxlists):
                 results[s] = [bl]
         return {s: results[s] for s in items}
@@ -231,14 +229,14 @@ class StreamSet:
         box_init_all = torch.cat(noise)
         fh, fw = frames[0].shape[-2:]
         hh, ww = parsed[order[0]][0].image_sizes[0]
-        whwh = (float(ww), float(hh))
+        size = (int(ww), int(hh))
         cap = self.frames_per_launch
         eng.reserve(min(cap, n_total), fh, fw, M)
         per_frame = []
         for ci, a in enumerate(range(0, n_total, cap)):
             b = min(n_total, a + cap)
             feats = eng.backbone_frames(frames[a:b]) if as_list else eng.backbone(total[a:b].contiguous())
-            res = det._extract_launch(feats, whwh, box_init_all[a:b], max(n_local, a) - a, b - a, ci)
+            res = det._extract_launch(feats, size, box_init_all[a:b], max(n_local, a) - a, b - a, ci)
             per_frame += [(res, i) for i in range(b - a)]
 
         glob = {}

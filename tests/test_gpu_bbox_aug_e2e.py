@@ -158,7 +158,7 @@ def test_device_draws_give_view_0_the_draws_of_detect_images():
         with torch.no_grad():
             both = model.detect_images_aug([_images()[0], _images()[1]], [5, 6])
             one = model.detect_images_aug([_images()[0], _images()[1]], [9, 6])
-        got = model._still_draws("renew", [5, 6], 1, (0, 1))
+        got = model.stills.draws("renew", [5, 6], 1, (0, 1))
         assert torch.equal(got[0], dn.draw("renew", 5, 1, 0, 1, (40, 4), "cuda")[0]) and torch.equal(got[3], dn.draw("renew", 6, 1, 1, 1, (40, 4), "cuda")[0])
     finally:
         model.noise_fn = synthetic.noise_fn

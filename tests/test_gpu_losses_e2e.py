@@ -87,7 +87,7 @@ def test_compute_losses_equals_the_composition_of_its_pieces(p2, dtype):
     assert (S, n, M, logits.shape[3]) == (2, 3, 100, 30) and int(dev[3].abs().sum()) == 0
     # 1. t and the noisy boxes: the documented derivation of t, the host form of q_sample on the same draws
     sizes = torch.tensor([(w, h) for h, w in IMAGE_HW], dtype=torch.float32)
-    assert steps.tolist() == [model._train_step(i) for i in IDS] and all(0 <= t < 1000 for t in steps.tolist())
+    assert steps.tolist() == [model.objective.train_step(i) for i in IDS] and all(0 <= t < 1000 for t in steps.tolist())
     gt_abs = torch.tensor(sum((g[0] for g in GT), []), dtype=torch.float32).reshape(-1, 4)
     lab = torch.tensor(sum((g[1] for g in GT), []), dtype=torch.int32)
     starts = torch.tensor([0, 3, 3, 5], dtype=torch.int32)

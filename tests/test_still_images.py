@@ -100,17 +100,59 @@ def _model(opts=()):
     return DiffusionDet(cfg).eval()
 
 
-@pytest.mark.parametrize("opts,key", [
+REFUSED = [
     (["MODEL.VID.ROI_BOX_HEAD.ATTENTION.ENABLE", False, "MODEL.DiffusionDet.NUM_HEADS_LOCAL", 0], "GLOBAL.ENABLE"),
     (["MODEL.VID.MEGA.GLOBAL.ENABLE", False, "MODEL.VID.ROI_BOX_HEAD.ATTENTION.ENABLE", True, "MODEL.DiffusionDet.NUM_HEADS_LOCAL", 0], "ATTENTION.ENABLE"),
     (["MODEL.VID.MEGA.GLOBAL.ENABLE", False, "MODEL.VID.ROI_BOX_HEAD.ATTENTION.ENABLE", False, "MODEL.DiffusionDet.NUM_HEADS_LOCAL", 1], "NUM_HEADS_LOCAL"),
-])
+]
+
+
+@pytest.mark.parametrize("opts,key", REFUSED)
 def test_detect_images_refuses_models_with_attention(opts, key):
     model = _model(opts)
     with pytest.raises(NotImplementedError) as e:
         model.detect_images([torch.zeros(3, 32, 32)])
     assert key in str(e.value), str(e.value)
     assert model._engine is None          # refused before anything was built or launched
+
+
+DIFFUSION_BUFFERS = ("betas", "alphas_cumprod", "alphas_cumprod_prev", "sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod",
+                     "log_one_minus_alphas_cumprod", "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "posterior_variance",
+                     "posterior_log_variance_clipped", "posterior_mean_coef1", "posterior_mean_coef2")          # diffusion_det.py:222-267
+
+
+def _call(model, entry):
+    if entry == "detect_images":
+        return model.detect_images([torch.zeros(3, 32, 32)])
+    if entry == "detect_images_aug":
+        return model.detect_images_aug([np.zeros((32, 32, 3), dtype=np.uint8)])
+    target = _boxlist([[4, 4, 20, 20]], (32, 32), [1.0], [1])
+    return getattr(model, entry)([torch.zeros(3, 32, 32)], [target])
+
+
+@pytest.mark.parametrize("entry", ["detect_images", "detect_images_aug", "compute_losses", "loss_gradients"])
+@pytest.mark.parametrize("opts,key", REFUSED)
+def test_one_admission_refuses_for_every_still_entry_point(entry, opts, key):
+    """the refusals of a still batch are written once (StillImages.admit's) and carry the entry point's name; the two objects that took the
+    still and loss paths out of the detector are no modules, so the checkpoint's keys are the ones __init__ registers"""
+    from torch import nn
+    from diffusionvid_amd.modeling.detector.objective import Objective
+    from diffusionvid_amd.modeling.detector.stills import StillImages
+    from diffusionvid_amd.utils import synthetic
+    aug = ["TEST.BBOX_AUG.ENABLED", True] if entry == "detect_images_aug" else []
+    model = _model(list(opts) + aug)
+    with pytest.raises(NotImplementedError) as e:
+        _call(model, entry)
+    assert str(e.value).startswith(entry + ":") and key in str(e.value), str(e.value)
+    assert model._engine is None          # refused before anything was built or launched
+    assert type(model.stills) is StillImages and type(model.objective) is Objective
+    assert not isinstance(model.stills, nn.Module) and not isinstance(model.objective, nn.Module)
+    base = _model(BASELINE + aug)
+    d = base.cfg.MODEL.DiffusionDet
+    want = synthetic.make_state_dict(0, blocks=BLOCKS, hidden=d.HIDDEN_DIM, nheads=d.NHEADS, dim_ff=d.DIM_FEEDFORWARD, dim_dynamic=d.DIM_DYNAMIC,
+                                     num_classes=d.NUM_CLASSES, num_cls=d.NUM_CLS, num_reg=d.NUM_REG, num_heads=d.NUM_HEADS, num_heads_cond=0,
+                                     pooler=base.cfg.MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION, prior_prob=d.PRIOR_PROB, local_stages=0, fpn_levels=base.fpn_levels)
+    assert set(base.state_dict()) == set(want) | set(DIFFUSION_BUFFERS)
 
 
 def test_detect_images_checks_its_arguments():
@@ -147,7 +189,7 @@ def test_detect_images_leaves_the_video_state_alone(monkeypatch):
     state = ("queue", "local_img_queue", "_ahead", "_results_ahead", "video_index", "_graphs", "_graph_seen", "_graph_generation", "graph_replays")
     before = {k: (id(getattr(model, k)), repr(getattr(model, k))) for k in state}
     head_before = (list(model.head.proposal_feats_global), list(model.head.proposal_feats_local), list(model.head.proposals_feat_cur))
-    monkeypatch.setattr(model, "_detect_images", lambda canvas, sizes_wh, ids, cls: [(tuple(canvas.shape), sizes_wh, ids)])
+    monkeypatch.setattr(model.stills, "_detect", lambda canvas, sizes_wh, ids, cls: [(tuple(canvas.shape), sizes_wh, ids)])
     out = model.detect_images([torch.zeros(3, 40, 70), torch.zeros(3, 64, 30)], image_ids=[11, 4])
     assert out == [((2, 3, 64, 96), [(70, 40), (30, 64)], [11, 4])]
     assert before == {k: (id(getattr(model, k)), repr(getattr(model, k))) for k in state}
