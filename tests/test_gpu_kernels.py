@@ -343,7 +343,9 @@ def test_head_tail_fused_matches_layerwise(dv, tmp_path, cond, n):
     """csrc/headtail.hip (FFN + norm3 + modulation + towers + class_logits + bboxes_delta + apply_deltas in one row-tile kernel)
     against the layer-by-layer launches it replaces (library option head_tail = 0) on the same inputs: the
     same fp16 operands and fp32 statistics in another summation order, so logits / object features agree to rounding (3e-3 of
-    the O(1) values) and boxes to 5e-3 of their size.  300 rows (32-row tiles, ragged last tile), 900 rows, 18000 rows (64-row tiles)."""
+    the O(1) values) and boxes to 5e-3 of their size.  300, 900 and 18000 rows, all on 32-row tiles (dvid_head_tail_launch takes them at
+    every size) with a ragged last one; 300 rows per frame, so every tenth tile or so straddles two frames.  The three frames of the 900-row
+    case carry a time step each (the tile's rows then read different scale rows of the per-frame table), the others one for all frames."""
     sd, _ = _head_setup()
     g = torch.Generator().manual_seed(80 + n)
     M, H, W = 300, 96, 160
@@ -352,7 +354,7 @@ def test_head_tail_fused_matches_layerwise(dv, tmp_path, cond, n):
     boxes[0, 0] = torch.tensor([10.0, 10.0, 14.0, 13.0])
     pro = torch.randn(n * M, 256, generator=g)
     cnd = torch.randn(n * M, 256, generator=g) if cond else None
-    t = torch.full((n,), 499, dtype=torch.long)
+    t = torch.tensor([999, 499, 0], dtype=torch.long) if n == 3 else torch.full((n,), 499, dtype=torch.long)
     model = dv.Model(sd, res_blocks=(0, 0, 0, 0))
     model.reserve(n, H, W, M)
     fd = [dv.nhwc_from_nchw(f.cuda()) for f in feats]
