@@ -47,6 +47,8 @@ SIGNATURES = {
     "dvid_backbone_swin_fpn_levels_frames": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "dvid_rcnn_head_levels": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                       c_void_p, C.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dvid_rcnn_head_levels_keep": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                           c_void_p, C.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dvid_rcnn_head": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                c_void_p, C.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dvid_global_xattn": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
@@ -96,6 +98,8 @@ SIGNATURES = {
                            [c_void_p, c_void_p, c_int] + [c_void_p] * 3 + [c_int64, c_void_p]),
     "dvid_set_criterion_scratch_bytes": (c_int64, [c_int] * 4),
     "dvid_set_criterion_backward": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 5 + [c_float, c_float] + [c_void_p] * 6),
+    "dvid_head_tail_backward": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p, c_int] + [c_float] * 5 + [c_void_p] * 11 + [c_int64, c_void_p]),
+    "dvid_head_tail_backward_scratch_bytes": (c_int64, [c_int] * 7),
     "dvid_cdist":(c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "dvid_fps_greedy": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dvid_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -179,6 +179,21 @@ struct HeadTailParams {
 bool dvid_head_tail_supported(int hidden, int dff, int num_cls, int num_reg, int num_classes);
 int dvid_head_tail_launch(const HeadTailParams& p, hipStream_t s);
 
+// headtail_bwd.hip: the tail's fp32 recompute and its backward (include/dvid_hip.h: dvid_head_tail_backward states the arguments)
+struct HeadTailBwdArgs {
+    const float *x, *boxes_in, *time_emb, *cond;
+    int n, m, dff, num_classes, num_cls, num_reg;
+    const float* const* params;
+    float wx, wy, ww, wh, scale_clamp;
+    const float *d_logits, *d_boxes, *d_obj;
+    float *logits_out, *boxes_out, *obj_out;
+    float *d_x, *d_time_emb, *d_cond;
+    float* const* grads;          // null: the forward only
+    void* scratch;
+};
+long long dvid_head_tail_backward_scratch_bytes_host(int n, int m, int dff, int num_classes, int num_cls, int num_reg, int has_cond);
+int dvid_head_tail_backward_launch(const HeadTailBwdArgs& a, hipStream_t s);
+
 // boxes.hip
 int dvid_apply_deltas_launch(const float* deltas, int delta_ld, const float* boxes, float* out, int n, float wx, float wy, float ww,
                              float wh, float clamp, int* bad_flag, hipStream_t s);

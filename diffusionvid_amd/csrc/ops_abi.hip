@@ -402,6 +402,46 @@ int dvid_set_criterion_backward(const float* logits, const float* boxes, int n_s
     return DVID_OK;
 }
 
+int64_t dvid_head_tail_backward_scratch_bytes(int n, int m, int dff, int num_classes, int num_cls, int num_reg, int has_cond) {
+    return dvid_head_tail_backward_scratch_bytes_host(n, m, dff, num_classes, num_cls, num_reg, has_cond);
+}
+
+int dvid_head_tail_backward(const float* x, const float* boxes_in, const float* time_emb, const float* cond, int n, int m, int hidden, int dff,
+                            int num_classes, int num_cls, int num_reg, const float* const* params, int n_params, float wx, float wy, float ww, float wh,
+                            float scale_clamp, const float* d_logits, const float* d_boxes, const float* d_obj, float* logits_out, float* boxes_out,
+                            float* obj_out, float* d_x, float* d_time_emb, float* d_cond, float* const* grads, void* scratch, int64_t scratch_bytes,
+                            void* stream) {
+    g_err[0] = 0;
+    const char* what = "head tail backward";
+    if (hidden != 256) FAIL(DVID_ERR_UNSUPPORTED, "%s: hidden size %d, the kernels take 256", what, hidden);
+    if (dff < DVID_HEAD_TAIL_BWD_TILE || dff % DVID_HEAD_TAIL_BWD_TILE)
+        FAIL(DVID_ERR_UNSUPPORTED, "%s: dim_feedforward %d is not a positive multiple of the product tile, %d (DVID_HEAD_TAIL_BWD_TILE)", what, dff,
+             DVID_HEAD_TAIL_BWD_TILE);
+    if (num_classes < 1 || num_classes > DVID_MAX_CLASSES)
+        FAIL(DVID_ERR_UNSUPPORTED, "%s: %d classes, the limit is 1 .. %d (DVID_MAX_CLASSES)", what, num_classes, DVID_MAX_CLASSES);
+    if (num_cls < 0 || num_cls > 4 || num_reg < 0 || num_reg > 4)
+        FAIL(DVID_ERR_UNSUPPORTED, "%s: NUM_CLS %d / NUM_REG %d, the forward takes 0 .. 4 of each", what, num_cls, num_reg);
+    if (n < 1 || m < 1) FAIL(DVID_ERR_ARG, "%s: %d images x %d boxes: no rows", what, n, m);
+    if (n > 65535 || (long long)n * m > DVID_HEAD_TAIL_BWD_MAX_ROWS)
+        FAIL(DVID_ERR_UNSUPPORTED, "%s: %d images x %d boxes, the limit is 65535 images and %d rows (DVID_HEAD_TAIL_BWD_MAX_ROWS)", what, n, m,
+             DVID_HEAD_TAIL_BWD_MAX_ROWS);
+    if (n_params != 14 + 3 * (num_cls + num_reg))
+        FAIL(DVID_ERR_ARG, "%s: %d parameter pointers, NUM_CLS %d and NUM_REG %d make it %d", what, n_params, num_cls, num_reg, 14 + 3 * (num_cls + num_reg));
+    if (!x || !boxes_in || !time_emb || !params || !scratch) FAIL(DVID_ERR_ARG, "%s: null pointer", what);
+    const bool backward = grads || d_x || d_time_emb || d_cond;
+    if (backward && (!grads || !d_x || !d_time_emb || (cond && !d_cond))) FAIL(DVID_ERR_ARG, "%s: null pointer among the gradient outputs", what);
+    if (!backward && (d_logits || d_boxes || d_obj)) FAIL(DVID_ERR_ARG, "%s: cotangents without gradient outputs", what);
+    for (int i = 0; i < n_params; ++i) {
+        if ((i == 8 || i == 9) && !cond) continue;          // c_mlp.1 belongs to the cond head
+        if (!params[i] || (backward && !grads[i])) FAIL(DVID_ERR_ARG, "%s: null pointer for parameter %d", what, i);
+    }
+    TRY(scratch_ok(what, scratch, scratch_bytes, dvid_head_tail_backward_scratch_bytes_host(n, m, dff, num_classes, num_cls, num_reg, cond != nullptr)));
+    HeadTailBwdArgs a{x, boxes_in, time_emb, cond, n, m, dff, num_classes, num_cls, num_reg, params, wx, wy, ww, wh, scale_clamp, d_logits, d_boxes, d_obj,
+                      logits_out, boxes_out, obj_out, d_x, d_time_emb, d_cond, backward ? grads : nullptr, scratch};
+    TRY(dvid_head_tail_backward_launch(a, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
 // What dvid_coco_eval_match and dvid_lvis_eval_match check alike; `what` names the protocol, `pointers` is false when one the entry needs
 // is null, *max_gt gets the greatest box count of one image
 static int image_eval_args_ok(const char* what, bool pointers, int n_images, int cap, int num_classes, const int* gt_starts_host, int limit,

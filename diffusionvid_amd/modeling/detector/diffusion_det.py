@@ -434,17 +434,27 @@ class DiffusionDet(nn.Module):
         nothing is replayed from a hipGraph.  The video item dict is refused by name (not built)."""
         return self.objective.losses(images, targets, image_ids)
 
-    def loss_gradients(self, images, targets, image_ids=None):
-        """compute_losses and the first link of its backward pass: -> (losses, d_logits [S, n, M, C], d_boxes [S, n, M, 4]).  Inputs and
+    def loss_gradients(self, images, targets, image_ids=None, through="outputs"):
+        """compute_losses and the first links of its backward pass: -> (losses, d_logits [S, n, M, C], d_boxes [S, n, M, 4]).  Inputs and
         refusals are compute_losses'; `losses` is compute_losses' dict; the two fp32 tensors, which stay on the device, are the gradient of
         the SUM of the weighted losses with respect to every kept head output (logits and absolute xyxy boxes as
         debug_taps["train_heads"] records them), the final head output last; S is 1 without DEEP_SUPERVISION.  One
         ops.set_criterion_backward launch behind the forward's ops.set_criterion, on the same tensors.
 
-        The gradient stops at the head outputs: the HIP head, the FPN and the backbone have no backward.  A coefficient divides by the
-        BATCH's matched count of its head output (the reference's denominators), so an image's gradient depends on the batch it is in; its
-        loss sums do not."""
-        return self.objective.gradients(images, targets, image_ids)
+        through="outputs" (the default) stops at the head outputs.  through="tail" (DTYPE float32 models, DROPOUT 0.0; anything else is refused
+        by key) goes on through the tail of every kept head -- FFN, norm3, modulation, towers, class_logits, bboxes_delta, apply_deltas:
+        box_head.tail, csrc/headtail_bwd.hip -- and returns a dict: "losses", "d_logits", "d_boxes" as above, and
+          "param_grads"  {state-dict name: gradient} of every tail parameter whose gradient is COMPLETE at this link: block_time_mlp.1, the
+                         cls / reg towers, class_logits and bboxes_delta of every kept head (the reference detaches the boxes between
+                         heads), and linear1, linear2, norm3 of the last head
+          "partial"      the own-output term of linear1 / linear2 / norm3 of the earlier kept heads: NOT their gradient, the path through the
+                         next head's attention and DynamicConv is not built
+          "d_tail_in"    [kept heads, n * M, 256] and "d_time_emb" [n, 1024] (summed over the kept heads): the hand-over to the next link,
+                         with "tail_in", "boxes_in" and "time_emb", the tail inputs they belong to
+        Without DEEP_SUPERVISION only the last head's tail is differentiated.  Attention, DynamicConv, RoIAlign, the FPN, the backbone and
+        time_mlp have no backward.  A coefficient divides by the BATCH's matched count of its head output (the reference's denominators), so
+        an image's gradient depends on the batch it is in; its loss sums do not."""
+        return self.objective.gradients(images, targets, image_ids, through)
 
     def _reset_video(self):
         self._ahead = {}

@@ -7,10 +7,15 @@ import functools
 import math
 
 import torch
+import torch.nn.functional as F
 
 from ... import ops
+from ..roi_heads.box_head import tail as T
 from ..roi_heads.box_head.loss import (LOSS_KEYS, HungarianMatcherDynamicK, SetCriterionDynamicK, check_limits, coef_from_counts,
                                        losses_from_sums)
+
+
+TAIL_PARAMS = ("linear1.", "linear2.", "norm3.", "block_time_mlp.", "cls_module.", "reg_module.", "class_logits.", "bboxes_delta.")
 
 
 class Objective:
@@ -68,11 +73,68 @@ class Objective:
             starts.append(starts[-1] + b.shape[0])
         return torch.cat(gt_abs), torch.cat(gt_norm), torch.cat(labels), torch.tensor(starts, dtype=torch.int32)
 
-    def forward(self, images, targets, image_ids, gradients):
+    THROUGH = ("outputs", "tail")
+
+    def check_through(self, through):
+        """what loss_gradients(through=...) refuses, each by name, before anything is built or launched"""
+        if through not in self.THROUGH:
+            raise ValueError("loss_gradients: through=%r is not one of %s" % (through, ", ".join(repr(v) for v in self.THROUGH)))
+        if through == "tail":
+            if self.det.dtype != "float32":
+                raise NotImplementedError("loss_gradients: through='tail' needs DTYPE float32, this model is %s (fp16 gradients are out of scope)"
+                                          % self.det.dtype)
+            T.check_dropout(self.det.cfg, "loss_gradients")
+
+    def tail_params(self, head):
+        """{name without the prefix: fp32 device tensor} of head_series.<head>'s tail, copied on first use and kept while the engine lives"""
+        det = self.det
+        eng = det._get_engine()
+        if getattr(self, "_tail_cache", (None,))[0] is not eng:
+            self._tail_cache = (eng, {})
+        cache = self._tail_cache[1]
+        if head not in cache:
+            pfx = "head.head_series.%d." % head
+            cache[head] = {k[len(pfx):]: v.detach().to(det.device, torch.float32).contiguous() for k, v in det.state_dict().items()
+                           if k.startswith(pfx) and k[len(pfx):].startswith(TAIL_PARAMS)}
+        return cache[head]
+
+    def time_embedding(self, steps):
+        """time_mlp(t) [n, 4 d] in fp32 on the device (box_head.py:218-223: sinusoidal embedding, Linear, GELU, Linear); no backward"""
+        det = self.det
+        sd = det.state_dict()
+        d = det.cfg.MODEL.DiffusionDet.HIDDEN_DIM
+        half = d // 2
+        freq = torch.exp(torch.arange(half, dtype=torch.float32) * -(math.log(10000.0) / (half - 1)))
+        arg = steps.to(torch.float32)[:, None] * freq[None, :]
+        emb = torch.cat((arg.sin(), arg.cos()), dim=-1).to(det.device)
+        w = lambda k: sd["head.time_mlp." + k].detach().to(det.device, torch.float32)
+        return F.linear(F.gelu(F.linear(emb, w("1.weight"), w("1.bias"))), w("3.weight"), w("3.bias")).contiguous()
+
+    def tail_backward(self, kept_heads, tail_in, boxes_in, steps, d_logits, d_boxes):
+        """ops.head_tail_backward for every kept head -> the tail entries of loss_gradients(through="tail")"""
+        n, M = d_logits.shape[1:3]
+        time_emb = self.time_embedding(steps)
+        out = {"param_grads": {}, "partial": {}, "d_tail_in": [], "d_time_emb": torch.zeros_like(time_emb), "tail_in": tail_in, "boxes_in": boxes_in,
+               "time_emb": time_emb}
+        for s, head in enumerate(kept_heads):
+            g = ops.head_tail_backward(tail_in[s], boxes_in[s].reshape(n * M, 4), time_emb, self.tail_params(head), d_logits=d_logits[s].reshape(n * M, -1),
+                                       d_boxes=d_boxes[s].reshape(n * M, 4))
+            last = head == self.det.num_heads - 1
+            for k, v in g["param_grads"].items():
+                whole = last or not k.startswith(("linear1.", "linear2.", "norm3."))
+                out["param_grads" if whole else "partial"]["head.head_series.%d.%s" % (head, k)] = v
+            out["d_tail_in"].append(g["d_x"])
+            out["d_time_emb"] += g["d_time_emb"]
+        out["d_tail_in"] = torch.stack(out["d_tail_in"])
+        return out
+
+    def forward(self, images, targets, image_ids, gradients, through="outputs"):
         """The forward sums and gradients share -> (the device tuple of ops.set_criterion, None or (d_logits, d_boxes) of the sum of the
-        weighted losses with respect to the kept head outputs, from ops.set_criterion_backward on the same stream)."""
+        weighted losses with respect to the kept head outputs, from ops.set_criterion_backward on the same stream; with through="tail" a
+        third entry, the dict of tail_backward)."""
         det = self.det
         what = "loss_gradients" if gradients else "compute_losses"
+        tail = gradients and through == "tail"
         if isinstance(images, dict):
             raise NotImplementedError("%s: the video item dict (cur / ref_l / ref_g) of the training protocol is not built; "
                                       "hand over a batch of still images" % what)
@@ -101,9 +163,15 @@ class Objective:
             canvas = imgs.tensors.to(dev, torch.float32).contiguous()
             x_boxes = ops.q_sample_boxes(up[1], starts, steps, det.sqrt_alphas_cumprod, det.sqrt_one_minus_alphas_cumprod, noise, placeholder,
                                          det.scale, sizes)
-            logits, boxes = [], []
+            logits, boxes, tail_in, boxes_in = [], [], [], []
             for a, b, feats in det.stills.chunks(canvas):
-                lg, bx = det.head.plain_heads(feats, x_boxes[a:b].contiguous(), steps[a:b], intermediate=True)
+                if tail:          # the same launches plus one copy per head: every head's tail input, and the boxes each head started from
+                    lg, bx, tx = det.head.plain_heads(feats, x_boxes[a:b].contiguous(), steps[a:b], intermediate=True, tail_inputs=True)
+                    bi = torch.cat((x_boxes[a:b][None], bx[:-1]))
+                    tail_in.append(tx.reshape(tx.shape[0], b - a, -1, tx.shape[-1]) if deep else tx[-1:].reshape(1, b - a, -1, tx.shape[-1]))
+                    boxes_in.append(bi if deep else bi[-1:])
+                else:
+                    lg, bx = det.head.plain_heads(feats, x_boxes[a:b].contiguous(), steps[a:b], intermediate=True)
                 if not deep:
                     lg, bx = lg[-1:], bx[-1:]
                 logits.append(lg), boxes.append(bx)
@@ -117,7 +185,13 @@ class Objective:
             assert logits.shape[0] == weights.shape[0], "one row of weights per kept head output"
             p = criterion.matcher.params()
             coef = coef_from_counts(weights, out[2][:, :, 3].sum(1))
-            return out, ops.set_criterion_backward(logits, boxes, up[0], up[2], starts, sizes, p["alpha"], p["gamma"], out[0], out[3], coef)
+            grads = ops.set_criterion_backward(logits, boxes, up[0], up[2], starts, sizes, p["alpha"], p["gamma"], out[0], out[3], coef)
+            if not tail:
+                return out, grads
+            tail_in = torch.cat(tail_in, dim=1)
+            kept = list(range(det.num_heads)) if deep else [det.num_heads - 1]
+            return out, grads, self.tail_backward(kept, tail_in.reshape(tail_in.shape[0], -1, tail_in.shape[-1]).contiguous(),
+                                                  torch.cat(boxes_in, dim=1).contiguous(), steps, grads[0], grads[1])
 
     def _weighted(self, sums):
         return {k: v * self.weights.get(k, 1.0) for k, v in losses_from_sums(sums).items()}
@@ -129,6 +203,11 @@ class Objective:
     def losses(self, images, targets, image_ids=None):
         return self._weighted(self.sums(images, targets, image_ids)[0])
 
-    def gradients(self, images, targets, image_ids=None):
-        out, grads = self.forward(images, targets, image_ids, True)
-        return self._weighted(out[2].detach().to("cpu", torch.float64)), grads[0], grads[1]
+    def gradients(self, images, targets, image_ids=None, through="outputs"):
+        self.check_through(through)
+        res = self.forward(images, targets, image_ids, True, through)
+        out, grads = res[:2]
+        losses = self._weighted(out[2].detach().to("cpu", torch.float64))
+        if through == "outputs":
+            return losses, grads[0], grads[1]
+        return dict(res[2], losses=losses, d_logits=grads[0], d_boxes=grads[1])

@@ -1120,9 +1120,12 @@ class Model:
         call(fn, self.handle, table, n, h, w, levels, len(outs), stream_ptr())
         return outs          # `keep` may die here: the stream-ordered caching allocator re-uses a frame's block only behind this stream's reads
 
-    def rcnn_head(self, head_index, feats_nhwc, height, width, boxes, pro_features, t, cond=None, bad_flag=None):
+    def rcnn_head(self, head_index, feats_nhwc, height, width, boxes, pro_features, t, cond=None, bad_flag=None, keep_tail_input=False):
         """One RCNNHead / RCNNHead_cond pass over the maps it is given, [p3, p4, p5] or [p2, p3, p4, p5].  boxes [n, M, 4]; pro_features
-        [n*M, d] or None; t: int64 [n] (CPU)."""
+        [n*M, d] or None; t: int64 [n] (CPU).  keep_tail_input=True (DTYPE float32 models only): a fourth return value, the tail's input
+        -- the fp32 norm2 output [n*M, d] that head_tail_backward takes as x (dvid_rcnn_head_levels_keep); the other three keep their bits."""
+        if keep_tail_input and self.precision != "float32":
+            raise _lib.DvidError(f"rcnn_head: keep_tail_input needs a DTYPE float32 model, this one is {self.precision} (fp16 gradients are out of scope)")
         boxes = _cuda(boxes, torch.float32)
         n, M = boxes.shape[:2]
         dev = boxes.device
@@ -1141,6 +1144,11 @@ class Model:
         if cond is not None:
             cond = _cuda(cond, torch.float32)
         levels, nl = _pyramid(feats_nhwc, height, width, "rcnn_head")
+        if keep_tail_input:
+            tail_in = torch.empty((n * M, d), dtype=torch.float32, device=dev)
+            call("dvid_rcnn_head_levels_keep", self.handle, head_index, int(cond is not None), levels, nl, n, height, width, M, ptr(boxes),
+                 ptr(pro_features), tp, ptr(cond), ptr(logits), ptr(boxes_out), ptr(obj), ptr(bad_flag), ptr(tail_in), stream_ptr())
+            return logits, boxes_out, obj, tail_in
         call("dvid_rcnn_head_levels", self.handle, head_index, int(cond is not None), levels, nl, n, height, width, M, ptr(boxes),
              ptr(pro_features), tp, ptr(cond), ptr(logits), ptr(boxes_out), ptr(obj), ptr(bad_flag), stream_ptr())
         return logits, boxes_out, obj
@@ -1273,6 +1281,69 @@ def q_sample_boxes(gt_cxcywh, gt_starts, t, sqrt_alphas_cumprod, sqrt_one_minus_
     starts_dev, t_dev = starts_host.to(dev), t_host.to(dev)          # named: a temporary would be freed, and its block reused, before the call
     call("dvid_q_sample_boxes", ptr(gt), ptr(starts_dev), ptr(starts_host), n, M, ptr(t_dev), ptr(t_host), ptr(sa), ptr(so), sa.shape[0],
          ptr(noise), ptr(placeholder), float(snr_scale), ptr(fs), ptr(out), stream_ptr())
+    return out
+
+
+HEAD_TAIL_BWD_ROW_CHUNK = 256          # DVID_HEAD_TAIL_BWD_ROW_CHUNK: the rows of one partial of a sum over rows
+
+
+def head_tail_backward_scratch_bytes(n, M, dff, num_classes, num_cls, num_reg, cond):
+    """bytes of scratch dvid_head_tail_backward needs for n images of M boxes (-1: sizes it does not take)"""
+    return int(_lib.load().dvid_head_tail_backward_scratch_bytes(int(n), int(M), int(dff), int(num_classes), int(num_cls), int(num_reg), int(bool(cond))))
+
+
+def head_tail_backward(x, boxes_in, time_emb, params, cond=None, d_logits=None, d_boxes=None, d_obj=None, bbox_weights=(2.0, 2.0, 1.0, 1.0),
+                       scale_clamp=None, forward_only=False):
+    """The tail of an RCNNHead / RCNNHead_cond pass recomputed in fp32 and its gradient (dvid_head_tail_backward, csrc/headtail_bwd.hip;
+    box_head.tail states the function).  x [R, 256] (the norm2 output, R = n * M image-major), boxes_in [R, 4], time_emb [n, 1024], cond
+    [R, 256] or None, all fp32 on the device; params {name without the head's prefix: fp32 device tensor in the reference's layout}.
+    Cotangents d_logits [R, C], d_boxes [R, 4], d_obj [R, 256]: None means zeros.  Returns a dict: the forward outputs "logits", "boxes",
+    "obj", and -- unless forward_only -- "d_x", "d_time_emb", "d_cond" (None without cond) and "param_grads" {name: gradient}, every element
+    written.  include/dvid_hip.h states the arithmetic (fp32 MFMA products, fixed-order sums without atomics: two runs give the same bits) and
+    the conventions at the kinks."""
+    from .modeling.roi_heads.box_head import tail as T
+    x, boxes_in, time_emb = _cuda(x, torch.float32), _cuda(boxes_in, torch.float32), _cuda(time_emb, torch.float32)
+    assert x.dim() == 2 and time_emb.dim() == 2 and time_emb.shape[0] >= 1 and x.shape[0] % time_emb.shape[0] == 0, "x is [n * M, d], time_emb [n, 4 d]"
+    R, d = x.shape
+    n = time_emb.shape[0]
+    M = R // n
+    assert boxes_in.shape == (R, 4) and time_emb.shape == (n, 4 * d), "boxes_in is [R, 4], time_emb [n, 4 d]"
+    if cond is not None:
+        cond = _cuda(cond, torch.float32)
+        assert cond.shape == (R, d), "cond is [R, d]"
+    num_cls, num_reg = T.tower_depths(params)
+    names = T.param_names(num_cls, num_reg, cond is not None)
+    plist = [None if k is None else _cuda(params[k].detach(), torch.float32) for k in names]
+    dff, c = plist[0].shape[0], plist[10].shape[0]
+    want = {"linear1.weight": (dff, d), "linear1.bias": (dff,), "linear2.weight": (d, dff), "linear2.bias": (d,), "block_time_mlp.1.weight":
+            (d if cond is not None else 2 * d, 4 * d), "block_time_mlp.1.bias": (d if cond is not None else 2 * d,), "class_logits.weight": (c, d),
+            "class_logits.bias": (c,), "bboxes_delta.weight": (4, d), "bboxes_delta.bias": (4,)}
+    for k, t in zip(names, plist):
+        if k is not None:
+            shape = want.get(k, (d, d) if k.endswith("weight") and t.dim() == 2 else (d,))
+            assert tuple(t.shape) == shape, "%s is %s, expected %s" % (k, tuple(t.shape), shape)
+    dev = x.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = {"logits": new(R, c), "boxes": new(R, 4), "obj": new(R, d)}
+    cot = [None if t is None else _cuda(t, torch.float32) for t in (d_logits, d_boxes, d_obj)]
+    for t, shape in zip(cot, ((R, c), (R, 4), (R, d))):
+        assert t is None or tuple(t.shape) == shape, "a cotangent has its output's shape"
+    glist = []
+    if forward_only:
+        assert all(t is None for t in cot), "cotangents without a backward"
+    else:
+        out.update({"d_x": new(R, d), "d_time_emb": new(n, 4 * d), "d_cond": new(R, d) if cond is not None else None})
+        glist = [None if t is None else torch.empty_like(t) for t in plist]
+        out["param_grads"] = {k: g for k, g in zip(names, glist) if k is not None}
+    table = lambda ts: (C.c_void_p * len(names))(*[None if t is None else t.data_ptr() for t in ts])
+    ptable = table(plist)
+    gtable = table(glist) if glist else None
+    nbytes = head_tail_backward_scratch_bytes(n, M, dff, c, num_cls, num_reg, cond is not None)
+    scratch = torch.empty((max(nbytes, 16) + 15) // 16 * 4, dtype=torch.float32, device=dev)
+    call("dvid_head_tail_backward", ptr(x), ptr(boxes_in), ptr(time_emb), ptr(cond), n, M, d, dff, c, num_cls, num_reg, C.cast(ptable, C.c_void_p),
+         len(names), *(float(w) for w in bbox_weights), float(T.SCALE_CLAMP if scale_clamp is None else scale_clamp), *(ptr(t) for t in cot),
+         ptr(out["logits"]), ptr(out["boxes"]), ptr(out["obj"]), ptr(out.get("d_x")), ptr(out.get("d_time_emb")), ptr(out.get("d_cond")),
+         None if gtable is None else C.cast(gtable, C.c_void_p), ptr(scratch), scratch.numel() * 4, stream_ptr())
     return out
 
 

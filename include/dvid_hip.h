@@ -165,6 +165,14 @@ int dvid_rcnn_head_levels(dvid_model* m, int head_index, int is_cond, const void
                           int height, int width, int boxes_per_frame, const float* boxes, const float* pro_features,
                           const int64_t* t, const float* cond, float* logits, float* boxes_out, float* obj_features,
                           int* bad_box_flag, void* stream);
+/* dvid_rcnn_head_levels_keep (dvid_version >= 14): dvid_rcnn_head_levels, which also writes the tail's input -- the fp32 norm2 output
+ * [n_frames * boxes_per_frame][256] that dvid_head_tail_backward takes as x -- to tail_input.  Null: exactly dvid_rcnn_head_levels.  The copy
+ * is one device-to-device transfer behind norm2; every kernel of the pass reads and writes what it did, so all other outputs keep their
+ * bits.  DTYPE float32 models only: a float16 model is refused (DVID_ERR_UNSUPPORTED), fp16 gradients being out of scope. */
+int dvid_rcnn_head_levels_keep(dvid_model* m, int head_index, int is_cond, const void* const* levels, int n_levels, int n_frames,
+                               int height, int width, int boxes_per_frame, const float* boxes, const float* pro_features,
+                               const int64_t* t, const float* cond, float* logits, float* boxes_out, float* obj_features,
+                               int* bad_box_flag, float* tail_input, void* stream);
 
 /* cond[R,hidden] = MHA(query = obj_features[R,hidden], key = value = memory[lk,hidden]).  memory == NULL: use the K/V
  * projections kept by the last dvid_global_memory_project (lk 0 or the same row count). */
@@ -676,6 +684,46 @@ int64_t dvid_set_criterion_scratch_bytes(int n_sets, int n, int m, int gmax);
 int dvid_set_criterion_backward(const float* logits, const float* boxes, int n_sets, int n, int m, int c, const float* gt_boxes, const int* gt_labels,
                                 const int* gt_starts, const int* gt_starts_host, const float* sizes, float alpha, float gamma, const int* assign,
                                 const int* status, const double* coef, float* d_logits, float* d_boxes, void* stream);
+
+/* ---- the backward of the head's tail (dvid_version >= 14; csrc/headtail_bwd.hip) ----
+ * dvid_head_tail_backward (dvid_version >= 14): the tail of an RCNNHead / RCNNHead_cond pass (box_head.py:524-548 / :636-664) recomputed in
+ * fp32, and its gradient.  The host mirror is modeling/roi_heads/box_head/tail.py (head_tail_host).  The function: x [R][256] is the norm2
+ * output, R = n * m rows image-major; boxes_in [R][4]; time_emb [n][1024]; cond [R][256] or null (null: RCNNHead; given: RCNNHead_cond,
+ * whose shift is c_mlp.1(SiLU(cond)) per row and whose block_time_mlp.1 has 256 rows, the scale alone).
+ *   obj    = norm3(x + linear2(ReLU(linear1(x))))                 fc = obj * (scale + 1) + shift, (scale, shift) = block_time_mlp.1(SiLU(time_emb))
+ *   logits = class_logits(cls tower(fc))                            boxes = apply_deltas(bboxes_delta(reg tower(fc)), boxes_in)
+ * a tower layer being ReLU(LayerNorm(Linear without bias)), dropout the identity.  `params` is a HOST table of n_params = 14 + 3 * (num_cls +
+ * num_reg) device pointers, fp32 in the reference's row-major layout, and `grads` a host table of the same length and shapes:
+ *   0 linear1.weight [dff][256]   1 linear1.bias   2 linear2.weight [256][dff]   3 linear2.bias   4 norm3.weight   5 norm3.bias
+ *   6 block_time_mlp.1.weight [512 or 256][1024]   7 block_time_mlp.1.bias   8 c_mlp.1.weight [256][256]   9 c_mlp.1.bias (8, 9: cond head
+ *   only, ignored without cond)   10 class_logits.weight [c][256]   11 class_logits.bias   12 bboxes_delta.weight [4][256]   13 bboxes_delta.bias
+ *   14 + 3 l, 15 + 3 l, 16 + 3 l: tower layer l's Linear weight [256][256], LayerNorm weight and bias; the num_cls layers of cls_module first
+ *   (cls_module.{3 i, 3 i + 1}), then the num_reg layers of reg_module.
+ * Forward outputs logits_out [R][c], boxes_out [R][4], obj_out [R][256]: any of them may be null.  Cotangents d_logits, d_boxes, d_obj: null
+ * means zeros.  Gradient outputs d_x [R][256], d_time_emb [n][1024], d_cond [R][256] (with cond) and grads: every element is written.  With
+ * grads, d_x, d_time_emb and d_cond ALL null the call is the forward alone.
+ * Arithmetic: fp32 storage, fp32 products on v_mfma_f32_32x32x2_f32, fp32 accumulation -- not the split fp16 operands of the DTYPE float32
+ * inference path, whose low half is lost on a cotangent below fp16's normal range.  A sum over the R rows (weight, bias and LayerNorm
+ * gradients; over an image's m rows for d_time_emb) is formed in chunks of DVID_HEAD_TAIL_BWD_ROW_CHUNK rows whose partial results go to
+ * scratch and are added in ascending order: no atomics, two runs give the same bits.
+ * At the kinks the gradient is what torch's autograd gives on the host restatement, and this is part of the contract:
+ *   ReLU passes nothing at a pre-activation of exactly 0;
+ *   clamp(max = scale_clamp) passes the gradient at equality and nothing above it;
+ *   a row whose dw is clamped still gets its dx and dy gradients (and dh its own, unless clamped too);
+ *   a box of zero width gets exact zeros for the terms that multiply the width (likewise the height).
+ * Refused before any launch, with the numbers: hidden other than 256, dff not a positive multiple of DVID_HEAD_TAIL_BWD_TILE, c outside
+ * 1 .. DVID_MAX_CLASSES, num_cls / num_reg outside the forward's 0 .. 4, more than 65535 images or DVID_HEAD_TAIL_BWD_MAX_ROWS rows
+ * (DVID_ERR_UNSUPPORTED); n < 1 or m < 1, a wrong n_params, null pointers, a scratch smaller than dvid_head_tail_backward_scratch_bytes or
+ * not 16-byte aligned (DVID_ERR_ARG). */
+#define DVID_HEAD_TAIL_BWD_ROW_CHUNK 256
+#define DVID_HEAD_TAIL_BWD_TILE 64
+#define DVID_HEAD_TAIL_BWD_MAX_ROWS 1048576
+int dvid_head_tail_backward(const float* x, const float* boxes_in, const float* time_emb, const float* cond, int n, int m, int hidden, int dff,
+                            int num_classes, int num_cls, int num_reg, const float* const* params, int n_params, float wx, float wy, float ww, float wh,
+                            float scale_clamp, const float* d_logits, const float* d_boxes, const float* d_obj, float* logits_out, float* boxes_out,
+                            float* obj_out, float* d_x, float* d_time_emb, float* d_cond, float* const* grads, void* scratch, int64_t scratch_bytes,
+                            void* stream);
+int64_t dvid_head_tail_backward_scratch_bytes(int n, int m, int dff, int num_classes, int num_cls, int num_reg, int has_cond);
 
 /* ---- options ------------------------------------------------------------------------------
  * The library's behaviour switches are ONE table set through this ABI, never through the environment (csrc/options.h; the defaults
