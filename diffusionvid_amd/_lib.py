@@ -49,6 +49,8 @@ SIGNATURES = {
                                       c_void_p, C.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dvid_rcnn_head_levels_keep": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                            c_void_p, C.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dvid_rcnn_head_levels_keep2": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                            c_void_p, C.POINTER(c_int64)] + [c_void_p] * 9),
     "dvid_rcnn_head": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                c_void_p, C.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dvid_global_xattn": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
@@ -100,6 +102,8 @@ SIGNATURES = {
     "dvid_set_criterion_backward": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 5 + [c_float, c_float] + [c_void_p] * 6),
     "dvid_head_tail_backward": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p, c_int] + [c_float] * 5 + [c_void_p] * 11 + [c_int64, c_void_p]),
     "dvid_head_tail_backward_scratch_bytes": (c_int64, [c_int] * 7),
+    "dvid_inst_interact_backward": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_void_p, c_int] + [c_void_p] * 6 + [c_int64, c_void_p]),
+    "dvid_inst_interact_backward_scratch_bytes": (c_int64, [c_int]),
     "dvid_cdist":(c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "dvid_fps_greedy": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dvid_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -170,7 +170,8 @@ int rcnn_head_chain(dvid_model* m, const HeadW& hw, int is_cond, const void* con
 // The same pass with DTYPE float32 (the f32_* kernels of csrc/roialign.hip, attention.hip, dynconv.hip, elementwise.hip; csrc/f32.hip for the layers): fp32 RoI tiles, q / k / v, dynamic parameters, hidden layers; layer by layer.
 int rcnn_head_chain_f32(dvid_model* m, const HeadW& hw, int is_cond, const void* const* levels, int n_levels, int nf, int height, int width,
                         int M, const float* boxes, const float* pro_features, const float* cond, float* logits, float* boxes_out,
-                        float* obj_features, int* bad_box_flag, const float* ss_dev, int ss_stride, hipStream_t s, float* tail_input = nullptr) {
+                        float* obj_features, int* bad_box_flag, const float* ss_dev, int ss_stride, hipStream_t s, float* tail_input = nullptr, float* interact_input = nullptr,
+                        float* roi_tiles = nullptr) {
     const int d = m->cfg.hidden_dim, R = nf * M, dd = m->cfg.dim_dynamic;
     float* roi = m->roi.as<float>();
     float* dyn = m->dyn.as<float>();
@@ -202,6 +203,9 @@ int rcnn_head_chain_f32(dvid_model* m, const HeadW& hw, int is_cond, const void*
     TRY(linear_run32(hw.out_proj, attn, R, f32b, 0, s));
     float* x1 = f32c;
     TRY(dvid_add_layernorm_launch(pro, f32b, hw.norm1.g, hw.norm1.b, x1, nullptr, R, d, 0, s));
+    // the inputs of DynamicConv's backward (dvid_rcnn_head_levels_keep2): copies, as the tail's input below
+    if (interact_input) HIP_TRY(hipMemcpyAsync(interact_input, x1, (size_t)R * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (roi_tiles) HIP_TRY(hipMemcpyAsync(roi_tiles, roi, (size_t)R * 49 * d * sizeof(float), hipMemcpyDeviceToDevice, s));
     // --- DynamicConv (box_head.py:687-711)
     TRY(linear_run32(hw.dynamic_layer, x1, R, params, 0, s));
     TRY(prof_other("dynconv_f32", R, d, dd, 2.0 * R * 49.0 * d * dd * 2.0, (double)R * (2.0 * 49 * d * 4.0 + 2.0 * d * dd * 4.0), s,
@@ -338,17 +342,25 @@ int dvid_rcnn_head_levels(dvid_model* m, int head_index, int is_cond, const void
                           int height, int width, int boxes_per_frame, const float* boxes, const float* pro_features,
                           const int64_t* t, const float* cond, float* logits, float* boxes_out, float* obj_features,
                           int* bad_box_flag, void* stream) {
-    return dvid_rcnn_head_levels_keep(m, head_index, is_cond, levels, n_levels, n_frames, height, width, boxes_per_frame, boxes, pro_features, t, cond,
-                                      logits, boxes_out, obj_features, bad_box_flag, nullptr, stream);
+    return dvid_rcnn_head_levels_keep2(m, head_index, is_cond, levels, n_levels, n_frames, height, width, boxes_per_frame, boxes, pro_features, t, cond,
+                                       logits, boxes_out, obj_features, bad_box_flag, nullptr, nullptr, nullptr, stream);
 }
 
 int dvid_rcnn_head_levels_keep(dvid_model* m, int head_index, int is_cond, const void* const* levels, int n_levels, int n_frames,
                                int height, int width, int boxes_per_frame, const float* boxes, const float* pro_features,
                                const int64_t* t, const float* cond, float* logits, float* boxes_out, float* obj_features,
                                int* bad_box_flag, float* tail_input, void* stream) {
+    return dvid_rcnn_head_levels_keep2(m, head_index, is_cond, levels, n_levels, n_frames, height, width, boxes_per_frame, boxes, pro_features, t, cond,
+                                       logits, boxes_out, obj_features, bad_box_flag, tail_input, nullptr, nullptr, stream);
+}
+
+int dvid_rcnn_head_levels_keep2(dvid_model* m, int head_index, int is_cond, const void* const* levels, int n_levels, int n_frames,
+                                int height, int width, int boxes_per_frame, const float* boxes, const float* pro_features,
+                                const int64_t* t, const float* cond, float* logits, float* boxes_out, float* obj_features,
+                                int* bad_box_flag, float* tail_input, float* interact_input, float* roi_tiles, void* stream) {
     g_err[0] = 0;
     if (!m || !m->finalized) FAIL(DVID_ERR_STATE, "model not finalized");
-    if (tail_input && m->precision != 1)
+    if ((tail_input || interact_input || roi_tiles) && m->precision != 1)
         FAIL(DVID_ERR_UNSUPPORTED, "dvid_rcnn_head_levels_keep: the tail's input is kept for DTYPE float32 models only (fp16 gradients are out of scope)");
     if (!pyramid_ok(levels, n_levels)) FAIL(DVID_ERR_ARG, "the pyramid is 3 maps (p3..p5) or 4 (p2..p5), none of them null (got n_levels %d)", n_levels);
     if (m->has_backbone && n_levels != m->fpn_levels)
@@ -417,7 +429,7 @@ int dvid_rcnn_head_levels_keep(dvid_model* m, int head_index, int is_cond, const
     // measured slower -- 0.53 against 0.49 ms per pass, tools/bench_head.py -- the switch that kept that path is gone.)
     if (m->precision == 1)
         return rcnn_head_chain_f32(m, hw, is_cond, levels, n_levels, n_frames, height, width, M, boxes, pro_features, cond, logits, boxes_out, obj_features,
-                                   bad_box_flag, ss_dev, ss_stride, s, tail_input);
+                                   bad_box_flag, ss_dev, ss_stride, s, tail_input, interact_input, roi_tiles);
     return rcnn_head_chain(m, hw, is_cond, levels, n_levels, n_frames, height, width, M, boxes, pro_features, cond, logits, boxes_out, obj_features,
                            bad_box_flag, ss_dev, ss_stride, s);
 }

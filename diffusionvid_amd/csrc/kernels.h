@@ -194,6 +194,19 @@ struct HeadTailBwdArgs {
 long long dvid_head_tail_backward_scratch_bytes_host(int n, int m, int dff, int num_classes, int num_cls, int num_reg, int has_cond);
 int dvid_head_tail_backward_launch(const HeadTailBwdArgs& a, hipStream_t s);
 
+// interact_bwd.hip: the fp32 recompute of DynamicConv + norm2 and its backward (include/dvid_hip.h: dvid_inst_interact_backward)
+struct InstInteractBwdArgs {
+    const float *p, *roi;
+    long long rows;
+    const float* const* params;
+    const float* d_y;
+    float *y_out, *d_p, *d_roi;
+    float* const* grads;          // null: the forward only
+    void* scratch;
+};
+long long dvid_inst_interact_backward_scratch_bytes_host(long long rows);
+int dvid_inst_interact_backward_launch(const InstInteractBwdArgs& a, hipStream_t s);
+
 // boxes.hip
 int dvid_apply_deltas_launch(const float* deltas, int delta_ld, const float* boxes, float* out, int n, float wx, float wy, float ww,
                              float wh, float clamp, int* bad_flag, hipStream_t s);

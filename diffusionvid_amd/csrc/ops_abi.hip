@@ -442,6 +442,32 @@ int dvid_head_tail_backward(const float* x, const float* boxes_in, const float* 
     return DVID_OK;
 }
 
+int64_t dvid_inst_interact_backward_scratch_bytes(int rows) { return dvid_inst_interact_backward_scratch_bytes_host(rows); }
+
+int dvid_inst_interact_backward(const float* p, const float* roi, int rows, int hidden, int dim_dynamic, int pooler, const float* const* params,
+                                int n_params, const float* d_y, float* y_out, float* d_p, float* d_roi, float* const* grads, void* scratch,
+                                int64_t scratch_bytes, void* stream) {
+    g_err[0] = 0;
+    const char* what = "instance interaction backward";
+    if (hidden != 256) FAIL(DVID_ERR_UNSUPPORTED, "%s: hidden size %d, the kernels take 256", what, hidden);
+    if (dim_dynamic != 64) FAIL(DVID_ERR_UNSUPPORTED, "%s: dim_dynamic %d, the kernels take 64", what, dim_dynamic);
+    if (pooler != 7) FAIL(DVID_ERR_UNSUPPORTED, "%s: a %d x %d pooler, the kernels take 7 x 7", what, pooler, pooler);
+    if (rows < 1) FAIL(DVID_ERR_ARG, "%s: %d rows", what, rows);
+    if (rows > DVID_HEAD_TAIL_BWD_MAX_ROWS)
+        FAIL(DVID_ERR_UNSUPPORTED, "%s: %d rows, the limit is %d (DVID_HEAD_TAIL_BWD_MAX_ROWS)", what, rows, DVID_HEAD_TAIL_BWD_MAX_ROWS);
+    if (n_params != 12) FAIL(DVID_ERR_ARG, "%s: %d parameter pointers, the link has 12", what, n_params);
+    if (!p || !roi || !params || !scratch) FAIL(DVID_ERR_ARG, "%s: null pointer", what);
+    const bool backward = grads || d_p || d_roi;
+    if (backward && (!grads || !d_p)) FAIL(DVID_ERR_ARG, "%s: null pointer among the gradient outputs", what);
+    if (!backward && d_y) FAIL(DVID_ERR_ARG, "%s: a cotangent without gradient outputs", what);
+    for (int i = 0; i < n_params; ++i)
+        if (!params[i] || (backward && !grads[i])) FAIL(DVID_ERR_ARG, "%s: null pointer for parameter %d", what, i);
+    TRY(scratch_ok(what, scratch, scratch_bytes, dvid_inst_interact_backward_scratch_bytes_host(rows)));
+    InstInteractBwdArgs a{p, roi, rows, params, d_y, y_out, d_p, d_roi, backward ? grads : nullptr, scratch};
+    TRY(dvid_inst_interact_backward_launch(a, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
 // What dvid_coco_eval_match and dvid_lvis_eval_match check alike; `what` names the protocol, `pointers` is false when one the entry needs
 // is null, *max_gt gets the greatest box count of one image
 static int image_eval_args_ok(const char* what, bool pointers, int n_images, int cap, int num_classes, const int* gt_starts_host, int limit,

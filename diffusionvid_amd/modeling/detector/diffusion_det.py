@@ -434,7 +434,7 @@ class DiffusionDet(nn.Module):
         nothing is replayed from a hipGraph.  The video item dict is refused by name (not built)."""
         return self.objective.losses(images, targets, image_ids)
 
-    def loss_gradients(self, images, targets, image_ids=None, through="outputs"):
+    def loss_gradients(self, images, targets, image_ids=None, through="outputs", roi_gradients=False):
         """compute_losses and the first links of its backward pass: -> (losses, d_logits [S, n, M, C], d_boxes [S, n, M, 4]).  Inputs and
         refusals are compute_losses'; `losses` is compute_losses' dict; the two fp32 tensors, which stay on the device, are the gradient of
         the SUM of the weighted losses with respect to every kept head output (logits and absolute xyxy boxes as
@@ -451,10 +451,15 @@ class DiffusionDet(nn.Module):
                          next head's attention and DynamicConv is not built
           "d_tail_in"    [kept heads, n * M, 256] and "d_time_emb" [n, 1024] (summed over the kept heads): the hand-over to the next link,
                          with "tail_in", "boxes_in" and "time_emb", the tail inputs they belong to
-        Without DEEP_SUPERVISION only the last head's tail is differentiated.  Attention, DynamicConv, RoIAlign, the FPN, the backbone and
+        through="interact" (same refusals) returns all of that with the same bits and goes on through every kept head's instance interaction --
+        DynamicConv, its residual and norm2: box_head.interact, csrc/interact_bwd.hip.  It adds the twelve gradients inst_interact.* and norm2.*
+        per kept head ("param_grads" for the last head, "partial" for earlier ones, whose next head's path through pro_features is missing),
+          "d_interact_in"  [kept heads, n * M, 256], the cotangent of the norm1 output, for the self-attention link to come, with "interact_in"
+          "d_roi"          [kept heads, n * M, 49, 256], the cotangent of the RoI tiles "roi_tiles", only with roi_gradients=True
+        Without DEEP_SUPERVISION only the last head is differentiated.  Self-attention + norm1, RoIAlign, the FPN, the backbone and
         time_mlp have no backward.  A coefficient divides by the BATCH's matched count of its head output (the reference's denominators), so
         an image's gradient depends on the batch it is in; its loss sums do not."""
-        return self.objective.gradients(images, targets, image_ids, through)
+        return self.objective.gradients(images, targets, image_ids, through, roi_gradients)
 
     def _reset_video(self):
         self._ahead = {}

@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from ... import ops
+from ..roi_heads.box_head import interact as I
 from ..roi_heads.box_head import tail as T
 from ..roi_heads.box_head.loss import (LOSS_KEYS, HungarianMatcherDynamicK, SetCriterionDynamicK, check_limits, coef_from_counts,
                                        losses_from_sums)
@@ -73,16 +74,16 @@ class Objective:
             starts.append(starts[-1] + b.shape[0])
         return torch.cat(gt_abs), torch.cat(gt_norm), torch.cat(labels), torch.tensor(starts, dtype=torch.int32)
 
-    THROUGH = ("outputs", "tail")
+    THROUGH = ("outputs", "tail", "interact")
 
     def check_through(self, through):
         """what loss_gradients(through=...) refuses, each by name, before anything is built or launched"""
         if through not in self.THROUGH:
             raise ValueError("loss_gradients: through=%r is not one of %s" % (through, ", ".join(repr(v) for v in self.THROUGH)))
-        if through == "tail":
+        if through != "outputs":
             if self.det.dtype != "float32":
-                raise NotImplementedError("loss_gradients: through='tail' needs DTYPE float32, this model is %s (fp16 gradients are out of scope)"
-                                          % self.det.dtype)
+                raise NotImplementedError("loss_gradients: through=%r needs DTYPE float32, this model is %s (fp16 gradients are out of scope)"
+                                          % (through, self.det.dtype))
             T.check_dropout(self.det.cfg, "loss_gradients")
 
     def tail_params(self, head):
@@ -97,6 +98,36 @@ class Objective:
             cache[head] = {k[len(pfx):]: v.detach().to(det.device, torch.float32).contiguous() for k, v in det.state_dict().items()
                            if k.startswith(pfx) and k[len(pfx):].startswith(TAIL_PARAMS)}
         return cache[head]
+
+    def interact_params(self, head):
+        """{name without the prefix: fp32 device tensor} of head_series.<head>'s instance interaction and norm2, kept as tail_params keeps its own"""
+        det = self.det
+        eng = det._get_engine()
+        if getattr(self, "_interact_cache", (None,))[0] is not eng:
+            self._interact_cache = (eng, {})
+        cache = self._interact_cache[1]
+        if head not in cache:
+            pfx = "head.head_series.%d." % head
+            sd = det.state_dict()
+            cache[head] = {k: sd[pfx + k].detach().to(det.device, torch.float32).contiguous() for k in I.PARAM_NAMES}
+        return cache[head]
+
+    def interact_backward(self, kept_heads, out, interact_in, roi_tiles, roi_gradients):
+        """ops.inst_interact_backward for every kept head on the tail's d_tail_in -> the entries loss_gradients(through="interact") adds to
+        the tail's dict `out`.  An earlier head's d_tail_in lacks the next head's path through pro_features, so its twelve go to "partial"."""
+        out.update({"d_interact_in": [], "interact_in": interact_in, "roi_tiles": roi_tiles})
+        d_roi = []
+        for s, head in enumerate(kept_heads):
+            g = ops.inst_interact_backward(interact_in[s], roi_tiles[s], self.interact_params(head), d_y=out["d_tail_in"][s], want_d_roi=roi_gradients)
+            whole = "param_grads" if head == self.det.num_heads - 1 else "partial"
+            for k, v in g["param_grads"].items():
+                out[whole]["head.head_series.%d.%s" % (head, k)] = v
+            out["d_interact_in"].append(g["d_p"])
+            d_roi.append(g["d_roi"])
+        out["d_interact_in"] = torch.stack(out["d_interact_in"])
+        if roi_gradients:
+            out["d_roi"] = torch.stack(d_roi)
+        return out
 
     def time_embedding(self, steps):
         """time_mlp(t) [n, 4 d] in fp32 on the device (box_head.py:218-223: sinusoidal embedding, Linear, GELU, Linear); no backward"""
@@ -128,13 +159,14 @@ class Objective:
         out["d_tail_in"] = torch.stack(out["d_tail_in"])
         return out
 
-    def forward(self, images, targets, image_ids, gradients, through="outputs"):
+    def forward(self, images, targets, image_ids, gradients, through="outputs", roi_gradients=False):
         """The forward sums and gradients share -> (the device tuple of ops.set_criterion, None or (d_logits, d_boxes) of the sum of the
         weighted losses with respect to the kept head outputs, from ops.set_criterion_backward on the same stream; with through="tail" a
-        third entry, the dict of tail_backward)."""
+        third entry, the dict of tail_backward, which through="interact" extends by interact_backward's)."""
         det = self.det
         what = "loss_gradients" if gradients else "compute_losses"
-        tail = gradients and through == "tail"
+        tail = gradients and through in ("tail", "interact")
+        interact = gradients and through == "interact"
         if isinstance(images, dict):
             raise NotImplementedError("%s: the video item dict (cur / ref_l / ref_g) of the training protocol is not built; "
                                       "hand over a batch of still images" % what)
@@ -163,10 +195,16 @@ class Objective:
             canvas = imgs.tensors.to(dev, torch.float32).contiguous()
             x_boxes = ops.q_sample_boxes(up[1], starts, steps, det.sqrt_alphas_cumprod, det.sqrt_one_minus_alphas_cumprod, noise, placeholder,
                                          det.scale, sizes)
-            logits, boxes, tail_in, boxes_in = [], [], [], []
+            logits, boxes, tail_in, boxes_in, inter_in, tiles = [], [], [], [], [], []
             for a, b, feats in det.stills.chunks(canvas):
                 if tail:          # the same launches plus one copy per head: every head's tail input, and the boxes each head started from
-                    lg, bx, tx = det.head.plain_heads(feats, x_boxes[a:b].contiguous(), steps[a:b], intermediate=True, tail_inputs=True)
+                    if interact:          # and two more: the norm1 output and the RoI tiles
+                        lg, bx, tx, px, rx = det.head.plain_heads(feats, x_boxes[a:b].contiguous(), steps[a:b], intermediate=True, tail_inputs=True,
+                                                                  interact_inputs=True)
+                        inter_in.append(px.reshape(px.shape[0], b - a, -1, px.shape[-1]) if deep else px[-1:].reshape(1, b - a, -1, px.shape[-1]))
+                        tiles.append(rx.reshape(rx.shape[0], b - a, -1, *rx.shape[-2:]) if deep else rx[-1:].reshape(1, b - a, -1, *rx.shape[-2:]))
+                    else:
+                        lg, bx, tx = det.head.plain_heads(feats, x_boxes[a:b].contiguous(), steps[a:b], intermediate=True, tail_inputs=True)
                     bi = torch.cat((x_boxes[a:b][None], bx[:-1]))
                     tail_in.append(tx.reshape(tx.shape[0], b - a, -1, tx.shape[-1]) if deep else tx[-1:].reshape(1, b - a, -1, tx.shape[-1]))
                     boxes_in.append(bi if deep else bi[-1:])
@@ -190,8 +228,13 @@ class Objective:
                 return out, grads
             tail_in = torch.cat(tail_in, dim=1)
             kept = list(range(det.num_heads)) if deep else [det.num_heads - 1]
-            return out, grads, self.tail_backward(kept, tail_in.reshape(tail_in.shape[0], -1, tail_in.shape[-1]).contiguous(),
-                                                  torch.cat(boxes_in, dim=1).contiguous(), steps, grads[0], grads[1])
+            res = self.tail_backward(kept, tail_in.reshape(tail_in.shape[0], -1, tail_in.shape[-1]).contiguous(),
+                                     torch.cat(boxes_in, dim=1).contiguous(), steps, grads[0], grads[1])
+            if interact:
+                inter_in, tiles = torch.cat(inter_in, dim=1), torch.cat(tiles, dim=1)
+                res = self.interact_backward(kept, res, inter_in.reshape(inter_in.shape[0], -1, inter_in.shape[-1]).contiguous(),
+                                             tiles.reshape(tiles.shape[0], -1, *tiles.shape[-2:]).contiguous(), roi_gradients)
+            return out, grads, res
 
     def _weighted(self, sums):
         return {k: v * self.weights.get(k, 1.0) for k, v in losses_from_sums(sums).items()}
@@ -203,9 +246,9 @@ class Objective:
     def losses(self, images, targets, image_ids=None):
         return self._weighted(self.sums(images, targets, image_ids)[0])
 
-    def gradients(self, images, targets, image_ids=None, through="outputs"):
+    def gradients(self, images, targets, image_ids=None, through="outputs", roi_gradients=False):
         self.check_through(through)
-        res = self.forward(images, targets, image_ids, True, through)
+        res = self.forward(images, targets, image_ids, True, through, roi_gradients)
         out, grads = res[:2]
         losses = self._weighted(out[2].detach().to("cpu", torch.float64))
         if through == "outputs":

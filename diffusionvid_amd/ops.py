@@ -1120,12 +1120,17 @@ class Model:
         call(fn, self.handle, table, n, h, w, levels, len(outs), stream_ptr())
         return outs          # `keep` may die here: the stream-ordered caching allocator re-uses a frame's block only behind this stream's reads
 
-    def rcnn_head(self, head_index, feats_nhwc, height, width, boxes, pro_features, t, cond=None, bad_flag=None, keep_tail_input=False):
+    def rcnn_head(self, head_index, feats_nhwc, height, width, boxes, pro_features, t, cond=None, bad_flag=None, keep_tail_input=False,
+                  keep_interact_input=False):
         """One RCNNHead / RCNNHead_cond pass over the maps it is given, [p3, p4, p5] or [p2, p3, p4, p5].  boxes [n, M, 4]; pro_features
         [n*M, d] or None; t: int64 [n] (CPU).  keep_tail_input=True (DTYPE float32 models only): a fourth return value, the tail's input
-        -- the fp32 norm2 output [n*M, d] that head_tail_backward takes as x (dvid_rcnn_head_levels_keep); the other three keep their bits."""
+        -- the fp32 norm2 output [n*M, d] that head_tail_backward takes as x (dvid_rcnn_head_levels_keep); the other three keep their bits.
+        keep_interact_input=True (float32 models only): two more return values behind those, what inst_interact_backward takes as p and roi
+        -- the fp32 norm1 output [n*M, d] and the fp32 RoI tiles [n*M, 49, d] (dvid_rcnn_head_levels_keep2); the others keep their bits."""
         if keep_tail_input and self.precision != "float32":
             raise _lib.DvidError(f"rcnn_head: keep_tail_input needs a DTYPE float32 model, this one is {self.precision} (fp16 gradients are out of scope)")
+        if keep_interact_input and self.precision != "float32":
+            raise _lib.DvidError(f"rcnn_head: keep_interact_input needs a DTYPE float32 model, this one is {self.precision} (fp16 gradients are out of scope)")
         boxes = _cuda(boxes, torch.float32)
         n, M = boxes.shape[:2]
         dev = boxes.device
@@ -1144,6 +1149,13 @@ class Model:
         if cond is not None:
             cond = _cuda(cond, torch.float32)
         levels, nl = _pyramid(feats_nhwc, height, width, "rcnn_head")
+        if keep_interact_input:
+            tail_in = torch.empty((n * M, d), dtype=torch.float32, device=dev) if keep_tail_input else None
+            inter_in = torch.empty((n * M, d), dtype=torch.float32, device=dev)
+            tiles = torch.empty((n * M, 49, d), dtype=torch.float32, device=dev)
+            call("dvid_rcnn_head_levels_keep2", self.handle, head_index, int(cond is not None), levels, nl, n, height, width, M, ptr(boxes),
+                 ptr(pro_features), tp, ptr(cond), ptr(logits), ptr(boxes_out), ptr(obj), ptr(bad_flag), ptr(tail_in), ptr(inter_in), ptr(tiles), stream_ptr())
+            return (logits, boxes_out, obj) + ((tail_in,) if keep_tail_input else ()) + (inter_in, tiles)
         if keep_tail_input:
             tail_in = torch.empty((n * M, d), dtype=torch.float32, device=dev)
             call("dvid_rcnn_head_levels_keep", self.handle, head_index, int(cond is not None), levels, nl, n, height, width, M, ptr(boxes),
@@ -1344,6 +1356,56 @@ def head_tail_backward(x, boxes_in, time_emb, params, cond=None, d_logits=None, 
          len(names), *(float(w) for w in bbox_weights), float(T.SCALE_CLAMP if scale_clamp is None else scale_clamp), *(ptr(t) for t in cot),
          ptr(out["logits"]), ptr(out["boxes"]), ptr(out["obj"]), ptr(out.get("d_x")), ptr(out.get("d_time_emb")), ptr(out.get("d_cond")),
          None if gtable is None else C.cast(gtable, C.c_void_p), ptr(scratch), scratch.numel() * 4, stream_ptr())
+    return out
+
+
+INST_BWD_ROW_SLAB = 512          # DVID_INST_BWD_ROW_SLAB: the rows whose dynamic parameters and their gradient exist at a time
+
+
+def inst_interact_backward_scratch_bytes(R):
+    """bytes of scratch dvid_inst_interact_backward needs for R rows (-1: a row count it does not take)"""
+    return int(_lib.load().dvid_inst_interact_backward_scratch_bytes(int(R)))
+
+
+def inst_interact_backward(p, roi, params, d_y=None, forward_only=False, want_d_roi=True):
+    """An RCNNHead's DynamicConv with its residual and norm2 recomputed in fp32, and its gradient (dvid_inst_interact_backward,
+    csrc/interact_bwd.hip; box_head.interact states the function).  p [R, 256] (the norm1 output), roi [R, 49, 256] (the fp32 RoI tiles), fp32
+    on the device; params {name without the head's prefix: fp32 device tensor in the reference's layout}, the twelve of
+    box_head.interact.PARAM_NAMES.  Cotangent d_y [R, 256]: None means zeros.  Returns a dict: "y", and -- unless forward_only -- "d_p",
+    "d_roi" (None with want_d_roi=False: it is then not computed, every other output keeps its bits) and "param_grads" {name: gradient},
+    every element written.  include/dvid_hip.h states the arithmetic (fp32 MFMA products, fixed-order sums without atomics: two runs give the
+    same bits)."""
+    from .modeling.roi_heads.box_head.interact import PARAM_NAMES
+    p, roi = _cuda(p, torch.float32), _cuda(roi, torch.float32)
+    assert p.dim() == 2 and roi.dim() == 3 and roi.shape[0] == p.shape[0] and roi.shape[2] == p.shape[1], "p is [R, d], roi [R, bins, d]"
+    R, d = p.shape
+    bins = roi.shape[1]
+    pooler = int(round(bins ** 0.5))
+    assert pooler * pooler == bins, "roi holds the bins of a square pooler"
+    plist = [_cuda(params[k].detach(), torch.float32) for k in PARAM_NAMES]
+    dd = plist[4].shape[0]
+    want = ((2 * d * dd, d), (2 * d * dd,), (d, bins * d), (d,), (dd,), (dd,), (d,), (d,), (d,), (d,), (d,), (d,))
+    for k, t, shape in zip(PARAM_NAMES, plist, want):
+        assert tuple(t.shape) == shape, "%s is %s, expected %s" % (k, tuple(t.shape), shape)
+    dev = p.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = {"y": new(R, d)}
+    d_y = None if d_y is None else _cuda(d_y, torch.float32)
+    assert d_y is None or tuple(d_y.shape) == (R, d), "the cotangent has y's shape"
+    glist = []
+    if forward_only:
+        assert d_y is None, "a cotangent without a backward"
+    else:
+        out.update({"d_p": new(R, d), "d_roi": new(R, bins, d) if want_d_roi else None})
+        glist = [torch.empty_like(t) for t in plist]
+        out["param_grads"] = dict(zip(PARAM_NAMES, glist))
+    table = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+    ptable = table(plist)
+    gtable = table(glist) if glist else None
+    nbytes = inst_interact_backward_scratch_bytes(R)
+    scratch = torch.empty((max(nbytes, 16) + 15) // 16 * 4, dtype=torch.float32, device=dev)
+    call("dvid_inst_interact_backward", ptr(p), ptr(roi), R, d, dd, pooler, C.cast(ptable, C.c_void_p), len(plist), ptr(d_y), ptr(out["y"]),
+         ptr(out.get("d_p")), ptr(out.get("d_roi")), None if gtable is None else C.cast(gtable, C.c_void_p), ptr(scratch), scratch.numel() * 4, stream_ptr())
     return out
 
 

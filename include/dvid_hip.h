@@ -173,6 +173,14 @@ int dvid_rcnn_head_levels_keep(dvid_model* m, int head_index, int is_cond, const
                                int height, int width, int boxes_per_frame, const float* boxes, const float* pro_features,
                                const int64_t* t, const float* cond, float* logits, float* boxes_out, float* obj_features,
                                int* bad_box_flag, float* tail_input, void* stream);
+/* dvid_rcnn_head_levels_keep2 (dvid_version >= 15): dvid_rcnn_head_levels_keep with two more nullable outputs, the inputs of
+ * dvid_inst_interact_backward: interact_input [n_frames * boxes_per_frame][256], the fp32 norm1 output, and roi_tiles
+ * [n_frames * boxes_per_frame][49][256], the fp32 RoI tiles.  Each is one device-to-device copy; with both null the call is exactly
+ * dvid_rcnn_head_levels_keep, and every other output keeps its bits.  A float16 model is refused when any of the three is asked for. */
+int dvid_rcnn_head_levels_keep2(dvid_model* m, int head_index, int is_cond, const void* const* levels, int n_levels, int n_frames,
+                                int height, int width, int boxes_per_frame, const float* boxes, const float* pro_features,
+                                const int64_t* t, const float* cond, float* logits, float* boxes_out, float* obj_features,
+                                int* bad_box_flag, float* tail_input, float* interact_input, float* roi_tiles, void* stream);
 
 /* cond[R,hidden] = MHA(query = obj_features[R,hidden], key = value = memory[lk,hidden]).  memory == NULL: use the K/V
  * projections kept by the last dvid_global_memory_project (lk 0 or the same row count). */
@@ -724,6 +732,36 @@ int dvid_head_tail_backward(const float* x, const float* boxes_in, const float* 
                             float* obj_out, float* d_x, float* d_time_emb, float* d_cond, float* const* grads, void* scratch, int64_t scratch_bytes,
                             void* stream);
 int64_t dvid_head_tail_backward_scratch_bytes(int n, int m, int dff, int num_classes, int num_cls, int num_reg, int has_cond);
+
+/* ---- the backward of the head's instance interaction (dvid_version >= 15; csrc/interact_bwd.hip) ----
+ * dvid_inst_interact_backward (dvid_version >= 15): an RCNNHead's DynamicConv (box_head.py:666-711) with its residual and norm2
+ * (box_head.py:521-524) recomputed in fp32, and its gradient: the link in front of dvid_head_tail_backward, whose x is this function's y.  The
+ * host mirror is modeling/roi_heads/box_head/interact.py (inst_interact_host).  The function: p [rows][256] is the norm1 output, rows image-major;
+ * roi [rows][49][256] the fp32 RoI tiles, bin-major as dvid_roialign_v2_levels_f32 writes them;
+ *   params = dynamic_layer(p)   [rows][32768], param1 = [:16384] as [256][64], param2 = [16384:] as [64][256]
+ *   F1 = ReLU(LN64(roi . param1))   F2 = ReLU(LN256(F1 . param2))   o = ReLU(LN256(out_layer(F2 flattened bin * 256 + c)))   y = norm2(p + o)
+ * dropout being the identity.  `params` is a HOST table of n_params = 12 device pointers, fp32 in the reference's names and row-major layouts
+ * (NOT the inference runtime's repacked dynamic_layer order), and `grads` a host table of the same length and shapes:
+ *   0 inst_interact.dynamic_layer.weight [32768][256]   1 inst_interact.dynamic_layer.bias [32768]
+ *   2 inst_interact.out_layer.weight [256][12544]       3 inst_interact.out_layer.bias [256]
+ *   4, 5 inst_interact.norm1.weight, .bias [64]         6, 7 inst_interact.norm2.weight, .bias [256]
+ *   8, 9 inst_interact.norm3.weight, .bias [256]        10, 11 norm2.weight, .bias [256]
+ * Forward output y_out [rows][256] (may be null).  Cotangent d_y [rows][256]: null means zeros.  Gradient outputs d_p [rows][256], d_roi
+ * [rows][49][256] (may be null, then it is not written) and grads: every element is written.  With d_p, d_roi and grads ALL null the call is
+ * the forward alone.
+ * Arithmetic and order of summation as dvid_head_tail_backward: fp32 products on v_mfma_f32_32x32x2_f32, no atomics, sums over rows in chunks
+ * of DVID_HEAD_TAIL_BWD_ROW_CHUNK added in ascending order, two runs give the same bits.  A box's dynamic parameters and their gradient (128 KiB
+ * each) exist for DVID_INST_BWD_ROW_SLAB rows at a time; of the scratch only the kept F2 and its cotangent ([rows][49][256] each) and a few
+ * [rows][256] terms grow with rows.  ReLU passes nothing at a pre-activation of exactly 0.
+ * Refused before any launch, with the numbers: hidden other than 256, dim_dynamic other than 64, a pooler other than 7 (7 x 7 bins), rows
+ * above DVID_HEAD_TAIL_BWD_MAX_ROWS (DVID_ERR_UNSUPPORTED); rows < 1, n_params other than 12, null pointers, d_roi or a cotangent without
+ * d_p and grads, a scratch smaller than dvid_inst_interact_backward_scratch_bytes or not 16-byte aligned (DVID_ERR_ARG). */
+#define DVID_INST_BWD_ROW_SLAB 512
+int dvid_inst_interact_backward(const float* p, const float* roi, int rows, int hidden, int dim_dynamic, int pooler, const float* const* params,
+                                int n_params, const float* d_y, float* y_out, float* d_p, float* d_roi, float* const* grads, void* scratch,
+                                int64_t scratch_bytes, void* stream);
+/* bytes of scratch for `rows` rows; -1 for a row count the entry refuses */
+int64_t dvid_inst_interact_backward_scratch_bytes(int rows);
 
 /* ---- options ------------------------------------------------------------------------------
  * The library's behaviour switches are ONE table set through this ABI, never through the environment (csrc/options.h; the defaults
