@@ -104,6 +104,8 @@ SIGNATURES = {
     "dvid_head_tail_backward_scratch_bytes": (c_int64, [c_int] * 7),
     "dvid_inst_interact_backward": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_void_p, c_int] + [c_void_p] * 6 + [c_int64, c_void_p]),
     "dvid_inst_interact_backward_scratch_bytes": (c_int64, [c_int]),
+    "dvid_self_attn_backward": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_int] + [c_void_p] * 5 + [c_int64, c_void_p]),
+    "dvid_self_attn_backward_scratch_bytes": (c_int64, [c_int, c_int]),
     "dvid_cdist":(c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "dvid_fps_greedy": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dvid_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

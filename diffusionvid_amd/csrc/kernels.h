@@ -207,6 +207,19 @@ struct InstInteractBwdArgs {
 long long dvid_inst_interact_backward_scratch_bytes_host(long long rows);
 int dvid_inst_interact_backward_launch(const InstInteractBwdArgs& a, hipStream_t s);
 
+// selfattn_bwd.hip: the fp32 recompute of self-attention + norm1 and its backward (include/dvid_hip.h: dvid_self_attn_backward)
+struct SelfAttnBwdArgs {
+    const float* x;
+    int n, m;
+    const float* const* params;
+    const float* d_y;
+    float *y_out, *d_x;
+    float* const* grads;          // null: the forward only
+    void* scratch;
+};
+long long dvid_self_attn_backward_scratch_bytes_host(long long n, long long m);
+int dvid_self_attn_backward_launch(const SelfAttnBwdArgs& a, hipStream_t s);
+
 // boxes.hip
 int dvid_apply_deltas_launch(const float* deltas, int delta_ld, const float* boxes, float* out, int n, float wx, float wy, float ww,
                              float wh, float clamp, int* bad_flag, hipStream_t s);

@@ -108,7 +108,7 @@ int linear_run32(const ConvW& w, const float* in, int rows, float* out, int relu
 
 extern "C" {
 const char* dvid_last_error(void) { return g_err; }
-int dvid_version(void) { return 15; }
+int dvid_version(void) { return 16; }
 
 int dvid_model_create(const dvid_config* cfg, dvid_model** out) {
     g_err[0] = 0;

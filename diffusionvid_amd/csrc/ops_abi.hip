@@ -468,6 +468,32 @@ int dvid_inst_interact_backward(const float* p, const float* roi, int rows, int 
     return DVID_OK;
 }
 
+int64_t dvid_self_attn_backward_scratch_bytes(int n, int m) { return dvid_self_attn_backward_scratch_bytes_host(n, m); }
+
+int dvid_self_attn_backward(const float* x, int n, int m, int hidden, int nheads, const float* const* params, int n_params, const float* d_y,
+                            float* y_out, float* d_x, float* const* grads, void* scratch, int64_t scratch_bytes, void* stream) {
+    g_err[0] = 0;
+    const char* what = "self-attention backward";
+    if (hidden != 256) FAIL(DVID_ERR_UNSUPPORTED, "%s: hidden size %d, the kernels take 256", what, hidden);
+    if (nheads != 8) FAIL(DVID_ERR_UNSUPPORTED, "%s: %d heads, the kernels take 8 of 32", what, nheads);
+    if (n < 1 || m < 1) FAIL(DVID_ERR_ARG, "%s: %d images of %d rows", what, n, m);
+    if (m > DVID_CRITERION_MAX_ROWS) FAIL(DVID_ERR_UNSUPPORTED, "%s: %d rows per image, the limit is %d (DVID_CRITERION_MAX_ROWS)", what, m, DVID_CRITERION_MAX_ROWS);
+    if ((long long)n * m > DVID_HEAD_TAIL_BWD_MAX_ROWS)
+        FAIL(DVID_ERR_UNSUPPORTED, "%s: %lld rows, the limit is %d (DVID_HEAD_TAIL_BWD_MAX_ROWS)", what, (long long)n * m, DVID_HEAD_TAIL_BWD_MAX_ROWS);
+    if (n > 65535) FAIL(DVID_ERR_UNSUPPORTED, "%s: %d images, the limit is 65535", what, n);
+    if (n_params != 6) FAIL(DVID_ERR_ARG, "%s: %d parameter pointers, the link has 6", what, n_params);
+    if (!x || !params || !scratch) FAIL(DVID_ERR_ARG, "%s: null pointer", what);
+    const bool backward = grads || d_x;
+    if (backward && (!grads || !d_x)) FAIL(DVID_ERR_ARG, "%s: null pointer among the gradient outputs", what);
+    if (!backward && d_y) FAIL(DVID_ERR_ARG, "%s: a cotangent without gradient outputs", what);
+    for (int i = 0; i < n_params; ++i)
+        if (!params[i] || (backward && !grads[i])) FAIL(DVID_ERR_ARG, "%s: null pointer for parameter %d", what, i);
+    TRY(scratch_ok(what, scratch, scratch_bytes, dvid_self_attn_backward_scratch_bytes_host(n, m)));
+    SelfAttnBwdArgs a{x, n, m, params, d_y, y_out, d_x, backward ? grads : nullptr, scratch};
+    TRY(dvid_self_attn_backward_launch(a, reinterpret_cast<hipStream_t>(stream)));
+    return DVID_OK;
+}
+
 // What dvid_coco_eval_match and dvid_lvis_eval_match check alike; `what` names the protocol, `pointers` is false when one the entry needs
 // is null, *max_gt gets the greatest box count of one image
 static int image_eval_args_ok(const char* what, bool pointers, int n_images, int cap, int num_classes, const int* gt_starts_host, int limit,

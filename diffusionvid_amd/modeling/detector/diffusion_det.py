@@ -457,9 +457,27 @@ class DiffusionDet(nn.Module):
           "d_interact_in"  [kept heads, n * M, 256], the cotangent of the norm1 output, for the self-attention link to come, with "interact_in"
           "d_roi"          [kept heads, n * M, 49, 256], the cotangent of the RoI tiles "roi_tiles", only with roi_gradients=True
         Without DEEP_SUPERVISION only the last head is differentiated.  Self-attention + norm1, RoIAlign, the FPN, the backbone and
-        time_mlp have no backward.  A coefficient divides by the BATCH's matched count of its head output (the reference's denominators), so
+        time_mlp have no backward HERE: head_gradients crosses self-attention + norm1, joins the heads and returns the whole gradient of every
+        head parameter.  A coefficient divides by the BATCH's matched count of its head output (the reference's denominators), so
         an image's gradient depends on the batch it is in; its loss sums do not."""
         return self.objective.gradients(images, targets, image_ids, through, roi_gradients)
+
+    def head_gradients(self, images, targets, image_ids=None, roi_gradients=False):
+        """The complete gradient of the sum of the weighted losses with respect to EVERY parameter of the detection head.  Inputs are
+        compute_losses'; refusals are loss_gradients(through="interact")'s (DTYPE float32, DROPOUT 0.0, the video item dict, USE_FED_LOSS),
+        each by key.  The forward is the one loss_gradients(through="interact") runs, with the inputs of all NUM_HEADS heads kept, with or
+        without DEEP_SUPERVISION.  The backward walks the heads from the last to the first: the tail (its own d_logits / d_boxes -- null for
+        a head without a loss of its own -- and, as d_obj, the cotangent the NEXT head's self-attention hands back), the instance
+        interaction, self-attention + norm1 (box_head.attention, csrc/selfattn_bwd.hip).  The reference detaches the boxes between heads, so
+        pro_features is the only path from a head to the next, and the first head's is the mean over the bins of its RoI tiles.  -> a dict:
+          "losses", "d_logits", "d_boxes"  as loss_gradients returns them
+          "param_grads"  {state-dict name: gradient} for every key under head.head_series. and head.time_mlp., fp32 on the device in the
+                         parameter's shape; no "partial".  Without DEEP_SUPERVISION the earlier heads' class_logits, bboxes_delta, towers
+                         and block_time_mlp get exact zeros.  time_mlp's four come from torch's autograd on the summed d_time_emb (n rows)
+          with roi_gradients=True: "d_roi" [NUM_HEADS, n * M, 49, 256], the cotangent of every head's RoI tiles (head 0's includes the
+                         share of the mean), with "roi_tiles" and "boxes_in" [NUM_HEADS, n, M, 4]: the hand-over to the RoIAlign backward to come
+        The gradient stops at the RoI tiles: RoIAlign, the FPN and the backbone have no backward."""
+        return self.objective.head_gradients(images, targets, image_ids, roi_gradients)
 
     def _reset_video(self):
         self._ahead = {}

@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from ... import ops
+from ..roi_heads.box_head import attention as A
 from ..roi_heads.box_head import interact as I
 from ..roi_heads.box_head import tail as T
 from ..roi_heads.box_head.loss import (LOSS_KEYS, HungarianMatcherDynamicK, SetCriterionDynamicK, check_limits, coef_from_counts,
@@ -112,6 +113,66 @@ class Objective:
             cache[head] = {k: sd[pfx + k].detach().to(det.device, torch.float32).contiguous() for k in I.PARAM_NAMES}
         return cache[head]
 
+    def attn_params(self, head):
+        """{name without the prefix: fp32 device tensor} of head_series.<head>'s self-attention and norm1, kept as tail_params keeps its own"""
+        det = self.det
+        eng = det._get_engine()
+        if getattr(self, "_attn_cache", (None,))[0] is not eng:
+            self._attn_cache = (eng, {})
+        cache = self._attn_cache[1]
+        if head not in cache:
+            pfx = "head.head_series.%d." % head
+            sd = det.state_dict()
+            cache[head] = {k: sd[pfx + k].detach().to(det.device, torch.float32).contiguous() for k in A.PARAM_NAMES}
+        return cache[head]
+
+    def check_chain(self):
+        """what head_gradients refuses, each by name, before anything is built or launched: check_through("interact")'s conditions"""
+        if self.det.dtype != "float32":
+            raise NotImplementedError("head_gradients: needs DTYPE float32, this model is %s (fp16 gradients are out of scope)" % self.det.dtype)
+        T.check_dropout(self.det.cfg, "head_gradients")
+
+    def chain_backward(self, tail_in, boxes_in, interact_in, roi_tiles, obj, steps, d_logits, d_boxes, roi_gradients):
+        """The backward over ALL heads, from the last to the first: per head ops.head_tail_backward (the head's own d_logits / d_boxes, null
+        for a head without a loss of its own, and d_obj = the next head's d_attn_in), ops.inst_interact_backward, ops.self_attn_backward.
+        A head's x is the previous head's obj_features (`obj`), the first head's the mean over the bins of its RoI tiles, whose share
+        d_attn_in[0] / 49 is added to every bin of d_roi[0].  time_mlp's four gradients: torch's autograd through time_embedding's arithmetic
+        with the summed d_time_emb.  tail_in / interact_in / obj [H, R, d], roi_tiles [H, R, 49, d], boxes_in [H, n, M, 4]; d_logits /
+        d_boxes [S, n, M, .] with S = H (DEEP_SUPERVISION) or 1 (the last head's).  -> {"param_grads"} and, with roi_gradients, "d_roi"."""
+        H, R = tail_in.shape[:2]
+        n = steps.numel()
+        S = d_logits.shape[0]
+        time_emb = self.time_embedding(steps)
+        grads, d_time_emb, d_attn_in, d_roi = {}, torch.zeros_like(time_emb), None, [None] * H
+        for h in reversed(range(H)):
+            s = h - (H - S)          # the head's own output among the kept ones
+            own = (d_logits[s].reshape(R, -1), d_boxes[s].reshape(R, 4)) if s >= 0 else (None, None)
+            t = ops.head_tail_backward(tail_in[h], boxes_in[h].reshape(R, 4), time_emb, self.tail_params(h), d_logits=own[0], d_boxes=own[1], d_obj=d_attn_in)
+            i = ops.inst_interact_backward(interact_in[h], roi_tiles[h], self.interact_params(h), d_y=t["d_x"], want_d_roi=roi_gradients)
+            x = obj[h - 1] if h > 0 else roi_tiles[0].mean(1)
+            a = ops.self_attn_backward(x, n, self.attn_params(h), d_y=i["d_p"])
+            for part in (t, i, a):
+                grads.update({"head.head_series.%d.%s" % (h, k): v for k, v in part["param_grads"].items()})
+            d_time_emb += t["d_time_emb"]
+            d_attn_in, d_roi[h] = a["d_x"], i["d_roi"]
+        grads.update(self.time_mlp_gradients(steps, d_time_emb))
+        out = {"param_grads": grads}
+        if roi_gradients:
+            d_roi[0] = d_roi[0] + (d_attn_in / roi_tiles.shape[2])[:, None, :]
+            out["d_roi"] = torch.stack(d_roi)
+        return out
+
+    def time_mlp_gradients(self, steps, d_time_emb):
+        """{"head.time_mlp.<1|3>.<weight|bias>": gradient} of sum(d_time_emb * time_mlp(t)): torch's autograd through time_embedding's own
+        arithmetic on the device -- n rows, plumbing"""
+        names = ["head.time_mlp." + k for k in ("1.weight", "1.bias", "3.weight", "3.bias")]
+        sd = self.det.state_dict()
+        with torch.enable_grad():
+            w = {k: sd[k].detach().to(self.det.device, torch.float32).requires_grad_(True) for k in names}
+            emb = self.time_embedding(steps, {k[len("head.time_mlp."):]: v for k, v in w.items()})
+            got = torch.autograd.grad(emb, [w[k] for k in names], d_time_emb)
+        return dict(zip(names, got))
+
     def interact_backward(self, kept_heads, out, interact_in, roi_tiles, roi_gradients):
         """ops.inst_interact_backward for every kept head on the tail's d_tail_in -> the entries loss_gradients(through="interact") adds to
         the tail's dict `out`.  An earlier head's d_tail_in lacks the next head's path through pro_features, so its twelve go to "partial"."""
@@ -129,8 +190,9 @@ class Objective:
             out["d_roi"] = torch.stack(d_roi)
         return out
 
-    def time_embedding(self, steps):
-        """time_mlp(t) [n, 4 d] in fp32 on the device (box_head.py:218-223: sinusoidal embedding, Linear, GELU, Linear); no backward"""
+    def time_embedding(self, steps, weights=None):
+        """time_mlp(t) [n, 4 d] in fp32 on the device (box_head.py:218-223: sinusoidal embedding, Linear, GELU, Linear); `weights`
+        {"1.weight", ...}: those tensors instead of the state dict's (time_mlp_gradients differentiates through them)"""
         det = self.det
         sd = det.state_dict()
         d = det.cfg.MODEL.DiffusionDet.HIDDEN_DIM
@@ -138,7 +200,7 @@ class Objective:
         freq = torch.exp(torch.arange(half, dtype=torch.float32) * -(math.log(10000.0) / (half - 1)))
         arg = steps.to(torch.float32)[:, None] * freq[None, :]
         emb = torch.cat((arg.sin(), arg.cos()), dim=-1).to(det.device)
-        w = lambda k: sd["head.time_mlp." + k].detach().to(det.device, torch.float32)
+        w = lambda k: sd["head.time_mlp." + k].detach().to(det.device, torch.float32) if weights is None else weights[k]
         return F.linear(F.gelu(F.linear(emb, w("1.weight"), w("1.bias"))), w("3.weight"), w("3.bias")).contiguous()
 
     def tail_backward(self, kept_heads, tail_in, boxes_in, steps, d_logits, d_boxes):
@@ -159,12 +221,14 @@ class Objective:
         out["d_tail_in"] = torch.stack(out["d_tail_in"])
         return out
 
-    def forward(self, images, targets, image_ids, gradients, through="outputs", roi_gradients=False):
+    def forward(self, images, targets, image_ids, gradients, through="outputs", roi_gradients=False, chain=False):
         """The forward sums and gradients share -> (the device tuple of ops.set_criterion, None or (d_logits, d_boxes) of the sum of the
         weighted losses with respect to the kept head outputs, from ops.set_criterion_backward on the same stream; with through="tail" a
-        third entry, the dict of tail_backward, which through="interact" extends by interact_backward's)."""
+        third entry, the dict of tail_backward, which through="interact" extends by interact_backward's).  chain=True (head_gradients; with
+        through="interact"): the same forward, the inputs of ALL heads kept with or without DEEP_SUPERVISION and every head's obj_features;
+        the third entry is then chain_backward's dict with "roi_tiles" and "boxes_in"."""
         det = self.det
-        what = "loss_gradients" if gradients else "compute_losses"
+        what = "head_gradients" if chain else "loss_gradients" if gradients else "compute_losses"
         tail = gradients and through in ("tail", "interact")
         interact = gradients and through == "interact"
         if isinstance(images, dict):
@@ -183,6 +247,7 @@ class Objective:
         check_limits(det.num_proposals, det.num_classes, criterion.matcher.ota_k, (starts[1:] - starts[:-1]).tolist())
         steps = torch.tensor([self.train_step(i) for i in ids], dtype=torch.int64)
         deep = det.cfg.MODEL.DiffusionDet.DEEP_SUPERVISION
+        keep_all = deep or chain          # every head's inputs, or the last head's
         with torch.no_grad(), det._on_device():
             dev = det.device
             # every upload and draw before any kernel is queued (the rule of StillImages.detect)
@@ -195,19 +260,21 @@ class Objective:
             canvas = imgs.tensors.to(dev, torch.float32).contiguous()
             x_boxes = ops.q_sample_boxes(up[1], starts, steps, det.sqrt_alphas_cumprod, det.sqrt_one_minus_alphas_cumprod, noise, placeholder,
                                          det.scale, sizes)
-            logits, boxes, tail_in, boxes_in, inter_in, tiles = [], [], [], [], [], []
+            logits, boxes, tail_in, boxes_in, inter_in, tiles, objs = [], [], [], [], [], [], []
             for a, b, feats in det.stills.chunks(canvas):
                 if tail:          # the same launches plus one copy per head: every head's tail input, and the boxes each head started from
                     if interact:          # and two more: the norm1 output and the RoI tiles
-                        lg, bx, tx, px, rx = det.head.plain_heads(feats, x_boxes[a:b].contiguous(), steps[a:b], intermediate=True, tail_inputs=True,
-                                                                  interact_inputs=True)
-                        inter_in.append(px.reshape(px.shape[0], b - a, -1, px.shape[-1]) if deep else px[-1:].reshape(1, b - a, -1, px.shape[-1]))
-                        tiles.append(rx.reshape(rx.shape[0], b - a, -1, *rx.shape[-2:]) if deep else rx[-1:].reshape(1, b - a, -1, *rx.shape[-2:]))
+                        lg, bx, tx, px, rx, *ox = det.head.plain_heads(feats, x_boxes[a:b].contiguous(), steps[a:b], intermediate=True, tail_inputs=True,
+                                                                       interact_inputs=True, obj_features=chain)
+                        inter_in.append(px.reshape(px.shape[0], b - a, -1, px.shape[-1]) if keep_all else px[-1:].reshape(1, b - a, -1, px.shape[-1]))
+                        tiles.append(rx.reshape(rx.shape[0], b - a, -1, *rx.shape[-2:]) if keep_all else rx[-1:].reshape(1, b - a, -1, *rx.shape[-2:]))
+                        if chain:
+                            objs.append(ox[0].reshape(ox[0].shape[0], b - a, -1, ox[0].shape[-1]))
                     else:
                         lg, bx, tx = det.head.plain_heads(feats, x_boxes[a:b].contiguous(), steps[a:b], intermediate=True, tail_inputs=True)
                     bi = torch.cat((x_boxes[a:b][None], bx[:-1]))
-                    tail_in.append(tx.reshape(tx.shape[0], b - a, -1, tx.shape[-1]) if deep else tx[-1:].reshape(1, b - a, -1, tx.shape[-1]))
-                    boxes_in.append(bi if deep else bi[-1:])
+                    tail_in.append(tx.reshape(tx.shape[0], b - a, -1, tx.shape[-1]) if keep_all else tx[-1:].reshape(1, b - a, -1, tx.shape[-1]))
+                    boxes_in.append(bi if keep_all else bi[-1:])
                 else:
                     lg, bx = det.head.plain_heads(feats, x_boxes[a:b].contiguous(), steps[a:b], intermediate=True)
                 if not deep:
@@ -227,6 +294,11 @@ class Objective:
             if not tail:
                 return out, grads
             tail_in = torch.cat(tail_in, dim=1)
+            if chain:
+                rows = lambda ts: (lambda t: t.reshape(t.shape[0], -1, *t.shape[3:]).contiguous())(torch.cat(ts, dim=1))
+                boxes_in, tiles = torch.cat(boxes_in, dim=1).contiguous(), rows(tiles)
+                res = self.chain_backward(rows([tail_in]), boxes_in, rows(inter_in), tiles, rows(objs), steps, grads[0], grads[1], roi_gradients)
+                return out, grads, dict(res, roi_tiles=tiles, boxes_in=boxes_in)
             kept = list(range(det.num_heads)) if deep else [det.num_heads - 1]
             res = self.tail_backward(kept, tail_in.reshape(tail_in.shape[0], -1, tail_in.shape[-1]).contiguous(),
                                      torch.cat(boxes_in, dim=1).contiguous(), steps, grads[0], grads[1])
@@ -245,6 +317,12 @@ class Objective:
 
     def losses(self, images, targets, image_ids=None):
         return self._weighted(self.sums(images, targets, image_ids)[0])
+
+    def head_gradients(self, images, targets, image_ids=None, roi_gradients=False):
+        self.check_chain()
+        out, grads, res = self.forward(images, targets, image_ids, True, "interact", roi_gradients, chain=True)
+        keep = ("param_grads", "d_roi", "roi_tiles", "boxes_in") if roi_gradients else ("param_grads",)
+        return dict({k: res[k] for k in keep}, losses=self._weighted(out[2].detach().to("cpu", torch.float64)), d_logits=grads[0], d_boxes=grads[1])
 
     def gradients(self, images, targets, image_ids=None, through="outputs", roi_gradients=False):
         self.check_through(through)

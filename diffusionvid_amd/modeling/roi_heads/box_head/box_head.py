@@ -143,7 +143,7 @@ class DynamicHead(nn.Module):
                                                                       cond=attn_, bad_flag=flag)
         return class_logits2[None], bboxes2[None]
 
-    def plain_heads(self, features, init_bboxes, t, intermediate=False, tail_inputs=False, interact_inputs=False):
+    def plain_heads(self, features, init_bboxes, t, intermediate=False, tail_inputs=False, interact_inputs=False, obj_features=False):
         """The NUM_HEADS RCNNHeads on `init_bboxes` and nothing else -> (class_logits [B, M, C], bboxes [B, M, 4]): what forward computes for
         a model without attention, with no cache popped or filled and no memory read (the detector's still-image path).
         intermediate=True: every head's output, stacked -> (class_logits [NUM_HEADS, B, M, C], bboxes [NUM_HEADS, B, M, 4]), the last one
@@ -151,7 +151,9 @@ class DynamicHead(nn.Module):
         models only): one more return value, every head's tail input -- its fp32 norm2 output, what box_head.tail.head_tail takes as x --
         stacked [NUM_HEADS, B * M, d]; the other values keep their bits.  interact_inputs=True (float32 models only): two more behind
         those, what box_head.interact.inst_interact takes as p and roi -- every head's fp32 norm1 output [NUM_HEADS, B * M, d] and its fp32
-        RoI tiles [NUM_HEADS, B * M, 49, d]; the other values keep their bits."""
+        RoI tiles [NUM_HEADS, B * M, 49, d]; the other values keep their bits.  obj_features=True: one more behind everything else,
+        every head's obj_features stacked [NUM_HEADS, B * M, d] -- head h + 1 takes head h's as its pro_features, the x of
+        box_head.attention.self_attention; they are held between the heads anyway, so nothing is copied and the other values keep their bits."""
         eng = self._engine()
         feats = self._as_nhwc(features, eng)
         if len(feats) not in (3, 4):
@@ -163,7 +165,7 @@ class DynamicHead(nn.Module):
         t_host = torch.as_tensor(t).to("cpu", torch.int64)
         flag = self._bad_flag(init_bboxes.device)
         class_logits, bboxes, proposal_features = None, init_bboxes, None
-        kept, tails, inters, tiles = [], [], [], []
+        kept, tails, inters, tiles, objs = [], [], [], [], []
         for i in range(self.num_heads):
             if interact_inputs:
                 res = eng.rcnn_head(i, feats, height, width, bboxes, proposal_features, t_host, bad_flag=flag, keep_tail_input=tail_inputs,
@@ -179,9 +181,12 @@ class DynamicHead(nn.Module):
                 class_logits, bboxes, proposal_features = eng.rcnn_head(i, feats, height, width, bboxes, proposal_features, t_host, bad_flag=flag)
             if intermediate:
                 kept.append((class_logits, bboxes))
+            if obj_features:
+                objs.append(proposal_features)
         out = (torch.stack([k[0] for k in kept]), torch.stack([k[1] for k in kept])) if intermediate else (class_logits, bboxes)
         out = out + (torch.stack(tails),) if tail_inputs else out
-        return out + (torch.stack(inters), torch.stack(tiles)) if interact_inputs else out
+        out = out + (torch.stack(inters), torch.stack(tiles)) if interact_inputs else out
+        return out + (torch.stack(objs),) if obj_features else out
 
     # device flag standing in for `assert (pred_boxes[:, 2:] >= pred_boxes[:, :2]).all()` (box_head.py:588)
     def _bad_flag(self, device):

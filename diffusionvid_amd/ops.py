@@ -1409,6 +1409,50 @@ def inst_interact_backward(p, roi, params, d_y=None, forward_only=False, want_d_
     return out
 
 
+def self_attn_backward_scratch_bytes(n, m):
+    """bytes of scratch dvid_self_attn_backward needs for n images of m rows (-1: sizes it does not take)"""
+    return int(_lib.load().dvid_self_attn_backward_scratch_bytes(int(n), int(m)))
+
+
+def self_attn_backward(x, n, params, d_y=None, forward_only=False):
+    """An RCNNHead's self-attention with its residual and norm1 recomputed in fp32, and its gradient (dvid_self_attn_backward,
+    csrc/selfattn_bwd.hip; box_head.attention states the function).  x [n * m, 256], fp32 on the device, rows image-major: the m rows of each
+    of the n images attend to each other.  params {name without the head's prefix: fp32 device tensor in the reference's layout}, the six of
+    box_head.attention.PARAM_NAMES.  Cotangent d_y [n * m, 256]: None means zeros.  Returns a dict: "y", and -- unless forward_only -- "d_x"
+    and "param_grads" {name: gradient}, every element written.  include/dvid_hip.h states the arithmetic (fp32 MFMA products, fixed-order
+    sums without atomics: two runs give the same bits)."""
+    from .modeling.roi_heads.box_head.attention import NHEADS, PARAM_NAMES
+    x = _cuda(x, torch.float32)
+    n = int(n)
+    assert x.dim() == 2 and n >= 1 and x.shape[0] % n == 0, "x is [n * m, d]"
+    R, d = x.shape
+    m = R // n
+    plist = [_cuda(params[k].detach(), torch.float32) for k in PARAM_NAMES]
+    want = ((3 * d, d), (3 * d,), (d, d), (d,), (d,), (d,))
+    for k, t, shape in zip(PARAM_NAMES, plist, want):
+        assert tuple(t.shape) == shape, "%s is %s, expected %s" % (k, tuple(t.shape), shape)
+    dev = x.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = {"y": new(R, d)}
+    d_y = None if d_y is None else _cuda(d_y, torch.float32)
+    assert d_y is None or tuple(d_y.shape) == (R, d), "the cotangent has y's shape"
+    glist = []
+    if forward_only:
+        assert d_y is None, "a cotangent without a backward"
+    else:
+        out["d_x"] = new(R, d)
+        glist = [torch.empty_like(t) for t in plist]
+        out["param_grads"] = dict(zip(PARAM_NAMES, glist))
+    table = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+    ptable = table(plist)
+    gtable = table(glist) if glist else None
+    nbytes = self_attn_backward_scratch_bytes(n, m)
+    scratch = torch.empty((max(nbytes, 16) + 15) // 16 * 4, dtype=torch.float32, device=dev)
+    call("dvid_self_attn_backward", ptr(x), n, m, d, NHEADS, C.cast(ptable, C.c_void_p), len(plist), ptr(d_y), ptr(out["y"]), ptr(out.get("d_x")),
+         None if gtable is None else C.cast(gtable, C.c_void_p), ptr(scratch), scratch.numel() * 4, stream_ptr())
+    return out
+
+
 def set_criterion_scratch_bytes(S, n, M, gmax):
     """bytes of scratch dvid_set_criterion needs for S head outputs of n images with M queries and at most gmax boxes per image"""
     return int(_lib.load().dvid_set_criterion_scratch_bytes(int(S), int(n), int(M), int(gmax)))

@@ -763,6 +763,34 @@ int dvid_inst_interact_backward(const float* p, const float* roi, int rows, int 
 /* bytes of scratch for `rows` rows; -1 for a row count the entry refuses */
 int64_t dvid_inst_interact_backward_scratch_bytes(int rows);
 
+/* ---- the backward of the head's self-attention (dvid_version >= 16; csrc/selfattn_bwd.hip) ----
+ * dvid_self_attn_backward (dvid_version >= 16): an RCNNHead's self-attention with its residual and norm1 (box_head.py:514-518) recomputed in
+ * fp32, and its gradient: the link in front of dvid_inst_interact_backward, whose p is this function's y.  A head's x is the previous head's
+ * obj_features (the mean over the RoI bins for the first), so this function's d_x is the previous head's d_obj: with it the links compose over
+ * all heads.  The host mirror is modeling/roi_heads/box_head/attention.py (self_attention_host).  The function: x [n * m][256], rows
+ * image-major; the m rows of an image attend to each other, nheads = 8 heads of 32:
+ *   qkv = in_proj(x)   O = softmax(q k^T / sqrt 32) v per (image, head)   y = norm1(x + out_proj(O))
+ * dropout being the identity.  `params` is a HOST table of n_params = 6 device pointers, fp32 in the reference's names and row-major layouts,
+ * and `grads` a host table of the same length and shapes:
+ *   0 self_attn.in_proj_weight [768][256] (q, k, v rows in this order)   1 self_attn.in_proj_bias [768]
+ *   2 self_attn.out_proj.weight [256][256]                               3 self_attn.out_proj.bias [256]
+ *   4 norm1.weight [256]                                                 5 norm1.bias [256]
+ * Forward output y_out [n * m][256] (may be null).  Cotangent d_y [n * m][256]: null means zeros.  Gradient outputs d_x [n * m][256] and
+ * grads: every element is written.  With d_x and grads BOTH null the call is the forward alone.
+ * Arithmetic and order of summation as dvid_head_tail_backward: fp32 products on v_mfma_f32_32x32x2_f32, no atomics, sums over rows in chunks
+ * of DVID_HEAD_TAIL_BWD_ROW_CHUNK added in ascending order, two runs give the same bits.  The [m][m] probabilities are never stored: the
+ * forward keeps the log-sum-exp of every (row, head) and the backward forms P = exp(S - L) again in 32 x 32 tiles, once by query tiles (dQ,
+ * the key tiles in ascending order) and once by key tiles (dK and dV, the query tiles in ascending order); every element has one writer.
+ * Padded keys: rows past an image's last row in its last tile are staged as zeros and their probabilities are set to an exact 0, never
+ * exp(S - L) of what lies behind -- the next image's rows.  The scratch grows linearly with n * m.
+ * Refused before any launch, with the numbers: hidden other than 256, nheads other than 8, m above DVID_CRITERION_MAX_ROWS, n * m above
+ * DVID_HEAD_TAIL_BWD_MAX_ROWS, more than 65535 images (DVID_ERR_UNSUPPORTED); n < 1 or m < 1, n_params other than 6, null pointers, a
+ * cotangent without d_x and grads, a scratch smaller than dvid_self_attn_backward_scratch_bytes or not 16-byte aligned (DVID_ERR_ARG). */
+int dvid_self_attn_backward(const float* x, int n, int m, int hidden, int nheads, const float* const* params, int n_params, const float* d_y,
+                            float* y_out, float* d_x, float* const* grads, void* scratch, int64_t scratch_bytes, void* stream);
+/* bytes of scratch for n images of m rows; -1 for sizes the entry refuses */
+int64_t dvid_self_attn_backward_scratch_bytes(int n, int m);
+
 /* ---- options ------------------------------------------------------------------------------
  * The library's behaviour switches are ONE table set through this ABI, never through the environment (csrc/options.h; the defaults
  * are the benchmarked configuration).  Names: conv3x3, wstat, bneck_fuse (0 off / 1 by the layer's shape rule / 2 wherever the layer
